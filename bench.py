@@ -1,12 +1,14 @@
 #!/usr/bin/env python
 """bench.py -- images/sec of the Faster R-CNN R50-FPN training step on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL all-reduce of the gradient buckets)
 
 A step = forward + RPN/RCNN targets + losses + explicit backward + gradient all-reduce + SGD-momentum update on
 a synthetic batch of 2 images of 3x800x1333 (zero-padded to 1344) per GPU, inputs resident in HBM.
 Prints ONE JSON line (rank 0). See DESIGN.md section 7 for what each field means.
+A plain run sets up, warms up, times K steps and prints the line. --full adds what the headline figure does not need:
+the conv roofline pass (in-step kernel trace in a child process, per-launch timing) and the CPU baseline.
 """
 import argparse
 import json
@@ -25,6 +27,10 @@ G_MAX = 100
 # algorithmic conv-GEMM work per image: fwd 201.6 GMAC; training with conv1+C2 frozen
 TRAIN_CONV_FLOP_PER_IMAGE = 1.142e12
 MFMA_PEAK_BF16 = 2.5e15
+# --dump-outputs: names of the loss tensors a step returns, and how many parameter / gradient entries it samples
+LOSS_NAMES = {"faster_rcnn": ("rpn_loss", "rcnn_loss"), "mask_rcnn": ("rpn_loss", "rcnn_loss", "mask_loss"),
+              "retinanet": ("loss",)}
+DUMP_SAMPLE = 1 << 19
 
 
 def synth_batch(rank, step, device):
@@ -44,6 +50,26 @@ def synth_batch(rank, step, device):
             gt[n, k] = [x1, y1, x1 + w - 1, y1 + h - 1, float(rng.integers(1, 81))]
     im_info = torch.tensor([[IM_H, IM_W, 1.0]] * BATCH_PER_GPU, dtype=torch.float32)
     return img.to(device), torch.from_numpy(gt).to(device), im_info.to(device)
+
+
+def dump_outputs(out_dir, model, losses, names):
+    """--dump-outputs: what the last timed step gave its caller, as float32 DIR/<name>.npy -- the loss tensors it
+    returned, and the parameters it updated in place with the gradients it computed. The parameter arena is larger than
+    the 64 MB the dump may take, so the same seeded sample of its entries (alignment padding excluded) is written in
+    every run."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in zip(names, losses):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+    a = model.arena
+    offs = np.array([e[2] for e in a.entries], np.int64)
+    lens = np.array([e[3] for e in a.entries], np.int64)
+    ends = np.cumsum(lens)                                  # entries packed back to back, padding left out
+    k = np.sort(np.random.default_rng(0).choice(int(ends[-1]), size=min(DUMP_SAMPLE, int(ends[-1])), replace=False))
+    e = np.searchsorted(ends, k, side="right")              # entry that packed index k falls in
+    idx = torch.from_numpy(offs[e] + k - (ends[e] - lens[e])).to(a.w.device)
+    for name, t in (("params_sample", a.w), ("grads_sample", a.g)):
+        np.save(os.path.join(out_dir, name + ".npy"), t[idx].float().cpu().numpy())
 
 
 class ConvTimer:
@@ -380,10 +406,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--timeout", type=float, default=0.0,
                     help="--gpus N launcher only: overall deadline in seconds (0 = none); the ranks are stopped when it passes")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-conv-timer", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the conv roofline pass and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (losses, a seeded sample of the updated parameters "
+                         "and of their gradients) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-conv-timer", action="store_true", help="--full without the conv roofline pass")
     ap.add_argument("--no-instep", action="store_true",
-                    help="skip the in-step kernel timing (a child run under rocprofv3 --kernel-trace before the timed run)")
+                    help="--full without the in-step kernel timing (a child run under rocprofv3 --kernel-trace before "
+                         "the timed run)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--no-wgrad-stream", action="store_true", help="keep weight gradients on the main stream")
     ap.add_argument("--no-branch-stream", action="store_true", help="keep the RPN training branch on the main stream")
@@ -394,6 +426,9 @@ def main():
     ap.add_argument("--model", default="faster_rcnn", choices=["faster_rcnn", "mask_rcnn", "retinanet"],
                     help="faster_rcnn = BASELINE.json headline (configs 1-3); mask_rcnn = config 4; retinanet = config 5 (R101)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    conv_timer = args.full and not args.no_conv_timer
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Plain `python bench.py --gpus N`: this process becomes a launcher. It starts N fresh rank processes BEFORE
@@ -403,7 +438,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     instep = None
     under_profiler = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
-    if world == 1 and args.gpus == 1 and not (args.no_instep or args.no_conv_timer or args.no_graph or under_profiler) \
+    if world == 1 and args.gpus == 1 and conv_timer and not (args.no_instep or args.no_graph or under_profiler) \
             and args.input == "resident":
         instep = instep_profile(args.model)       # before this process touches the GPU
 
@@ -426,7 +461,7 @@ def main():
 
     from mxdetection_amd.models import FasterRCNN, RetinaNet
     timer = ConvTimer()
-    if not args.no_conv_timer:
+    if conv_timer:
         timer.install()
     if args.model == "retinanet":
         model = RetinaNet(device, depth=101, seed=7)
@@ -523,12 +558,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     loss_vals = [float(v) for v in torch.cat(list(losses)).cpu().numpy()]
+    if args.dump_outputs and rank == 0:      # before the roofline pass, which runs another step on the same model
+        dump_outputs(args.dump_outputs, model, losses, LOSS_NAMES[args.model])
     if feed is not None:
         feed.close()
 
     # roofline pass (every rank does the same local work; the gradient exchange is switched off for it)
     fam = {}
-    if not args.no_conv_timer:
+    if conv_timer:
         from mxdetection_amd.models.utils.dp import BucketReducer
         saved = model.reducer
         model.reducer = BucketReducer(model.arena.g, None)
@@ -653,7 +690,7 @@ def main():
             "hbm_frac": hbm_frac,
             "conv_families": families,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(rank)
         else:
             out["cpu_baseline"] = None
