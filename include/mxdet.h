@@ -429,6 +429,44 @@ int mxdet_filter_transpose(const uint16_t* w, int32_t Cout, int32_t KH, int32_t 
 int mxdet_filter_transpose_batched(const void* descs_dev, int32_t ndesc, int32_t total_tiles,
                                    mxdet_stream_t stream);
 
+/* Deformable convolution (DCN v1 / v2), MXNet role contrib.DeformableConvolution (Deformable-ConvNets'
+ * deformable_im2col semantics; dilation 1, 3x3 kernels only: anything else is MXDET_ESHAPE).
+ * x bf16 [N,H,W,C]; off bf16 [N,Ho,Wo,off_channels] (off_channels % 8 == 0) with G = groups deformable groups:
+ *   channel g*18 + 2k = dy, g*18 + 2k + 1 = dx of tap k = 3i + j; modulated (v2): channel 18G + 9g + k = the mask LOGIT;
+ *   channels past 18G (v1) / 27G (v2) are padding: read never, written zero by col2im_coord.
+ * Input channel c belongs to group g = c / (C/G) (C % (8G) == 0). Sample of output (n,ho,wo), tap (i,j), channel c at
+ *   p_y = ho*stride - pad + i + dy,  p_x = wo*stride - pad + j + dx:
+ *   0 if p_y <= -1, p_y >= H, p_x <= -1 or p_x >= W; else the bilinear mix of the four corners around
+ *   (floor(p_y), floor(p_x)), corners outside [0,H) x [0,W) reading 0; v2 multiplies it by sigmoid(logit) (fused: the
+ *   mask is never stored). Gradients w.r.t. p_y / p_x are those of that bilinear form with the floor held fixed
+ *   (one-sided at integer positions, as in MXNet).
+ * col bf16 [N,Ho,Wo,9*C], tap-major then channel: the [Cout,3,3,C] filter seen as [Cout,1,1,9C], so forward, data
+ * gradient and weight gradient are mxdet_conv2d_fwd / _dgrad / _wgrad as 1x1 convolutions on col. */
+typedef struct {
+  int32_t N, H, W, C;
+  int32_t Ho, Wo;             /* must equal (H + 2*pad - 3)/stride + 1 etc. */
+  int32_t KH, KW;             /* 3, 3 */
+  int32_t stride, pad;
+  int32_t groups;             /* deformable groups G */
+  int32_t modulated;          /* 1: v2 (mask logits in off) */
+  int32_t off_channels;       /* Coff */
+  int32_t accumulate;         /* col2im: add into dx instead of overwriting */
+} mxdet_deform_desc_t;
+/* col[n,ho,wo,k*C + c] = sample (bf16, one rounding) */
+int mxdet_deform_im2col(const mxdet_deform_desc_t* d, const uint16_t* x, const uint16_t* off, uint16_t* col,
+                        mxdet_stream_t stream);
+/* doff [N,Ho,Wo,off_channels] (fully written): per (pixel, tap, group) sum over the group's channels of
+ * dcol * d(sample)/d(p) (and, v2, dcol * sample * sigma'(logit)), channels reduced in a fixed order; bf16. */
+int mxdet_deform_col2im_coord(const mxdet_deform_desc_t* d, const uint16_t* x, const uint16_t* off,
+                              const uint16_t* dcol, uint16_t* doff, mxdet_stream_t stream);
+/* dx [N,H,W,C] (=, or += under accumulate) the adjoint of im2col applied to dcol, without float atomics: an inverted
+ * index (input pixel -> (output pixel, tap, corner, weight) entries in ascending (pixel, tap, corner) order; it depends
+ * on off only) and a gather that sums every pixel's entries in fp32 in that order, rounded to bf16 once -- bit-
+ * reproducible run to run. Workspace: mxdet_deform_col2im_workspace_bytes(d) (0 for an invalid descriptor). */
+size_t mxdet_deform_col2im_workspace_bytes(const mxdet_deform_desc_t* d);
+int mxdet_deform_col2im(const mxdet_deform_desc_t* d, const uint16_t* off, const uint16_t* dcol, uint16_t* dx,
+                        void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
+
 /* stem: 7x7 stride-2 pad-3 convolution reading the NCHW fp32/bf16 image [N,3,H,W] directly
  * (coalesced plane reads), + bias + ReLU, writing bf16 [N,Ho,Wo,64]; w bf16 [64,7,7,3]. */
 int mxdet_stem_conv7x7(const void* image, int32_t dtype, int32_t N, int32_t H, int32_t W,

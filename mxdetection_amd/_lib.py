@@ -57,6 +57,16 @@ class ConvDescT(C.Structure):
     ]
 
 
+class DeformDescT(C.Structure):
+    """mxdet_deform_desc_t (include/mxdet.h)."""
+    _fields_ = [
+        ("N", c_i32), ("H", c_i32), ("W", c_i32), ("C", c_i32),
+        ("Ho", c_i32), ("Wo", c_i32), ("KH", c_i32), ("KW", c_i32),
+        ("stride", c_i32), ("pad", c_i32), ("groups", c_i32), ("modulated", c_i32),
+        ("off_channels", c_i32), ("accumulate", c_i32),
+    ]
+
+
 WgradItemT._fields_ = [("desc", ConvDescT), ("x", c_vp), ("dy", c_vp), ("dw", c_vp), ("db", c_vp)]
 ConvItemT._fields_ = [("desc", ConvDescT), ("src", c_vp), ("filt", c_vp), ("bias", c_vp), ("residual", c_vp),
                       ("relu_mask", c_vp), ("dst", c_vp)]
@@ -142,6 +152,10 @@ SIGNATURES = {
     "mxdet_debug_force_wgrad_ksplit": (c_i32, [c_i32]),
     "mxdet_filter_transpose": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mxdet_filter_transpose_batched": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
+    "mxdet_deform_im2col": (c_i32, [P(DeformDescT), c_vp, c_vp, c_vp, c_vp]),
+    "mxdet_deform_col2im_coord": (c_i32, [P(DeformDescT), c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mxdet_deform_col2im_workspace_bytes": (c_sz, [P(DeformDescT)]),
+    "mxdet_deform_col2im": (c_i32, [P(DeformDescT), c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mxdet_stem_conv7x7": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mxdet_stem_conv7x7_pool": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mxdet_maxpool3x3s2": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),

@@ -11,7 +11,7 @@ import os
 import torch
 
 from ...ops import dense
-from ..utils.layers import ConvLayer, cached_buf
+from ..utils.layers import ConvLayer, DeformConvLayer, cached_buf
 
 
 BITMASKS = os.environ.get("MXDET_TUNE_RELU_BITS", "1") == "1"      # 1-bit ReLU masks for the backbone's data gradients
@@ -22,14 +22,21 @@ CHAIN3_FROZEN = os.environ.get("MXDET_TUNE_CHAIN", "2") not in ("0", "1")
 
 
 class Bottleneck:
-    def __init__(self, name, cin, planes, stride, downsample, trainable, need_dx, arena, ws, device, gen):
+    def __init__(self, name, cin, planes, stride, downsample, trainable, need_dx, arena, ws, device, gen, dcn=None):
+        """dcn: None, or {"groups": G, "modulated": bool} -- conv2 is then a deformable convolution (trainable blocks)."""
         kw = dict(arena=arena, ws=ws, device=device, gen=gen, trainable=trainable, train_bias=False)
         self.trainable, self.need_dx = trainable, need_dx
-        # registered in backward completion order: conv3, conv2, conv1 / downsample
+        # registered in backward completion order: conv3, conv2 (+ its offset conv), conv1 / downsample
         # random-init stand-in for pretrained weights: the residual branch's last conv starts small so that
         # activations stay O(1) through 16 blocks without live BatchNorm statistics (frozen BN is identity here)
         self.conv3 = ConvLayer(name + ".conv3", planes, planes * 4, 1, init_std=0.25 * (2.0 / planes) ** 0.5, **kw)
-        self.conv2 = ConvLayer(name + ".conv2", planes, planes, 3, stride, **kw)
+        self.dcn = dcn is not None
+        if self.dcn:
+            assert trainable, "deformable convolutions only in trainable stages"
+            self.conv2 = DeformConvLayer(name + ".conv2", planes, planes, stride, dcn["groups"], dcn["modulated"],
+                                         arena=arena, ws=ws, device=device, gen=gen)
+        else:
+            self.conv2 = ConvLayer(name + ".conv2", planes, planes, 3, stride, **kw)
         self.conv1 = ConvLayer(name + ".conv1", cin, planes, 1, **kw)
         self.down = ConvLayer(name + ".down", cin, planes * 4, 1, stride, 0, **kw) if downsample else None
         self.x = self.a1 = self.a2 = self.y = self.sc = None
@@ -37,7 +44,8 @@ class Bottleneck:
         self.y_key = "y"      # name of the output buffer (ResNet.forward_front switches the frozen front end's between two)
 
     def layers(self):
-        return [l for l in (self.conv3, self.conv2, self.conv1, self.down) if l is not None]
+        c2 = self.conv2.layers() if self.dcn else [self.conv2]
+        return [l for l in [self.conv3] + c2 + [self.conv1, self.down] if l is not None]
 
     def _buf(self, key, shape):
         return cached_buf(self.bufs, key, shape, torch.bfloat16, self.conv1.device)
@@ -140,9 +148,17 @@ class Bottleneck:
 class ResNet:
     """depth 50: (3,4,6,3), depth 101: (3,4,23,3). Returns C2..C5 (bf16 channels-last)."""
 
-    def __init__(self, depth, arena, ws, device, gen, frozen_stages=1):
+    def __init__(self, depth, arena, ws, device, gen, frozen_stages=1, dcn_stages=(), dcn_modulated=True, dcn_groups=1):
+        """dcn_stages: subset of {3, 4, 5} (C3..C5, trainable stages only) whose blocks use a deformable conv2 (DCN v2
+        with dcn_modulated, else v1; dcn_groups deformable groups), the stride-2 first block included."""
         blocks = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3)}[depth]
         self.device = device
+        dcn_stages = set(int(s) for s in dcn_stages)
+        bad = [s for s in dcn_stages if s not in (3, 4, 5) or s - 2 < max(1, frozen_stages)]
+        if bad:
+            raise ValueError("dcn_stages %s: only trainable stages among 3, 4, 5" % sorted(bad))
+        self.dcn_stages = sorted(dcn_stages)
+        dcn = {"groups": int(dcn_groups), "modulated": bool(dcn_modulated)}
         # registration order == backward completion order: layer4 ... layer2 (layer1 + stem frozen)
         self.stages = [None] * 4
         cins = [64, 256, 512, 1024]
@@ -155,7 +171,8 @@ class ResNet:
                 stride = 2 if (bi == 0 and si > 0) else 1
                 need_dx = trainable and not (bi == 0 and (si == 0 or si - 1 < frozen_stages))
                 stage.insert(0, Bottleneck("layer%d.%d" % (si + 1, bi), cin, planes, stride, bi == 0, trainable,
-                                           need_dx, arena, ws, device, gen))
+                                           need_dx, arena, ws, device, gen,
+                                           dcn=dcn if si + 2 in dcn_stages else None))
             self.stages[si] = stage
         self.stem_w = (torch.randn((64, 7, 7, 3), generator=gen) * (2.0 / 147) ** 0.5).to(torch.bfloat16).to(device)
         self.stem_b = torch.zeros((64,), dtype=torch.float32, device=device)

@@ -5,12 +5,13 @@ neck, heads named in an experiment file, /root/reference/README.md:7,13)."""
 def build_detector(cfg, device="cuda"):
     from . import FasterRCNN, RetinaNet
     net, tr = cfg.network, cfg.TRAIN
+    dcn = dict(dcn_stages=tuple(net.dcn_stages), dcn_modulated=bool(net.dcn_modulated), dcn_groups=int(net.dcn_groups))
     if net.type in ("faster_rcnn", "mask_rcnn"):
         model = FasterRCNN(device, depth=net.backbone_depth, num_classes=net.num_classes, seed=net.seed,
                            rois_per_image=tr.batch_rois, pre_nms_top_n=tr.rpn_pre_nms_top_n,
-                           post_nms_top_n=tr.rpn_post_nms_top_n, with_mask=(net.type == "mask_rcnn"))
+                           post_nms_top_n=tr.rpn_post_nms_top_n, with_mask=(net.type == "mask_rcnn"), **dcn)
     elif net.type == "retinanet":
-        model = RetinaNet(device, depth=net.backbone_depth, num_classes=net.num_classes - 1, seed=net.seed)
+        model = RetinaNet(device, depth=net.backbone_depth, num_classes=net.num_classes - 1, seed=net.seed, **dcn)
     else:
         raise ValueError("unknown network.type %r" % (net.type,))
     if net.pretrained:

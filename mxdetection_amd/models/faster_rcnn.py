@@ -21,7 +21,9 @@ from .utils.layers import Workspace
 
 class FasterRCNN(DetectorBase):
     def __init__(self, device="cuda", depth=50, num_classes=81, seed=7, rpn_seed=99, rois_per_image=512,
-                 pre_nms_top_n=2000, post_nms_top_n=2000, with_mask=False):
+                 pre_nms_top_n=2000, post_nms_top_n=2000, with_mask=False, dcn_stages=(), dcn_modulated=True,
+                 dcn_groups=1):
+        """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet)."""
         gen = torch.Generator().manual_seed(seed)
         self._init_base(device)
         self.strides = [4, 8, 16, 32, 64]
@@ -49,7 +51,8 @@ class FasterRCNN(DetectorBase):
         self.mark_rpn = self.arena.size
         self.neck = FPN([256, 512, 1024, 2048], 256, self.arena, self.ws, device, gen)
         self.mark_fpn = self.arena.size
-        self.backbone = ResNet(depth, self.arena, self.ws, device, gen)
+        self.backbone = ResNet(depth, self.arena, self.ws, device, gen, dcn_stages=dcn_stages,
+                               dcn_modulated=dcn_modulated, dcn_groups=dcn_groups)
         self.roi_extractor = FPNRoIExtractor(self.strides[:4], device=device)
         layers = self.bbox_head.layers() + self.rpn_head.layers() + self.neck.layers() + self.backbone.layers()
         if with_mask:

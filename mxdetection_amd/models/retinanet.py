@@ -9,7 +9,8 @@ from .utils.detector import DetectorBase
 
 
 class RetinaNet(DetectorBase):
-    def __init__(self, device="cuda", depth=101, num_classes=80, seed=7):
+    def __init__(self, device="cuda", depth=101, num_classes=80, seed=7, dcn_stages=(), dcn_modulated=True, dcn_groups=1):
+        """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet)."""
         gen = torch.Generator().manual_seed(seed)
         self._init_base(device)
         self.strides = [8, 16, 32, 64, 128]
@@ -17,7 +18,8 @@ class RetinaNet(DetectorBase):
         self.mark_head = self.arena.size
         self.neck = RetinaFPN([512, 1024, 2048], 256, self.arena, self.ws, device, gen)
         self.mark_fpn = self.arena.size
-        self.backbone = ResNet(depth, self.arena, self.ws, device, gen)
+        self.backbone = ResNet(depth, self.arena, self.ws, device, gen, dcn_stages=dcn_stages,
+                               dcn_modulated=dcn_modulated, dcn_groups=dcn_groups)
         self._finalize_params(self.head.layers() + self.neck.layers() + self.backbone.layers())
         self.head.post_materialize()
         self.stage_marks = {}

@@ -104,7 +104,10 @@ class DetectorBase:
         t = t[:real].float()
         if t.dim() == 4:
             hwc = getattr(layer, "fc_in_hwc", None) if layer is not None else None
-            if hwc is not None:
+            khwc = getattr(layer, "dcn_khwc", None) if layer is not None else None
+            if khwc is not None:          # deformable filter held as [O,1,1,9C]: stored as the 3x3 filter it is (OIHW)
+                t = t.reshape(t.shape[0], *khwc).permute(0, 3, 1, 2)
+            elif hwc is not None:
                 O = t.shape[0]
                 if len(hwc) == 3:
                     t = t.reshape(O, *hwc).permute(0, 3, 1, 2)
@@ -119,7 +122,9 @@ class DetectorBase:
         src = torch.from_numpy(a).to(like.device)
         if like.dim() == 4:
             hwc = getattr(layer, "fc_in_hwc", None) if layer is not None else None
-            if hwc is not None:
+            if getattr(layer, "dcn_khwc", None) is not None:
+                src = src.permute(0, 2, 3, 1).reshape(src.shape[0], *like.shape[1:])
+            elif hwc is not None:
                 O = src.shape[0]
                 if len(hwc) == 3:
                     src = src.reshape(O, hwc[2], hwc[0], hwc[1]).permute(0, 2, 3, 1)

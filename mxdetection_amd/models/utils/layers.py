@@ -236,3 +236,78 @@ class ConvLayer:
         else:
             with ctx:
                 dense.conv2d_wgrad(x, dy, self.k, self.k, self.stride, self.pad, dw, db, accumulate, self.ws.get())
+
+
+class DeformConvLayer:
+    """3x3 deformable convolution (DCN v1, or v2 with `modulated`), MXNet role contrib.DeformableConvolution; the
+    drop-in for a bottleneck's conv2 ("Deformable convolution").
+
+    Two trainable parts:
+      * `offset`: a plain 3x3 ConvLayer at the layer's stride, with bias, that predicts the offsets (and v2 mask logits)
+        -- 18G (27G) real output channels padded to a multiple of 64 (mxdet_conv2d_dgrad needs Cout % 64), zero at
+        the start as DCN prescribes (a zero filter draws no random numbers, so the rest of a model initialises exactly
+        as without DCN);
+      * `conv`: the deformable filter [Cout,3,3,C] held as the 1x1 filter [Cout,1,1,9C] of the column tensor (same bytes,
+        same He-normal draw). Checkpoints store it in OIHW [Cout,C,3,3] under this layer's plain name (dcn_khwc).
+    Forward: offset conv -> im2col -> 1x1 forward on col (bias, ReLU, 1-bit mask from the existing epilogue). col is
+    kept for the backward pass. Backward: 1x1 data gradient into dcol -> col2im_coord (doff) -> col2im (unmasked dx) ->
+    offset-conv data gradient with residual = dx and the input's ReLU mask; the weight gradients of both parts go
+    through Workspace.defer like every other layer's."""
+
+    def __init__(self, name, cin, cout, stride=1, groups=1, modulated=True, arena=None, ws=None, device="cuda", gen=None,
+                 train_bias=False):
+        self.name, self.cin, self.cout, self.stride, self.pad = name, cin, cout, stride, 1
+        self.groups, self.modulated = groups, bool(modulated)
+        self.k = 3
+        self.trainable = True
+        self.conv = ConvLayer(name, 9 * cin, cout, 1, 1, 0, arena=arena, ws=ws, device=device, gen=gen,
+                              train_bias=train_bias)
+        self.conv.dcn_khwc = (3, 3, cin)
+        nreal = (27 if self.modulated else 18) * groups
+        self.offset = ConvLayer(name + "_offset", cin, (nreal + 63) // 64 * 64, 3, stride, 1, arena=arena, ws=ws,
+                                device=device, gen=gen, zero_init=True, cout_real=nreal)
+        self.ws = ws
+        self.device = device
+        self.bufs = {}
+        self.x = self.off = self.col = None
+
+    def layers(self):
+        """Registration (= backward completion) order: the deformable filter's gradient is final first."""
+        return [self.conv, self.offset]
+
+    def _buf(self, key, shape, dtype=torch.bfloat16):
+        return cached_buf(self.bufs, key, shape, dtype, self.device)
+
+    def out_shape(self, x_shape):
+        return self.offset.out_shape(x_shape)[:3] + (self.cout,)
+
+    def plan(self, x_shape):
+        N, Ho, Wo, _ = self.out_shape(x_shape)
+        self.offset.plan(x_shape)
+        self.conv.plan((N, Ho, Wo, 9 * self.cin))
+
+    def forward(self, x, relu=False, residual=None, out=None, bits_out=None):
+        from ...ops import deform_conv
+        N, Ho, Wo, _ = self.out_shape(x.shape)
+        off = self.offset.forward(x, out=self._buf("off", (N, Ho, Wo, self.offset.cout)))
+        col = deform_conv.im2col(x, off, self.stride, self.pad, self.groups, self.modulated,
+                                 out=self._buf("col", (N, Ho, Wo, 9 * self.cin)))
+        self.x, self.off, self.col = x, off, col
+        return self.conv.forward(col, relu=relu, residual=residual, out=out, bits_out=bits_out)
+
+    def backward_weight(self, x, dy, accumulate=False):
+        """The deformable filter's gradient (1x1 on col); the offset conv's follows in backward_data, once doff exists."""
+        self.conv.backward_weight(self.col, dy, accumulate)
+
+    def backward_data(self, dy, x_shape, residual=None, relu_mask=None, accumulate=False, out=None, relu_bits=None):
+        from ...ops import deform_conv
+        assert residual is None and not accumulate, "DeformConvLayer.backward_data: no residual / accumulate"
+        x_shape = tuple(x_shape)
+        dcol = self.conv.backward_data(dy, self.col.shape, out=self._buf("dcol", self.col.shape))
+        a = (self.stride, self.pad, self.groups, self.modulated)
+        doff = deform_conv.col2im_coord(self.x, self.off, dcol, *a, out=self._buf("doff", self.off.shape))
+        nws = deform_conv.col2im_workspace_bytes(x_shape, *a, self.off.shape[3])
+        dxu = deform_conv.col2im(self.off, dcol, x_shape, *a, out=self._buf("dxu", x_shape),
+                                 workspace=self._buf("c2i_ws", (max(nws, 256),), torch.uint8))
+        self.offset.backward_weight(self.x, doff)
+        return self.offset.backward_data(doff, x_shape, residual=dxu, relu_mask=relu_mask, out=out, relu_bits=relu_bits)

@@ -38,6 +38,9 @@ DEFAULTS = {
         "num_classes": 81,                # incl. background for the two-stage models; retinanet uses num_classes - 1
         "pretrained": "",                 # MXNet .params with ImageNet ResNet weights (utils.params_io)
         "seed": 7,
+        "dcn_stages": [],                 # backbone stages (subset of 3, 4, 5) whose conv2 is deformable (contrib.DeformableConvolution)
+        "dcn_modulated": True,            # DCN v2 (sigmoid mask) when true, v1 otherwise
+        "dcn_groups": 1,                  # deformable groups
     },
     "dataset": {
         "type": "synthetic",              # synthetic | coco | voc (ann_file = Annotations directory)

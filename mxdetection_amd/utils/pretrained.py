@@ -43,6 +43,7 @@ def load_pretrained_backbone(model, params, depth=50, names=None, eps=2e-5, fix_
     if not isinstance(blob, dict):
         raise ValueError("the .params file carries no names (NDArray list), cannot map it onto the backbone")
     tensors = {n: t for n, _, t, _ in model._named_tensors()}
+    layers = {n: l for n, _, _, l in model._named_tensors()}
     missing = []
     for ours, wname, bn in (names or resnet_v1_names(depth)):
         w = _get(blob, wname)
@@ -53,6 +54,9 @@ def load_pretrained_backbone(model, params, depth=50, names=None, eps=2e-5, fix_
         wf, bf = fold_batchnorm(w, stats[0], stats[1], stats[2], stats[3], eps=eps, fix_gamma=fix_gamma)
         tw, tb = tensors[ours + ".weight"], tensors[ours + ".bias"]
         src = torch.from_numpy(wf).permute(0, 2, 3, 1).contiguous()             # OIHW -> [Cout,KH,KW,Cin]
+        khwc = getattr(layers[ours + ".weight"], "dcn_khwc", None)
+        if khwc is not None and tuple(src.shape[1:]) == tuple(khwc):
+            src = src.reshape(tw.shape)          # deformable conv2: the same filter, held as [Cout,1,1,9*Cin]
         if tuple(src.shape) != tuple(tw.shape):
             raise ValueError("%s: %s has shape %s, the model expects %s" % (ours, wname, tuple(src.shape), tuple(tw.shape)))
         tw.copy_(src.to(tw.device).to(tw.dtype))

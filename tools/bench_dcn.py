@@ -1,0 +1,58 @@
+"""Training throughput of Faster R-CNN R50-FPN with deformable convolutions in the backbone, one configuration per
+process, on the synthetic batch and with the warm-up / capture / replay protocol of bench.py (2 images of 3x800x1333
+padded to 1344, weight gradients grouped on a side stream, RPN branch on its own stream, whole step replayed).
+
+    python tools/bench_dcn.py --dcn-stages 3,4,5 --modulated 1 --groups 1 --steps 30 --warmup 5
+    python tools/bench_dcn.py --dcn-stages ''              # the plain model, same protocol
+
+Prints one JSON line: {"dcn_stages", "modulated", "groups", "img_per_s", "step_ms", "losses"}.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dcn-stages", default="3,4,5", help="comma-separated subset of 3,4,5; empty = plain model")
+    ap.add_argument("--modulated", type=int, default=1)
+    ap.add_argument("--groups", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    args = ap.parse_args()
+    import torch
+    from bench import BATCH_PER_GPU, synth_batch
+    from mxdetection_amd.models import FasterRCNN
+    stages = tuple(int(s) for s in args.dcn_stages.split(",") if s.strip())
+    device = "cuda"
+    model = FasterRCNN(device, depth=50, seed=7, dcn_stages=stages, dcn_modulated=bool(args.modulated),
+                       dcn_groups=args.groups)
+    model.enable_wgrad_stream()
+    model.enable_branch_stream()
+    model.enable_grouped_wgrad()
+    lr = 0.02 * BATCH_PER_GPU / 16.0 / 3.0
+    batches = [synth_batch(0, s, device) for s in range(4)]
+    model.capture(*batches[0], lr=lr, image_offset=0)
+    for i in range(args.warmup):
+        img, gt, info = batches[i % len(batches)]
+        model.replay(img, gt, info, i)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        img, gt, info = batches[(args.warmup + i) % len(batches)]
+        losses = model.replay(img, gt, info, args.warmup + i)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    vals = [float(v) for v in torch.cat(list(losses)).cpu().numpy()]
+    print(json.dumps({"dcn_stages": list(stages), "modulated": bool(args.modulated), "groups": args.groups,
+                      "img_per_s": round(BATCH_PER_GPU * args.steps / dt, 2),
+                      "step_ms": round(1e3 * dt / args.steps, 3), "losses": vals}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
