@@ -205,6 +205,45 @@ int mxdet_roi_align_bwd_gather_prepared(const mxdet_feat_pyramid_t* f, int32_t N
                                         const uint16_t* grad_out, int32_t accumulate, void* workspace,
                                         size_t workspace_bytes, mxdet_stream_t stream);
 
+/* (Modulated) deformable RoI pooling, MXNet role contrib.DeformablePSROIPooling with group_size 1, part_size = pooled,
+ * output_dim = C, class-agnostic offsets (mmdetection dpool / mdpool), over the same pyramid and level map as RoIAlign,
+ * one launch for all levels. For roi r (batch n = rois[r][0], box x1,y1,x2,y2, level l, s = spatial_scale[l]):
+ *   rsw = round(x1)*s - 0.5, rew = (round(x2) + 1)*s - 0.5 (C round: half away from zero; likewise h with y1, y2),
+ *   roi_w = max(rew - rsw, 0.1), bin_w = roi_w / PW, sub_w = bin_w / S; tx = trans[r][ph*PW + pw] * trans_std,
+ *   ty = trans[r][PH*PW + ph*PW + pw] * trans_std (0 without trans); wstart = (pw*bin_w + rsw) + tx*roi_w (h alike);
+ *   samples w = wstart + iw*sub_w, h = hstart + ih*sub_h (ih, iw in [0,S)), skipped outside [-0.5, W-0.5] x
+ *   [-0.5, H-0.5], else clamped to [0, W-1] x [0, H-1] and mixed bilinearly from floor / ceil corners;
+ *   out[r,ph,pw,c] = count ? sum/count : 0, modulated: times sigmoid(mask_logit[r][ph*PW + pw]). bf16, rounded once.
+ * trans / mask_logit: bf16 rows of trans_stride / mask_stride elements (columns past 2*PH*PW / PH*PW are padding, never
+ * read). A call without trans (trans == NULL) is the no-trans pass; modulated needs trans and mask_logit. */
+typedef struct {
+  mxdet_feat_pyramid_t pyr;   /* fwd / bwd_trans: the features; bwd_feat: the bf16 GRADIENT maps */
+  int32_t N, C;               /* C % 8 == 0 */
+  int32_t PH, PW;             /* PH * PW <= 64 */
+  int32_t sample_per_part;    /* S in [1, 16] */
+  float trans_std;
+  int32_t modulated;
+  int32_t trans_stride, mask_stride;
+  int32_t accumulate;         /* bwd_feat: add into the maps instead of overwriting */
+} mxdet_dpool_desc_t;
+int mxdet_dpool_fwd(const mxdet_dpool_desc_t* d, const float* rois, const int32_t* levels, int64_t R,
+                    const uint16_t* trans, const uint16_t* mask_logit, uint16_t* out, mxdet_stream_t stream);
+/* d_trans [R, trans_stride], d_mask [R, mask_stride] (modulated), both written in full (padding columns zero):
+ *   d_tx = sum_{samples, c} (U(y1,x1)*dy + U(y0,x1)*(1-dy) - U(y1,x0)*dy - U(y0,x0)*(1-dy)) * trans_std * roi_w * g_c,
+ *   g_c = dout[r,ph,pw,c] (* sigmoid) / count, d_ty alike; d_mask = sum_c dout * (sum/count) * sigma * (1 - sigma).
+ *   Channels reduced in a fixed order (one wave per (roi, bin), a fixed butterfly). Needs trans. */
+int mxdet_dpool_bwd_trans(const mxdet_dpool_desc_t* d, const float* rois, const int32_t* levels, int64_t R,
+                          const uint16_t* trans, const uint16_t* mask_logit, const uint16_t* dout, uint16_t* d_trans,
+                          uint16_t* d_mask, mxdet_stream_t stream);
+/* The feature adjoint: d->pyr.feat[l] (=, or += under accumulate) the transpose of the pooling applied to dout, without
+ * float atomics: per-bin records, then a gather in which every 8-pixel row segment walks the rois that reach it
+ * (ascending), their bins (ascending) and samples (ih, iw) and sums in fp32 in that order, rounding once. Bit-
+ * reproducible, any overlap. R <= 65535, level sides < 32768. Workspace: mxdet_dpool_bwd_feat_workspace_bytes. */
+size_t mxdet_dpool_bwd_feat_workspace_bytes(const mxdet_dpool_desc_t* d, int64_t R);
+int mxdet_dpool_bwd_feat(const mxdet_dpool_desc_t* d, const float* rois, const int32_t* levels, int64_t R,
+                         const uint16_t* trans, const uint16_t* mask_logit, const uint16_t* dout, void* workspace,
+                         size_t workspace_bytes, mxdet_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * core/loss (README.md:19)
  * smooth-L1 (MXNet smooth_l1(scalar=sigma)): elementwise on (pred - target) * weight. */

@@ -67,6 +67,15 @@ class DeformDescT(C.Structure):
     ]
 
 
+class DpoolDescT(C.Structure):
+    """mxdet_dpool_desc_t (include/mxdet.h)."""
+    _fields_ = [
+        ("pyr", FeatPyramidT), ("N", c_i32), ("C", c_i32), ("PH", c_i32), ("PW", c_i32),
+        ("sample_per_part", c_i32), ("trans_std", c_f32), ("modulated", c_i32),
+        ("trans_stride", c_i32), ("mask_stride", c_i32), ("accumulate", c_i32),
+    ]
+
+
 WgradItemT._fields_ = [("desc", ConvDescT), ("x", c_vp), ("dy", c_vp), ("dw", c_vp), ("db", c_vp)]
 ConvItemT._fields_ = [("desc", ConvDescT), ("src", c_vp), ("filt", c_vp), ("bias", c_vp), ("residual", c_vp),
                       ("relu_mask", c_vp), ("dst", c_vp)]
@@ -156,6 +165,10 @@ SIGNATURES = {
     "mxdet_deform_col2im_coord": (c_i32, [P(DeformDescT), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mxdet_deform_col2im_workspace_bytes": (c_sz, [P(DeformDescT)]),
     "mxdet_deform_col2im": (c_i32, [P(DeformDescT), c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_dpool_fwd": (c_i32, [P(DpoolDescT), c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "mxdet_dpool_bwd_trans": (c_i32, [P(DpoolDescT), c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mxdet_dpool_bwd_feat_workspace_bytes": (c_sz, [P(DpoolDescT), c_i64]),
+    "mxdet_dpool_bwd_feat": (c_i32, [P(DpoolDescT), c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mxdet_stem_conv7x7": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mxdet_stem_conv7x7_pool": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mxdet_maxpool3x3s2": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),

@@ -7,10 +7,14 @@ def build_detector(cfg, device="cuda"):
     net, tr = cfg.network, cfg.TRAIN
     dcn = dict(dcn_stages=tuple(net.dcn_stages), dcn_modulated=bool(net.dcn_modulated), dcn_groups=int(net.dcn_groups))
     if net.type in ("faster_rcnn", "mask_rcnn"):
+        dpool = dict(roi_pool=str(net.roi_pool), dpool_trans_std=float(net.dpool_trans_std),
+                     dpool_sample_per_part=int(net.dpool_sample_per_part), dpool_offset_fcs=int(net.dpool_offset_fcs))
         model = FasterRCNN(device, depth=net.backbone_depth, num_classes=net.num_classes, seed=net.seed,
                            rois_per_image=tr.batch_rois, pre_nms_top_n=tr.rpn_pre_nms_top_n,
-                           post_nms_top_n=tr.rpn_post_nms_top_n, with_mask=(net.type == "mask_rcnn"), **dcn)
+                           post_nms_top_n=tr.rpn_post_nms_top_n, with_mask=(net.type == "mask_rcnn"), **dcn, **dpool)
     elif net.type == "retinanet":
+        if net.roi_pool != "roi_align":
+            raise ValueError("network.roi_pool = %r: retinanet has no RoI branch" % (net.roi_pool,))
         model = RetinaNet(device, depth=net.backbone_depth, num_classes=net.num_classes - 1, seed=net.seed, **dcn)
     else:
         raise ValueError("unknown network.type %r" % (net.type,))

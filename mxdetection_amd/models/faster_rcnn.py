@@ -13,7 +13,7 @@ from .backbones import ResNet
 from .bbox_heads import BBoxHead
 from .mask_heads import FCNMaskHead
 from .necks import FPN
-from .roi_extractors import FPNRoIExtractor
+from .roi_extractors import DeformRoIExtractor, FPNRoIExtractor
 from .rpn_heads import RPNHead
 from .utils.detector import DetectorBase
 from .utils.layers import Workspace
@@ -22,8 +22,14 @@ from .utils.layers import Workspace
 class FasterRCNN(DetectorBase):
     def __init__(self, device="cuda", depth=50, num_classes=81, seed=7, rpn_seed=99, rois_per_image=512,
                  pre_nms_top_n=2000, post_nms_top_n=2000, with_mask=False, dcn_stages=(), dcn_modulated=True,
-                 dcn_groups=1):
-        """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet)."""
+                 dcn_groups=1, roi_pool="roi_align", dpool_trans_std=0.1, dpool_sample_per_part=4, dpool_offset_fcs=3):
+        """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
+        roi_pool: the box branch's RoI pooling -- 'roi_align', or deformable RoI pooling with its offset head, 'dpool'
+        (v1) / 'mdpool' (v2, modulated) (roi_extractors.DeformRoIExtractor, options dpool_*). The mask branch keeps its
+        14x14 RoIAlign."""
+        if roi_pool not in ("roi_align", "dpool", "mdpool"):
+            raise ValueError("roi_pool must be 'roi_align', 'dpool' or 'mdpool' (got %r)" % (roi_pool,))
+        self.roi_pool = roi_pool
         gen = torch.Generator().manual_seed(seed)
         self._init_base(device)
         self.strides = [4, 8, 16, 32, 64]
@@ -42,6 +48,12 @@ class FasterRCNN(DetectorBase):
         self.mark_mask = self.arena.size
         self.bbox_head = BBoxHead(7 * 7 * 256, self.arena, self.ws, device, gen, num_classes=num_classes,
                                   rois_per_image=rois_per_image, seed=rpn_seed)
+        self.dpool = None
+        if roi_pool != "roi_align":
+            # the offset head belongs to the head bucket: its backward runs in the slot of the RoI extractor's
+            self.dpool = DeformRoIExtractor(self.strides[:4], 256, self.arena, self.ws, device,
+                                            modulated=(roi_pool == "mdpool"), trans_std=dpool_trans_std,
+                                            sample_per_part=dpool_sample_per_part, offset_fcs=dpool_offset_fcs)
         self.mark_head = self.arena.size
         # own wgrad scratch: the RPN training branch runs on its own stream (enable_branch_stream) and must not
         # share the split-K slabs with the weight-gradient stream of the rest of the model
@@ -53,8 +65,9 @@ class FasterRCNN(DetectorBase):
         self.mark_fpn = self.arena.size
         self.backbone = ResNet(depth, self.arena, self.ws, device, gen, dcn_stages=dcn_stages,
                                dcn_modulated=dcn_modulated, dcn_groups=dcn_groups)
-        self.roi_extractor = FPNRoIExtractor(self.strides[:4], device=device)
-        layers = self.bbox_head.layers() + self.rpn_head.layers() + self.neck.layers() + self.backbone.layers()
+        self.roi_extractor = self.dpool if self.dpool is not None else FPNRoIExtractor(self.strides[:4], device=device)
+        layers = self.bbox_head.layers() + (self.dpool.layers() if self.dpool is not None else [])
+        layers += self.rpn_head.layers() + self.neck.layers() + self.backbone.layers()
         if with_mask:
             layers = self.mask_head.layers() + layers
         self._finalize_params(layers)
@@ -77,6 +90,8 @@ class FasterRCNN(DetectorBase):
         p_shapes.append((N, (p_shapes[-1][1] + 1) // 2, (p_shapes[-1][2] + 1) // 2, 256))
         self.rpn_head.plan(p_shapes, g_max)
         self.bbox_head.plan(N)
+        if self.dpool is not None:
+            self.dpool.plan(N * self.bbox_head.R)
         if self.with_mask:
             self.mask_head.plan(N)
         self.ws.get()
@@ -139,6 +154,9 @@ class FasterRCNN(DetectorBase):
             # gradients, is +0.3 % on the step. MXDET_TUNE_ROI_FIRST=0: the round-2 order, bucket first)
             lo = 0
             roi_first = os.environ.get("MXDET_TUNE_ROI_FIRST", "1") == "1"     # the gather first, alone; the bucket behind it
+            # deformable RoI pooling: its offset head's weight gradients belong to the head bucket, so the bucket closes
+            # behind the extractor's backward
+            roi_first = roi_first or self.dpool is not None
             if self._bucket_here(0) and not roi_first:
                 self._reduce(0, self.mark_rpn, pre=self.ws_rpn if defer_rpn else None)
                 lo = self.mark_rpn
@@ -149,6 +167,7 @@ class FasterRCNN(DetectorBase):
                 self._reduce(0, self.mark_rpn, pre=self.ws_rpn if defer_rpn else None)
                 lo = self.mark_rpn
         else:
+            assert self.dpool is None, "deformable RoI pooling has the gather-form backward only (roi_bwd_gather)"
             acc = self.roi_extractor.backward(d_pooled.view(pooled.shape), self.dP[:4], finalize=False)
             if self.with_mask:
                 self.mask_roi_extractor.backward(d_mpooled, self.dP[:4], shared_acc=acc, zero=False, finalize=False)

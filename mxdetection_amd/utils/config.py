@@ -41,6 +41,10 @@ DEFAULTS = {
         "dcn_stages": [],                 # backbone stages (subset of 3, 4, 5) whose conv2 is deformable (contrib.DeformableConvolution)
         "dcn_modulated": True,            # DCN v2 (sigmoid mask) when true, v1 otherwise
         "dcn_groups": 1,                  # deformable groups
+        "roi_pool": "roi_align",          # box branch pooling: roi_align | dpool | mdpool (contrib.DeformablePSROIPooling)
+        "dpool_trans_std": 0.1,           # scale of the predicted bin offsets (in roi widths / heights)
+        "dpool_sample_per_part": 4,       # samples per bin and axis
+        "dpool_offset_fcs": 3,            # FCs of the offset head (1: Deformable-ConvNets' FPN head, 3: DCN v2 / mmdetection)
     },
     "dataset": {
         "type": "synthetic",              # synthetic | coco | voc (ann_file = Annotations directory)

@@ -4,8 +4,9 @@ padded to 1344, weight gradients grouped on a side stream, RPN branch on its own
 
     python tools/bench_dcn.py --dcn-stages 3,4,5 --modulated 1 --groups 1 --steps 30 --warmup 5
     python tools/bench_dcn.py --dcn-stages ''              # the plain model, same protocol
+    python tools/bench_dcn.py --dcn-stages 3,4,5 --roi-pool mdpool     # + deformable RoI pooling in the box branch
 
-Prints one JSON line: {"dcn_stages", "modulated", "groups", "img_per_s", "step_ms", "losses"}.
+Prints one JSON line: {"dcn_stages", "modulated", "groups", "roi_pool", "img_per_s", "step_ms", "losses"}.
 """
 import argparse
 import json
@@ -22,6 +23,7 @@ def main():
     ap.add_argument("--dcn-stages", default="3,4,5", help="comma-separated subset of 3,4,5; empty = plain model")
     ap.add_argument("--modulated", type=int, default=1)
     ap.add_argument("--groups", type=int, default=1)
+    ap.add_argument("--roi-pool", default="roi_align", choices=("roi_align", "dpool", "mdpool"))
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     args = ap.parse_args()
@@ -31,7 +33,7 @@ def main():
     stages = tuple(int(s) for s in args.dcn_stages.split(",") if s.strip())
     device = "cuda"
     model = FasterRCNN(device, depth=50, seed=7, dcn_stages=stages, dcn_modulated=bool(args.modulated),
-                       dcn_groups=args.groups)
+                       dcn_groups=args.groups, roi_pool=args.roi_pool)
     model.enable_wgrad_stream()
     model.enable_branch_stream()
     model.enable_grouped_wgrad()
@@ -50,6 +52,7 @@ def main():
     dt = time.perf_counter() - t0
     vals = [float(v) for v in torch.cat(list(losses)).cpu().numpy()]
     print(json.dumps({"dcn_stages": list(stages), "modulated": bool(args.modulated), "groups": args.groups,
+                      "roi_pool": args.roi_pool,
                       "img_per_s": round(BATCH_PER_GPU * args.steps / dt, 2),
                       "step_ms": round(1e3 * dt / args.steps, 3), "losses": vals}), flush=True)
 
