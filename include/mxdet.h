@@ -478,7 +478,8 @@ int mxdet_filter_transpose_batched(const void* descs_dev, int32_t ndesc, int32_t
  *   0 if p_y <= -1, p_y >= H, p_x <= -1 or p_x >= W; else the bilinear mix of the four corners around
  *   (floor(p_y), floor(p_x)), corners outside [0,H) x [0,W) reading 0; v2 multiplies it by sigmoid(logit) (fused: the
  *   mask is never stored). Gradients w.r.t. p_y / p_x are those of that bilinear form with the floor held fixed
- *   (one-sided at integer positions, as in MXNet).
+ *   (one-sided at integer positions, as in MXNet). floor(p) and p - floor(p) are those of the real number p: they are
+ *   taken from the offset alone (the rest of p is an integer), not from a sum rounded in fp32.
  * col bf16 [N,Ho,Wo,9*C], tap-major then channel: the [Cout,3,3,C] filter seen as [Cout,1,1,9C], so forward, data
  * gradient and weight gradient are mxdet_conv2d_fwd / _dgrad / _wgrad as 1x1 convolutions on col. */
 typedef struct {

@@ -44,14 +44,22 @@ __device__ __forceinline__ DSample deform_sample(const DeformArgs& a, const uint
   const float dx = bf16_bits_to_f32(o[g * 18 + 2 * k + 1]);
   *m = 1.0f;
   if (a.mod) *m = 1.0f / (1.0f + expf(-bf16_bits_to_f32(o[18 * a.G + 9 * g + k])));
-  const float py = (float)(ho * a.stride - a.pad + k / 3) + dy;
-  const float px = (float)(wo * a.stride - a.pad + k % 3) + dx;
+  // The position is base + offset with an integer base: floor and fraction are taken from the offset alone, so they are
+  // those of the real number (base + dy rounds in fp32 -- 2^-15 px at 728 -- and a sample that close to an integer
+  // pixel would land on its other side, where d(sample)/d(offset) is another one-sided derivative). The rounded sum
+  // only bounds the integer conversion (a NaN or huge offset is not valid).
+  const int by = ho * a.stride - a.pad + k / 3, bx = wo * a.stride - a.pad + k % 3;
+  const float py = (float)by + dy, px = (float)bx + dx;
+  const bool inrange = py > -2.0f && py < (float)a.H + 1.0f && px > -2.0f && px < (float)a.W + 1.0f;
+  const float fy = floorf(dy), fx = floorf(dx);
   DSample s;
-  s.valid = py > -1.0f && py < (float)a.H && px > -1.0f && px < (float)a.W;
-  const float fy = floorf(py), fx = floorf(px);
-  s.y0 = s.valid ? (int)fy : 0;
-  s.x0 = s.valid ? (int)fx : 0;
-  s.ly = py - fy; s.lx = px - fx;
+  s.ly = dy - fy; s.lx = dx - fx;
+  s.y0 = inrange ? by + (int)fy : 0;
+  s.x0 = inrange ? bx + (int)fx : 0;
+  // inside the open window (-1, H) x (-1, W)
+  s.valid = inrange && (s.y0 >= 0 || (s.y0 == -1 && s.ly > 0.0f)) && s.y0 < a.H &&
+            (s.x0 >= 0 || (s.x0 == -1 && s.lx > 0.0f)) && s.x0 < a.W;
+  if (!s.valid) s.y0 = s.x0 = 0;
   s.hy = 1.0f - s.ly; s.hx = 1.0f - s.lx;
   return s;
 }
