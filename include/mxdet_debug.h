@@ -44,6 +44,35 @@ int mxdet_debug_preprocess_direct(int32_t on);
 #define MXDET_TUNE_T3_PER_ITEM 18  /* grouped wgrad, three-tap tiles: at most this many workgroups per 3x3 layer of the group (0 = no cap; default 192) */
 #define MXDET_TUNE_COUNT 19
 int mxdet_debug_set_tuning(int32_t which, int64_t value);
+/* the value in effect (tests check that what they changed is back); -1 and an error string for an unknown key */
+int64_t mxdet_debug_get_tuning(int32_t which);
+
+
+/* Route probe (per calling thread): which kernel instantiation a dense convolution / weight-gradient call runs.
+ * While the probe is on, mxdet_conv2d_fwd / _fwd_splitk / _fwd_chain / _dgrad / _grouped, mxdet_conv2d_wgrad and
+ * mxdet_conv2d_wgrad_grouped(_parts) validate their arguments as usual, record the launch(es) they WOULD make and return
+ * MXDET_OK without launching, without dereferencing any pointer and without touching the device (so it also works on a
+ * machine without a GPU, with dummy non-null pointers). Switching it on clears the records. A record is 16 int32 words,
+ * word 0 = kind:
+ *   MXDET_ROUTE_CONV          BM, BN, WM, WN, NS, DGRAD, PAR, TAPS, CHAIN, tiles_m, tiles_n, m_begin, ksplit, grid
+ *                             (one per kernel launch: a 256x256 launch and its tail are two records)
+ *   MXDET_ROUTE_WGRAD         three-tap (0/1), ksplit, steps_per_split, t3_steps, ring depth of the three-tap kernel (0 = not
+ *                             launched), ring depth of the one-tap kernel (0 = not launched), fold (0/1), one-tap grid (tiles +
+ *                             bias workgroups), three-tap grid, accumulate, one-tap steps (of MXDET_WGRAD_BKP pixels), three-tap
+ *                             steps (of 64 virtual pixels)
+ *   MXDET_ROUTE_CONV_GROUPED  BM, BN, WM, WN, NS, DGRAD, 0, TAPS, 0, 0, 0, 0, 0, grid, items
+ *   MXDET_ROUTE_WGRAD_GROUPED mixed grid (0 / 1 / 2 = MXDET_TUNE_T3_MIX in effect), ring depth three-tap tiles, ring depth
+ *                             one-tap tiles (0 = none launched), grid_big, grid_wgrad, grid_reduce (after `parts`), parts */
+#define MXDET_ROUTE_CONV 1
+#define MXDET_ROUTE_WGRAD 2
+#define MXDET_ROUTE_CONV_GROUPED 3
+#define MXDET_ROUTE_WGRAD_GROUPED 4
+#define MXDET_ROUTE_WORDS 16
+#define MXDET_ROUTE_MAX 4
+int mxdet_debug_route_probe(int32_t on);
+/* copies up to max_records (<= MXDET_ROUTE_MAX) records to `records` ([max_records][16]); returns the number of launches
+ * recorded since the probe was switched on (more than MXDET_ROUTE_MAX are counted but not kept) */
+int mxdet_debug_route_read(int32_t* records, int32_t max_records);
 
 #ifdef __cplusplus
 }

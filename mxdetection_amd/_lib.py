@@ -190,11 +190,14 @@ SIGNATURES = {
     "mxdet_comm_wait": (c_i32, [c_vp, c_i32, c_vp]),
     "mxdet_comm_broadcast": (c_i32, [c_vp, c_vp, c_sz, c_i32, c_vp]),
     "mxdet_debug_set_tuning": (c_i32, [c_i32, c_i64]),
+    "mxdet_debug_get_tuning": (c_i64, [c_i32]),
+    "mxdet_debug_route_probe": (c_i32, [c_i32]),
+    "mxdet_debug_route_read": (c_i32, [P(c_i32), c_i32]),
 }
 
 # entries declared in include/mxdet_debug.h (tuning / test hooks, not part of the drop-in boundary)
 DEBUG_SYMBOLS = ("mxdet_debug_force_conv_cfg", "mxdet_debug_force_wgrad_ksplit", "mxdet_debug_preprocess_direct",
-                 "mxdet_debug_set_tuning")
+                 "mxdet_debug_set_tuning", "mxdet_debug_get_tuning", "mxdet_debug_route_probe", "mxdet_debug_route_read")
 TUNING_KEYS = {"T64": 0, "T128": 1, "PAR64": 2, "WG_TARGET": 3, "WG_MINSTEPS": 4, "WG_MAXSTEPS": 5, "T3_ENABLE": 6,
                "T3_TARGET": 7, "T3_MINSTEPS": 8, "T3_NS": 9, "TAIL": 10, "WG_NS": 11, "ROI_TABLE": 12, "ROI_ROWS": 13, "STATIC_TAPS": 14,
                "T128W": 15, "T3_MIX": 16, "SPLITK_TILE": 17, "T3_PER_ITEM": 18}

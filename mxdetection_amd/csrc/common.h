@@ -35,6 +35,13 @@ inline int check_launch(const char* what) {
 // plan-time thresholds (mxdet_debug_set_tuning; defaults in capi.hip). The library never reads the environment.
 long long tuning(int which);
 
+// Route probe (mxdet_debug_route_probe, include/mxdet_debug.h): while it is on for the calling thread, the dense conv /
+// weight-gradient launchers record the instantiation and grid they WOULD launch and return without touching the device.
+constexpr int kRouteWords = 16, kRouteMax = 4;
+extern thread_local int g_route_probe;                   // 0 = off (the only cost on the launch path: this load)
+void route_record(const int32_t (&rec)[kRouteWords]);
+static inline bool route_probe_on() { return g_route_probe != 0; }
+
 static inline hipStream_t as_stream(mxdet_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 constexpr int kWave = 64;

@@ -896,6 +896,12 @@ static int launch_cfg(ConvP& p, hipStream_t s) {
   p.tiles_n = ceil_div(p.Ncols, BN);
   long long nwg = (long long)p.tiles_m * p.tiles_n;
   if (TAPS == 1 && p.ksplit > 1) nwg *= p.ksplit;
+  if (route_probe_on()) {   // mxdet_debug_route_probe: say what would run, touch nothing
+    const int32_t rec[kRouteWords] = {MXDET_ROUTE_CONV, BM, BN, WM, WN, NS, DGRAD, PAR, TAPS, CHAIN, p.tiles_m, p.tiles_n,
+                                      p.m_begin, p.ksplit, (int32_t)nwg, 0};
+    route_record(rec);
+    return MXDET_OK;
+  }
   hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, NS, DGRAD, PAR, TAPS, CHAIN>), dim3((unsigned)nwg),
                      dim3(64 * WM * WN), 0, s, p);
   return check_launch("conv2d");
@@ -1165,7 +1171,7 @@ extern "C" int mxdet_conv2d_fwd_splitk(const mxdet_conv_desc_t* d, const uint16_
   if (big == 1) rc = launch_cfg<128, 128, 2, 2, 2, false, false, 1>(p, s);
   else if (big == 2) rc = launch_cfg<128, 128, 2, 4, 2, false, false, 1>(p, s);
   else rc = launch_cfg<64, 64, 2, 2, 3, false, false, 1>(p, s);
-  if (rc) return rc;
+  if (rc || route_probe_on()) return rc;
   const long long total = (long long)p.M * p.Ncols;
   hipLaunchKernelGGL(conv_splitk_fold_kernel, dim3((unsigned)ceil_div<long long>(total / 8, 256)), dim3(256), 0, s,
                      (const float*)workspace, ksplit, (long long)p.M, p.Ncols, bias, residual, d->relu, y);
@@ -1201,6 +1207,12 @@ extern "C" int mxdet_conv2d_dgrad(const mxdet_conv_desc_t* d, const uint16_t* dy
 template <int BM, int BN, int WM, int WN, int NS, bool DGRAD>
 static void launch_grouped_cfg(const ConvG* table, int n, int grid, hipStream_t s, int tapclass) {
   // tapclass: 0 = any geometry, 1 = every item a stride-1 1x1, 2 = every item a stride-1 3x3 (static-tap K loop)
+  if (route_probe_on()) {
+    const int32_t rec[kRouteWords] = {MXDET_ROUTE_CONV_GROUPED, BM, BN, WM, WN, NS, DGRAD, 0, tapclass == 1 ? 1 : tapclass == 2 ? 9 : 0,
+                                      0, 0, 0, 0, 0, grid, n};
+    route_record(rec);
+    return;
+  }
   if (tapclass == 1)
     hipLaunchKernelGGL((conv_igemm_grouped_kernel<BM, BN, WM, WN, NS, DGRAD, 1>), dim3((unsigned)grid), dim3(64 * WM * WN),
                        0, s, table, n);
@@ -1316,5 +1328,6 @@ extern "C" int mxdet_conv2d_grouped(const void* table_dev, int32_t n, int32_t ki
       default: launch_grouped_cfg<64, 64, 2, 2, 3, true>(t, n, grid, s, tc); break;
     }
   }
+  if (route_probe_on()) return MXDET_OK;
   return check_launch("conv2d_grouped");
 }

@@ -390,6 +390,21 @@ extern "C" int mxdet_conv2d_wgrad(const mxdet_conv_desc_t* d, const uint16_t* x,
   MXDET_REQUIRE(d->Cin % 4 == 0, MXDET_ESHAPE, "conv2d_wgrad: Cin must be a multiple of 4");
   hipStream_t s = as_stream(stream);
   const long long tiles = (long long)w.co_tiles * w.ci_tiles * w.taps;
+  // the launches this call makes, decided once: the route probe and the launch code below read the same values
+  const int steps = (int)ceil_div<long long>((long long)d->N * d->Ho * d->Wo, kWgradBKP);
+  const int t3_grid = w.t3 ? w.co_tiles * w.t3_ci_tiles * 3 * w.ksplit : 0;
+  const int t3_ns = w.t3 ? (tuning(MXDET_TUNE_T3_NS) == 3 ? 3 : 2) : 0;                 // ring depth of the three-tap kernel (0 = not launched)
+  const long long n1_grid = (w.t3 ? 0 : tiles * w.ksplit) + (db ? (long long)w.co_tiles * w.ksplit : 0);
+  // few workgroups per CU: a deeper ring hides the load latency that co-resident workgroups would otherwise hide
+  const int n1_ns = n1_grid > 0 ? (n1_grid <= 2 * 256 ? 4 : 2) : 0;                     // ... of the one-tap kernel
+  const bool fold = w.ksplit > 1;
+  if (route_probe_on()) {   // mxdet_debug_route_probe: say what would run, touch nothing
+    const int32_t rec[kRouteWords] = {MXDET_ROUTE_WGRAD, w.t3, w.ksplit, w.steps_per_split, w.t3_steps, t3_ns, n1_ns, fold,
+                                      (int32_t)n1_grid, t3_grid, d->accumulate, steps,
+                                      w.t3 ? (int)ceil_div<long long>(wgrad3_vpixels(d->N, d->H, d->W), kT3Px) : 0, 0, 0, 0};
+    route_record(rec);
+    return MXDET_OK;
+  }
   WgradP p;
   p.x = x; p.dy = dy; p.slab = (float*)workspace;
   p.bslab = (float*)((char*)workspace + w.bslab_off);
@@ -403,22 +418,19 @@ extern "C" int mxdet_conv2d_wgrad(const mxdet_conv_desc_t* d, const uint16_t* x,
   p.t3_nwg = 0; p.t3_ci_tiles = w.t3_ci_tiles; p.t3_ksplit = w.ksplit; p.t3_steps = w.t3_steps;
   if (w.t3) {
     // three-tap tiles first; the one-tap kernel keeps only the bias workgroups (same pixel ranges)
-    p.t3_nwg = w.co_tiles * w.t3_ci_tiles * 3 * w.ksplit;
-    p.nwg_main = 0;
-    if (tuning(MXDET_TUNE_T3_NS) == 3)
+    p.t3_nwg = t3_grid;
+    if (t3_ns == 3)
       hipLaunchKernelGGL((wgrad3_kernel<3>), dim3((unsigned)p.t3_nwg), dim3(256), 0, s, p);
     else
       hipLaunchKernelGGL((wgrad3_kernel<2>), dim3((unsigned)p.t3_nwg), dim3(256), 0, s, p);
     nwg = 0;
   }
   p.nwg_main = (int)nwg;
-  if (db) nwg += (long long)w.co_tiles * w.ksplit;
-  // few workgroups per CU: a deeper ring hides the load latency that co-resident workgroups would otherwise hide
-  if (nwg > 0 && nwg <= 2 * 256)
-    hipLaunchKernelGGL((wgrad_kernel<kWgradBKP, 4>), dim3((unsigned)nwg), dim3(256), 0, s, p);
-  else if (nwg > 0)
-    hipLaunchKernelGGL((wgrad_kernel<kWgradBKP, 2>), dim3((unsigned)nwg), dim3(256), 0, s, p);
-  if (w.ksplit > 1) {
+  if (n1_ns == 4)
+    hipLaunchKernelGGL((wgrad_kernel<kWgradBKP, 4>), dim3((unsigned)n1_grid), dim3(256), 0, s, p);
+  else if (n1_ns == 2)
+    hipLaunchKernelGGL((wgrad_kernel<kWgradBKP, 2>), dim3((unsigned)n1_grid), dim3(256), 0, s, p);
+  if (fold) {
     long long params = (long long)d->Cout * w.taps * d->Cin;
     int wblocks = (int)ceil_div<long long>(params / 4, 256);
     int bblocks = db ? ceil_div(d->Cout, 256) : 0;
@@ -639,40 +651,43 @@ extern "C" int mxdet_conv2d_wgrad_grouped_parts(const void* table_dev, int32_t n
   MXDET_REQUIRE(workspace_needed == 0 || (workspace && workspace_bytes >= workspace_needed), MXDET_EWORKSPACE,
                 "wgrad_grouped: workspace %zu < %zu", workspace_bytes, workspace_needed);
   hipStream_t s = as_stream(stream);
-  if (grid_big > 0 && grid_wgrad > 0 && tuning(MXDET_TUNE_T3_MIX) != 0 && (grid_big & 7) == 0 && (grid_wgrad & 7) == 0) {
+  // the launches this call makes, decided once: the route probe and the launch code below read the same values
+  const int mix = (grid_big > 0 && grid_wgrad > 0 && tuning(MXDET_TUNE_T3_MIX) != 0 && (grid_big & 7) == 0 && (grid_wgrad & 7) == 0)
+                      ? (tuning(MXDET_TUNE_T3_MIX) == 2 ? 2 : 1) : 0;            // both tile kinds in one grid (one-tap ring of 3 / of 2)
+  const int wg_ns = (int)tuning(MXDET_TUNE_WG_NS);
+  const int ns3 = grid_big > 0 ? (mix ? 2 : (tuning(MXDET_TUNE_T3_NS) == 3 ? 3 : 2)) : 0;                    // ring depth, three-tap tiles
+  // one-tap tiles: 2 stages (32 KiB, 4 workgroups per CU), 3 (48 KiB, 3 per CU) or 4 (64 KiB, 2 per CU)
+  const int ns1 = grid_wgrad > 0 ? (mix ? (mix == 2 ? 2 : 3) : (wg_ns == 3 || wg_ns == 4 ? wg_ns : 2)) : 0;
+  if (route_probe_on()) {
+    const int32_t rec[kRouteWords] = {MXDET_ROUTE_WGRAD_GROUPED, mix, ns3, ns1, grid_big, grid_wgrad, grid_reduce, parts,
+                                      0, 0, 0, 0, 0, 0, 0, 0};
+    route_record(rec);
+    return MXDET_OK;
+  }
+  if (mix) {
     const int n3g = grid_big >> 3, n1g = grid_wgrad >> 3;
-    if (tuning(MXDET_TUNE_T3_MIX) == 2)
+    if (mix == 2)
       hipLaunchKernelGGL((wgrad_mixed_grouped_kernel<2, 2>), dim3((unsigned)(grid_big + grid_wgrad)), dim3(256), 0, s,
                          (const WgradG*)table_dev, n, (unsigned char*)workspace, n3g, n1g);
     else
       hipLaunchKernelGGL((wgrad_mixed_grouped_kernel<2, 3>), dim3((unsigned)(grid_big + grid_wgrad)), dim3(256), 0, s,
                          (const WgradG*)table_dev, n, (unsigned char*)workspace, n3g, n1g);
-    grid_big = 0;
-    grid_wgrad = 0;
-  }
-  if (grid_big > 0) {
-    if (tuning(MXDET_TUNE_T3_NS) == 3)
+  } else {
+    if (ns3 == 3)
       hipLaunchKernelGGL((wgrad3_grouped_kernel<3>), dim3((unsigned)grid_big), dim3(256), 0, s, (const WgradG*)table_dev, n,
                          (unsigned char*)workspace);
-    else
+    else if (ns3 == 2)
       hipLaunchKernelGGL((wgrad3_grouped_kernel<2>), dim3((unsigned)grid_big), dim3(256), 0, s, (const WgradG*)table_dev, n,
                          (unsigned char*)workspace);
-  }
-  if (grid_wgrad > 0) {
-    // ring depth: 2 stages (32 KiB, 4 workgroups per CU), 3 (48 KiB, 3 per CU) or 4 (64 KiB, 2 per CU)
-    switch ((int)tuning(MXDET_TUNE_WG_NS)) {
-      case 3:
-        hipLaunchKernelGGL((wgrad_grouped_kernel<kWgradBKP, 3>), dim3((unsigned)grid_wgrad), dim3(256), 0, s,
-                           (const WgradG*)table_dev, n, (unsigned char*)workspace);
-        break;
-      case 4:
-        hipLaunchKernelGGL((wgrad_grouped_kernel<kWgradBKP, 4>), dim3((unsigned)grid_wgrad), dim3(256), 0, s,
-                           (const WgradG*)table_dev, n, (unsigned char*)workspace);
-        break;
-      default:
-        hipLaunchKernelGGL((wgrad_grouped_kernel<kWgradBKP, 2>), dim3((unsigned)grid_wgrad), dim3(256), 0, s,
-                           (const WgradG*)table_dev, n, (unsigned char*)workspace);
-    }
+    if (ns1 == 3)
+      hipLaunchKernelGGL((wgrad_grouped_kernel<kWgradBKP, 3>), dim3((unsigned)grid_wgrad), dim3(256), 0, s,
+                         (const WgradG*)table_dev, n, (unsigned char*)workspace);
+    else if (ns1 == 4)
+      hipLaunchKernelGGL((wgrad_grouped_kernel<kWgradBKP, 4>), dim3((unsigned)grid_wgrad), dim3(256), 0, s,
+                         (const WgradG*)table_dev, n, (unsigned char*)workspace);
+    else if (ns1 == 2)
+      hipLaunchKernelGGL((wgrad_grouped_kernel<kWgradBKP, 2>), dim3((unsigned)grid_wgrad), dim3(256), 0, s,
+                         (const WgradG*)table_dev, n, (unsigned char*)workspace);
   }
   if (grid_reduce > 0)
     hipLaunchKernelGGL(wgrad_reduce_grouped_kernel, dim3((unsigned)grid_reduce), dim3(256), 0, s,
