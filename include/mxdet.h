@@ -507,6 +507,37 @@ size_t mxdet_deform_col2im_workspace_bytes(const mxdet_deform_desc_t* d);
 int mxdet_deform_col2im(const mxdet_deform_desc_t* d, const uint16_t* off, const uint16_t* dcol, uint16_t* dx,
                         void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
 
+/* GroupNorm (+ fused ReLU) for the trainable heads (MXNet-lineage role: the GN of Detectron / mmdetection's 4conv1fc box
+ * head and GN mask head). x, y, dy, dx: bf16 channels-last [N, HW, C] (16-byte aligned); G groups of C/G adjacent channels;
+ * statistics per (sample, group) over m = HW * C/G elements, in fp32:
+ *   mean = sum x / m;  var = sum (x - mean)^2 / m  (about the mean, biased);  rstd = 1 / sqrt(var + eps);
+ *   y = act(gamma[c] * (x - mean) * rstd + beta[c]), act = ReLU if d->relu; mean, rstd fp32 [N, G] are written for bwd.
+ * bwd, with xh = (x - mean) * rstd and g = dy (under d->relu: dy where y > 0, else 0; y is the forward output, or NULL
+ * to have the mask recomputed from x, gamma and beta):
+ *   dgamma[c] (+)= sum_{n,hw} g * xh;  dbeta[c] (+)= sum_{n,hw} g   (d->accumulate as on the other backward entries);
+ *   dx = rstd * (g * gamma - (sum_group g * gamma + xh * sum_group g * gamma * xh) / m).
+ * Shapes: C % G == 0, (C/G) % 8 == 0, C <= 1024, any HW >= 1, any N >= 1 (a sample under 2^30 elements: its offsets are
+ * 32-bit); else MXDET_ESHAPE.
+ * Two routes, chosen from (HW, C) alone (mxdet_debug_group_norm_route): a sample of at most 8 * floor(1024 / (C/8))
+ * pixels is RESIDENT -- one workgroup per sample, x (bwd: x and dy) read once into registers, both statistics passes and
+ * the store from that copy; a sample's results do not depend on N or on its index. Larger samples are TILED over
+ * workgroups: per-chunk (count, mean, M2) in the workspace, merged in chunk order (Chan), then an apply kernel.
+ * dgamma / dbeta: per-workgroup fp32 partials in the workspace, folded in a fixed order; no float atomics: every output
+ * is bit-reproducible run to run. Workspace: mxdet_group_norm_workspace_bytes(d, backward) (0 for an invalid
+ * descriptor; the resident forward needs none and accepts workspace == NULL). */
+typedef struct {
+  int32_t N, HW, C, G;
+  float eps;
+  int32_t relu;
+  int32_t accumulate;        /* bwd: add into dgamma / dbeta instead of overwriting */
+} mxdet_gn_desc_t;
+size_t mxdet_group_norm_workspace_bytes(const mxdet_gn_desc_t* d, int32_t backward);
+int mxdet_group_norm_fwd(const mxdet_gn_desc_t* d, const uint16_t* x, const float* gamma, const float* beta, uint16_t* y,
+                         float* mean, float* rstd, void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
+int mxdet_group_norm_bwd(const mxdet_gn_desc_t* d, const uint16_t* x, const uint16_t* dy, const uint16_t* y,
+                         const float* mean, const float* rstd, const float* gamma, const float* beta, uint16_t* dx,
+                         float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
+
 /* stem: 7x7 stride-2 pad-3 convolution reading the NCHW fp32/bf16 image [N,3,H,W] directly
  * (coalesced plane reads), + bias + ReLU, writing bf16 [N,Ho,Wo,64]; w bf16 [64,7,7,3]. */
 int mxdet_stem_conv7x7(const void* image, int32_t dtype, int32_t N, int32_t H, int32_t W,

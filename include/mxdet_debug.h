@@ -8,6 +8,8 @@
 
 #include <stdint.h>
 
+#include "mxdet.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -73,6 +75,12 @@ int mxdet_debug_route_probe(int32_t on);
 /* copies up to max_records (<= MXDET_ROUTE_MAX) records to `records` ([max_records][16]); returns the number of launches
  * recorded since the probe was switched on (more than MXDET_ROUTE_MAX are counted but not kept) */
 int mxdet_debug_route_read(int32_t* records, int32_t max_records);
+
+/* Which route mxdet_group_norm_fwd / _bwd take for this descriptor (a pure function of HW and C; no device access):
+ * MXDET_GN_ROUTE_RESIDENT or MXDET_GN_ROUTE_TILED, or the negative code the entry itself would return for the shape. */
+#define MXDET_GN_ROUTE_RESIDENT 1
+#define MXDET_GN_ROUTE_TILED 2
+int mxdet_debug_group_norm_route(const mxdet_gn_desc_t* d);
 
 #ifdef __cplusplus
 }

@@ -76,6 +76,12 @@ class DpoolDescT(C.Structure):
     ]
 
 
+class GnDescT(C.Structure):
+    """mxdet_gn_desc_t (include/mxdet.h)."""
+    _fields_ = [("N", c_i32), ("HW", c_i32), ("C", c_i32), ("G", c_i32), ("eps", c_f32), ("relu", c_i32),
+                ("accumulate", c_i32)]
+
+
 WgradItemT._fields_ = [("desc", ConvDescT), ("x", c_vp), ("dy", c_vp), ("dw", c_vp), ("db", c_vp)]
 ConvItemT._fields_ = [("desc", ConvDescT), ("src", c_vp), ("filt", c_vp), ("bias", c_vp), ("residual", c_vp),
                       ("relu_mask", c_vp), ("dst", c_vp)]
@@ -169,6 +175,11 @@ SIGNATURES = {
     "mxdet_dpool_bwd_trans": (c_i32, [P(DpoolDescT), c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mxdet_dpool_bwd_feat_workspace_bytes": (c_sz, [P(DpoolDescT), c_i64]),
     "mxdet_dpool_bwd_feat": (c_i32, [P(DpoolDescT), c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_group_norm_workspace_bytes": (c_sz, [P(GnDescT), c_i32]),
+    "mxdet_group_norm_fwd": (c_i32, [P(GnDescT), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_group_norm_bwd": (c_i32, [P(GnDescT), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
+                                     c_vp]),
+    "mxdet_debug_group_norm_route": (c_i32, [P(GnDescT)]),
     "mxdet_stem_conv7x7": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mxdet_stem_conv7x7_pool": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mxdet_maxpool3x3s2": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
@@ -197,7 +208,8 @@ SIGNATURES = {
 
 # entries declared in include/mxdet_debug.h (tuning / test hooks, not part of the drop-in boundary)
 DEBUG_SYMBOLS = ("mxdet_debug_force_conv_cfg", "mxdet_debug_force_wgrad_ksplit", "mxdet_debug_preprocess_direct",
-                 "mxdet_debug_set_tuning", "mxdet_debug_get_tuning", "mxdet_debug_route_probe", "mxdet_debug_route_read")
+                 "mxdet_debug_set_tuning", "mxdet_debug_get_tuning", "mxdet_debug_route_probe", "mxdet_debug_route_read",
+                 "mxdet_debug_group_norm_route")
 TUNING_KEYS = {"T64": 0, "T128": 1, "PAR64": 2, "WG_TARGET": 3, "WG_MINSTEPS": 4, "WG_MAXSTEPS": 5, "T3_ENABLE": 6,
                "T3_TARGET": 7, "T3_MINSTEPS": 8, "T3_NS": 9, "TAIL": 10, "WG_NS": 11, "ROI_TABLE": 12, "ROI_ROWS": 13, "STATIC_TAPS": 14,
                "T128W": 15, "T3_MIX": 16, "SPLITK_TILE": 17, "T3_PER_ITEM": 18}

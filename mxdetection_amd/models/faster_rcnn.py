@@ -10,7 +10,7 @@ import os
 import torch
 
 from .backbones import ResNet
-from .bbox_heads import BBoxHead
+from .bbox_heads import BBoxHead, ConvFCBBoxHead
 from .mask_heads import FCNMaskHead
 from .necks import FPN
 from .roi_extractors import DeformRoIExtractor, FPNRoIExtractor
@@ -19,14 +19,34 @@ from .utils.detector import DetectorBase
 from .utils.layers import Workspace
 
 
+def check_head_options(bbox_head, head_norm, gn_groups, with_mask):
+    """The head options of FasterRCNN, checked before anything is allocated."""
+    if bbox_head not in ("2fc", "4conv1fc"):
+        raise ValueError("bbox_head must be '2fc' or '4conv1fc' (got %r)" % (bbox_head,))
+    if head_norm not in ("none", "gn"):
+        raise ValueError("head_norm must be 'none' or 'gn' (got %r)" % (head_norm,))
+    if head_norm == "gn":
+        if bbox_head == "2fc" and not with_mask:
+            raise ValueError("head_norm='gn' with nothing to normalise: the 2fc box head has no convolutions and there "
+                             "is no mask head")
+        g = gn_groups
+        if not isinstance(g, int) or isinstance(g, bool) or g <= 0 or 256 % g or (256 // g) % 8:
+            raise ValueError("gn_groups = %r does not divide 256 channels into groups of a multiple of 8" % (g,))
+
+
 class FasterRCNN(DetectorBase):
     def __init__(self, device="cuda", depth=50, num_classes=81, seed=7, rpn_seed=99, rois_per_image=512,
                  pre_nms_top_n=2000, post_nms_top_n=2000, with_mask=False, dcn_stages=(), dcn_modulated=True,
-                 dcn_groups=1, roi_pool="roi_align", dpool_trans_std=0.1, dpool_sample_per_part=4, dpool_offset_fcs=3):
+                 dcn_groups=1, roi_pool="roi_align", dpool_trans_std=0.1, dpool_sample_per_part=4, dpool_offset_fcs=3,
+                 bbox_head="2fc", head_norm="none", gn_groups=32):
         """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
         roi_pool: the box branch's RoI pooling -- 'roi_align', or deformable RoI pooling with its offset head, 'dpool'
         (v1) / 'mdpool' (v2, modulated) (roi_extractors.DeformRoIExtractor, options dpool_*). The mask branch keeps its
-        14x14 RoIAlign."""
+        14x14 RoIAlign.
+        bbox_head: '2fc' (two FCs) or '4conv1fc' (four 3x3 convs + one FC). head_norm: 'none' or 'gn' -- GroupNorm with
+        gn_groups groups after every conv of the 4conv1fc box head and of the mask head (bbox_heads.ConvFCBBoxHead,
+        mask_heads.FCNMaskHead)."""
+        check_head_options(bbox_head, head_norm, gn_groups, with_mask)
         if roi_pool not in ("roi_align", "dpool", "mdpool"):
             raise ValueError("roi_pool must be 'roi_align', 'dpool' or 'mdpool' (got %r)" % (roi_pool,))
         self.roi_pool = roi_pool
@@ -43,11 +63,15 @@ class FasterRCNN(DetectorBase):
         self.mask_head = None
         if with_mask:   # Mask R-CNN (BASELINE.json config 4): the mask branch's backward runs first
             self.mask_head = FCNMaskHead(256, self.arena, self.ws, device, gen, num_classes=num_classes,
-                                         rois_per_image=max(1, rois_per_image // 4))
+                                         rois_per_image=max(1, rois_per_image // 4), norm=head_norm, gn_groups=gn_groups)
             self.mask_roi_extractor = FPNRoIExtractor([4, 8, 16, 32], pooled=(14, 14), device=device)
         self.mark_mask = self.arena.size
-        self.bbox_head = BBoxHead(7 * 7 * 256, self.arena, self.ws, device, gen, num_classes=num_classes,
-                                  rois_per_image=rois_per_image, seed=rpn_seed)
+        if bbox_head == "4conv1fc":
+            self.bbox_head = ConvFCBBoxHead(7 * 7 * 256, self.arena, self.ws, device, gen, norm=head_norm, gn_groups=gn_groups,
+                                            num_classes=num_classes, rois_per_image=rois_per_image, seed=rpn_seed)
+        else:
+            self.bbox_head = BBoxHead(7 * 7 * 256, self.arena, self.ws, device, gen, num_classes=num_classes,
+                                      rois_per_image=rois_per_image, seed=rpn_seed)
         self.dpool = None
         if roi_pool != "roi_align":
             # the offset head belongs to the head bucket: its backward runs in the slot of the RoI extractor's
@@ -68,9 +92,11 @@ class FasterRCNN(DetectorBase):
         self.roi_extractor = self.dpool if self.dpool is not None else FPNRoIExtractor(self.strides[:4], device=device)
         layers = self.bbox_head.layers() + (self.dpool.layers() if self.dpool is not None else [])
         layers += self.rpn_head.layers() + self.neck.layers() + self.backbone.layers()
+        norms = self.bbox_head.norm_layers()
         if with_mask:
             layers = self.mask_head.layers() + layers
-        self._finalize_params(layers)
+            norms = self.mask_head.norm_layers() + norms
+        self._finalize_params(layers, norm_layers=norms)
         # arena offsets after each backbone stage (layer4, layer3, layer2) for bucketed all-reduce
         self.stage_marks = {}
         for si in (3, 2, 1):

@@ -50,11 +50,12 @@ class DetectorBase:
         self._front = None        # {"graphs": [g0, g1], "segments": [s0, s1], "losses": [l0, l1], "stream", "ready", "count"}
         self._tail_event = None
 
-    def _finalize_params(self, layers, frozen_layers=()):
+    def _finalize_params(self, layers, frozen_layers=(), norm_layers=()):
         self.layers = layers
+        self.norm_layers = list(norm_layers)      # GroupNormLayer: arena parameters without a filter (never transposed)
         self.frozen_layers = list(frozen_layers)
         self.arena.finalize()
-        for l in self.layers:
+        for l in self.layers + self.norm_layers:
             l.materialize()
         self.arena.refresh_bf16()
         self.refresh_transposed()
@@ -68,6 +69,9 @@ class DetectorBase:
             out[l.name + ".weight"] = l.w_bf16.float().cpu()
             if l.has_bias:
                 out[l.name + ".bias"] = l.bias_f32.float().cpu()
+        for l in getattr(self, "norm_layers", ()):
+            for name, idx in l.named_params():
+                out[name] = self.arena.view(idx, "w").float().cpu()
         return out
 
     # ---- checkpoints: MXNet NDArray-list container, MXNet tensor layouts ----
@@ -92,6 +96,9 @@ class DetectorBase:
                 out.append((l.name + ".weight", "frozen", l.w_bf16, l))
                 if l.has_bias:
                     out.append((l.name + ".bias", "frozen", l.bias_f32, l))
+        for l in getattr(self, "norm_layers", ()):       # 1-D fp32 arrays under their own names (layer None: stored as is)
+            for name, idx in l.named_params():
+                out.append((name, "w", self.arena.view(idx, "w"), None))
         return out
 
     @staticmethod

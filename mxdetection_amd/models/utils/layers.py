@@ -238,6 +238,70 @@ class ConvLayer:
                 dense.conv2d_wgrad(x, dy, self.k, self.k, self.stride, self.pad, dw, db, accumulate, self.ws.get())
 
 
+class GroupNormLayer:
+    """GroupNorm (+ fused ReLU) after a bias-free convolution of a trainable head (ops/group_norm.py).
+
+    Parameters `<name>.gamma` / `<name>.beta` are fp32 arena entries; the kernels read the master copy (the arena's bf16
+    working copy of them is never used), weight decay and the one-launch SGD update treat them like every other entry.
+    gamma starts at 1, beta at 0: creating the layer draws no random numbers. It is not a ConvLayer: detectors keep it in
+    `norm_layers`, apart from `layers`, so the filter-transpose tables, prefetch wiring and grouped weight-gradient plans
+    never see it. backward() writes dgamma / dbeta into the arena's gradient slice on the CURRENT stream; the bucket that
+    holds them is closed by DetectorBase._reduce afterwards, whose weight-gradient flush and update fork the side stream
+    from the current one (Workspace.fork) -- so the update is ordered behind these writes in eager, grouped and captured
+    steps alike (with a gradient exchange the bucket's event node / all-reduce is recorded behind them too)."""
+    trainable = True
+
+    def __init__(self, name, channels, groups, arena, device="cuda", eps=1e-5):
+        if groups <= 0 or channels % groups or (channels // groups) % 8:
+            raise ValueError("GroupNorm %s: %d groups do not divide %d channels into multiples of 8" % (name, groups, channels))
+        self.name, self.C, self.G, self.eps = name, channels, groups, eps
+        self.arena, self.device = arena, device
+        self.gi = arena.register(name + ".gamma", (channels,))
+        self.bi = arena.register(name + ".beta", (channels,))
+        self.bufs = {}
+        self.plans = {}
+        self.gamma = self.beta = None
+        self.x = self.y = self.mean = self.rstd = None
+        self.relu = False
+
+    def materialize(self):
+        self.gamma, self.beta = self.arena.view(self.gi, "w"), self.arena.view(self.bi, "w")
+        self.gamma.fill_(1.0)
+        self.beta.zero_()
+
+    def named_params(self):
+        return [(self.name + ".gamma", self.gi), (self.name + ".beta", self.bi)]
+
+    def plan(self, x_shape):
+        """Statistics and workspaces for an input of this shape: allocated at the first call for a shape (nothing is
+        allocated in a step), looked up afterwards -- forward() / backward() cost one dict lookup, no ABI call."""
+        x_shape = tuple(x_shape)
+        p = self.plans.get(x_shape)
+        if p is None:
+            from ...ops import group_norm as GN
+            stats = [cached_buf(self.bufs, k, (x_shape[0], self.G), torch.float32, self.device) for k in ("mean", "rstd")]
+            ws = [cached_buf(self.bufs, "ws%d" % b, (max(GN.workspace_bytes(x_shape, self.G, bool(b)), 256),), torch.uint8,
+                             self.device) for b in (0, 1)]
+            p = self.plans[x_shape] = (stats[0], stats[1], ws[0], ws[1])
+        return p
+
+    def forward(self, x, relu=False, out=None):
+        from ...ops import group_norm as GN
+        mean, rstd, ws, _ = self.plan(x.shape)
+        y, _, _ = GN.group_norm_forward(x, self.gamma, self.beta, self.G, self.eps, relu, out=out, mean=mean, rstd=rstd,
+                                        workspace=ws)
+        self.x, self.y, self.mean, self.rstd, self.relu = x, y, mean, rstd, relu
+        return y
+
+    def backward(self, dy, out=None):
+        """dx; dgamma / dbeta go to the arena's gradient slice. The ReLU mask is recomputed from x (a third fewer bytes
+        than reading y; the same bits: tests/test_gpu_group_norm.py)."""
+        from ...ops import group_norm as GN
+        return GN.group_norm_backward(self.x, dy, self.mean, self.rstd, self.gamma, self.G, self.arena.view(self.gi, "g"),
+                                      self.arena.view(self.bi, "g"), y=None, beta=self.beta, eps=self.eps, relu=self.relu,
+                                      out=out, workspace=self.plan(self.x.shape)[3])
+
+
 class DeformConvLayer:
     """3x3 deformable convolution (DCN v1, or v2 with `modulated`), MXNet role contrib.DeformableConvolution; the
     drop-in for a bottleneck's conv2 ("Deformable convolution").

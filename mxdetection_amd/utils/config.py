@@ -44,6 +44,9 @@ DEFAULTS = {
         "roi_pool": "roi_align",          # box branch pooling: roi_align | dpool | mdpool (contrib.DeformablePSROIPooling)
         "dpool_trans_std": 0.1,           # scale of the predicted bin offsets (in roi widths / heights)
         "dpool_sample_per_part": 4,       # samples per bin and axis
+        "bbox_head": "2fc",               # box head trunk: 2fc | 4conv1fc (four 3x3 convs + one FC)
+        "head_norm": "none",              # none | gn: GroupNorm after every conv of the 4conv1fc box head and of the mask head
+        "gn_groups": 32,                  # GroupNorm groups (256 / gn_groups must be a multiple of 8)
         "dpool_offset_fcs": 3,            # FCs of the offset head (1: Deformable-ConvNets' FPN head, 3: DCN v2 / mmdetection)
     },
     "dataset": {

@@ -5,8 +5,10 @@ padded to 1344, weight gradients grouped on a side stream, RPN branch on its own
     python tools/bench_dcn.py --dcn-stages 3,4,5 --modulated 1 --groups 1 --steps 30 --warmup 5
     python tools/bench_dcn.py --dcn-stages ''              # the plain model, same protocol
     python tools/bench_dcn.py --dcn-stages 3,4,5 --roi-pool mdpool     # + deformable RoI pooling in the box branch
+    python tools/bench_dcn.py --dcn-stages '' --bbox-head 4conv1fc --head-norm gn     # the GN box head on the plain backbone
+    python tools/bench_dcn.py --dcn-stages '' --mask 1 --bbox-head 4conv1fc --head-norm gn     # Mask R-CNN, GN in both heads
 
-Prints one JSON line: {"dcn_stages", "modulated", "groups", "roi_pool", "img_per_s", "step_ms", "losses"}.
+Prints one JSON line: {"dcn_stages", "modulated", "groups", "roi_pool", "mask", "img_per_s", "step_ms", "losses"}.
 """
 import argparse
 import json
@@ -24,35 +26,51 @@ def main():
     ap.add_argument("--modulated", type=int, default=1)
     ap.add_argument("--groups", type=int, default=1)
     ap.add_argument("--roi-pool", default="roi_align", choices=("roi_align", "dpool", "mdpool"))
+    ap.add_argument("--bbox-head", default="2fc", choices=("2fc", "4conv1fc"))
+    ap.add_argument("--head-norm", default="none", choices=("none", "gn"))
+    ap.add_argument("--gn-groups", type=int, default=32)
+    ap.add_argument("--mask", type=int, default=0, help="1 = Mask R-CNN (ground-truth masks: an ellipse in every box, as bench.py)")
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     args = ap.parse_args()
     import torch
-    from bench import BATCH_PER_GPU, synth_batch
+    from bench import BATCH_PER_GPU, IM_H, PAD_W, synth_batch
     from mxdetection_amd.models import FasterRCNN
     stages = tuple(int(s) for s in args.dcn_stages.split(",") if s.strip())
     device = "cuda"
     model = FasterRCNN(device, depth=50, seed=7, dcn_stages=stages, dcn_modulated=bool(args.modulated),
-                       dcn_groups=args.groups, roi_pool=args.roi_pool)
+                       dcn_groups=args.groups, roi_pool=args.roi_pool, bbox_head=args.bbox_head,
+                       head_norm=args.head_norm, gn_groups=args.gn_groups, with_mask=bool(args.mask))
     model.enable_wgrad_stream()
     model.enable_branch_stream()
     model.enable_grouped_wgrad()
     lr = 0.02 * BATCH_PER_GPU / 16.0 / 3.0
     batches = [synth_batch(0, s, device) for s in range(4)]
-    model.capture(*batches[0], lr=lr, image_offset=0)
+    masks = [None] * len(batches)
+    if args.mask:   # filled ellipse inside every GT box, [N,16,H,W] u8 (GT rows 0..15 are the valid ones)
+        yy = torch.arange(IM_H, device=device).view(1, 1, IM_H, 1).float()
+        xx = torch.arange(PAD_W, device=device).view(1, 1, 1, PAD_W).float()
+        for k, (_, gt, _) in enumerate(batches):
+            b = gt[:, :16]
+            cx, cy = 0.5 * (b[..., 0] + b[..., 2]), 0.5 * (b[..., 1] + b[..., 3])
+            rx, ry = 0.5 * (b[..., 2] - b[..., 0]) + 0.5, 0.5 * (b[..., 3] - b[..., 1]) + 0.5
+            m = (((xx - cx[..., None, None]) / rx[..., None, None]) ** 2 +
+                 ((yy - cy[..., None, None]) / ry[..., None, None]) ** 2) <= 1.0
+            masks[k] = (m & (b[..., 4] >= 0)[..., None, None]).to(torch.uint8).contiguous()
+    model.capture(*batches[0], lr=lr, image_offset=0, gt_masks=masks[0])
     for i in range(args.warmup):
         img, gt, info = batches[i % len(batches)]
-        model.replay(img, gt, info, i)
+        model.replay(img, gt, info, i, gt_masks=masks[i % len(batches)])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
         img, gt, info = batches[(args.warmup + i) % len(batches)]
-        losses = model.replay(img, gt, info, args.warmup + i)
+        losses = model.replay(img, gt, info, args.warmup + i, gt_masks=masks[(args.warmup + i) % len(batches)])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     vals = [float(v) for v in torch.cat(list(losses)).cpu().numpy()]
     print(json.dumps({"dcn_stages": list(stages), "modulated": bool(args.modulated), "groups": args.groups,
-                      "roi_pool": args.roi_pool,
+                      "roi_pool": args.roi_pool, "mask": bool(args.mask), "bbox_head": args.bbox_head, "head_norm": args.head_norm,
                       "img_per_s": round(BATCH_PER_GPU * args.steps / dt, 2),
                       "step_ms": round(1e3 * dt / args.steps, 3), "losses": vals}), flush=True)
 
