@@ -91,6 +91,44 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
   const bf16x2_t p = (bf16x2_t){(__bf16)lo, (__bf16)hi};
   return __builtin_bit_cast(unsigned, p);
 }
+// eight (four) packed bf16 -> fp32, exact: element 2k is the low half of word k
+__device__ __forceinline__ void unpack8_bf16(const uint4& v, float* f) {
+  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
+  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
+  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
+  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
+}
+__device__ __forceinline__ void unpack4_bf16(const uint2& v, float* f) {
+  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
+  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
+}
+// eight floats -> packed bf16 by pack_bf16x2 (the hardware conversion: tolerance-checked dense results)
+__device__ __forceinline__ uint4 pack8_bf16_hw(const float* f) {
+  return make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7]));
+}
+// ... and by f32_to_bf16_bits (the shared bit-exact helper: results that are compared with the C oracle)
+__device__ __forceinline__ uint4 pack8_bf16_exact(const float* v) {
+  uint4 o;
+  o.x = (uint32_t)f32_to_bf16_bits(v[0]) | ((uint32_t)f32_to_bf16_bits(v[1]) << 16);
+  o.y = (uint32_t)f32_to_bf16_bits(v[2]) | ((uint32_t)f32_to_bf16_bits(v[3]) << 16);
+  o.z = (uint32_t)f32_to_bf16_bits(v[4]) | ((uint32_t)f32_to_bf16_bits(v[5]) << 16);
+  o.w = (uint32_t)f32_to_bf16_bits(v[6]) | ((uint32_t)f32_to_bf16_bits(v[7]) << 16);
+  return o;
+}
+
+// MFMA operand / accumulator vectors and the LDS pointer type of the LDS-DMA builtins
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
+typedef __attribute__((ext_vector_type(4))) short s16x4_t;
+typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+typedef __attribute__((address_space(3))) void* lptr_t;
+
+// XCD-aware tile order: workgroup `bid` of `nwg` runs on XCD bid % 8. The map gives each XCD a contiguous range of
+// tiles, so the blocks that share an XCD walk consecutive tiles and re-read what those tiles share from that XCD's L2.
+__device__ __forceinline__ int xcd_tile_order(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
 // exact floor(n / d) and remainder for 0 <= n < 2^24 through one float multiply + a +-1 correction (an integer division
 // is ~40 instructions): the tile prologues do two per row
 __device__ __forceinline__ int fast_divmod(int n, int d, float rcp, int* rem) {

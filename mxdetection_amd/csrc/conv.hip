@@ -22,9 +22,6 @@
 
 namespace mxdet {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-
 struct ConvP {
   const uint16_t* x;     // gathered source [N,Hs,Ws,C]
   const uint16_t* w;     // [Ncols][KH*KW*C]
@@ -70,9 +67,6 @@ __device__ __forceinline__ int lds_off(int row, int chunk) {
   return row * 64 + ((chunk ^ ((row >> 1) & 7)) << 3);
 }
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 #ifdef MXDET_CONV_STAMP
 // diagnostic build (tools/build_conv_stamp.sh): cycle stamps of one workgroup's life, wave 0 of blocks 0 and 300:
 // [start, geometry done, first stage landed, K loop done, end]
@@ -98,7 +92,6 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvP& p, int bid, const i
   constexpr int NW = WM * WN, NTHR = 64 * NW;
   constexpr int WTM = BM / WM, WTN = BN / WN;
   constexpr int MT = WTM / 16, NT = WTN / 16;
-  constexpr int NBUF = NS;
   constexpr int RPI = 8;                              // tile rows per LDS-DMA instruction (8 rows x 128 B)
   constexpr int GA = BM / RPI / NW, GB = BN / RPI / NW;   // LDS-DMA instructions per wave per stage
   constexpr int STAGE = (BM + BN) * 64;               // bf16 elements per stage
@@ -108,7 +101,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvP& p, int bid, const i
   static_assert(TAPS == 0 || ((TAPS == 1 || TAPS == 9) && !PAR), "static taps: 1x1 or 3x3");
   constexpr int EP_STRIDE = WTN + 4;
   constexpr int EP_BYTES = NW * 32 * EP_STRIDE * 4;
-  constexpr int MAIN_BYTES = NBUF * STAGE * 2;
+  constexpr int MAIN_BYTES = NS * STAGE * 2;
   // CHAIN > 0: a 1x1 convolution to CHAIN columns follows in the same workgroup (see after the K loop); its whole filter
   // (CHAIN x 64 bf16) sits behind the ring / epilogue area for the workgroup's life
   static_assert(CHAIN == 0 || (TAPS == 9 && !DGRAD && WN == 1 && BN == 64 && CHAIN % (8 * NW) == 0),
@@ -127,8 +120,6 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvP& p, int bid, const i
 #endif
   MXDET_CS(0);
 
-  // XCD-aware tile order: blocks that share an XCD (bid % 8) walk consecutive tiles, and consecutive
-  // tiles share their A rows (n fastest), so the A tile is re-read from that XCD's L2.
   const int pf_bid = bid, pf_nwg = nwg;            // as launched: the prefetch hint's slices are dealt by this index
   int ks = 0, sl_begin = 0, sl_end = p.C >> 6;     // split-K (static 1x1 path): this workgroup's range of channel slices
   int nwg_ = nwg;
@@ -146,10 +137,8 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvP& p, int bid, const i
   }
   if constexpr (!PAR) {   // PAR: classes differ 4:2:2:1 in work and are laid out one after the other -- giving each XCD
                           // a contiguous range would put all the heavy tiles on two of the eight; keep the hardware's
-                          // round-robin instead
-    const int nwg = nwg_;
-    int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+                          // round-robin instead. Otherwise: consecutive tiles share their A rows (n fastest)
+    bid = xcd_tile_order(bid, nwg_);
   }
   const int tile_m = bid / p.tiles_n, tile_n = bid - tile_m * p.tiles_n;
   int m0 = p.m_begin + tile_m * BM;
@@ -304,23 +293,6 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvP& p, int bid, const i
     a_mask[i] = mask;
   }
 
-  // one stage at an explicit position (static-tap path: kh, kw are constants after unrolling)
-  auto issue_at = [&](int buf, int kh, int kw, int c0, bool live) {
-    unsigned char* sbase = smem_raw + (size_t)buf * (STAGE * 2);
-    const int tap = live ? kh * p.KW + kw : 31;
-    const int delta = DGRAD ? c0 - (kh * p.Ws + kw) * p.C : c0 + (kh * p.Ws + kw) * p.C;     // stride 1
-    const int koff = live ? (kh * p.KW + kw) * p.C + c0 : 0;
-#pragma unroll
-    for (int i = 0; i < GA; ++i) {
-      const unsigned vo = ((a_mask[i] >> tap) & 1u) ? 2u * (unsigned)(a_off[i] + delta) : kDmaOob;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (lptr_t)(sbase + (wid * GA + i) * 1024), 16, (int)vo, 0, 0, 0);
-    }
-#pragma unroll
-    for (int i = 0; i < GB; ++i) {
-      const unsigned wo = 2u * (unsigned)(wrow[i] + koff);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (lptr_t)(sbase + BM * 128 + (wid * GB + i) * 1024), 16, (int)wo, 0, 0, 0);
-    }
-  };
   // running (channel-slice, tap) position of the NEXT stage to load: uniform scalars, no divisions
   int ld_kt = 0, ld_kh = 0, ld_kw = 0, ld_c0 = 0;
   auto issue_stage = [&](int buf) {
@@ -609,12 +581,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvP& p, int bid, const i
 #pragma unroll
           for (int k = 0; k < 8; ++k) v[k] = v[k] > 0.0f ? v[k] : 0.0f;
         }
-        uint4 o;
-        o.x = pack_bf16x2(v[0], v[1]);
-        o.y = pack_bf16x2(v[2], v[3]);
-        o.z = pack_bf16x2(v[4], v[5]);
-        o.w = pack_bf16x2(v[6], v[7]);
-        af2[i][hf] = __builtin_bit_cast(bf16x8_t, o);
+        af2[i][hf] = __builtin_bit_cast(bf16x8_t, pack8_bf16_hw(v));
       }
     }
   }
@@ -763,6 +730,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvP& p, int bid, const i
       }
       float v[8] = {v0.x + b0.x, v0.y + b0.y, v0.z + b0.z, v0.w + b0.w, v1.x + b1.x, v1.y + b1.y, v1.z + b1.z, v1.w + b1.w};
       if (e_res) {
+        // (spelled out, not unpack8_bf16 + a loop: hipcc schedules this epilogue differently around the helper form)
         const uint4 rv = rres[ps];
         v[0] += __uint_as_float(rv.x << 16); v[1] += __uint_as_float(rv.x & 0xffff0000u);
         v[2] += __uint_as_float(rv.y << 16); v[3] += __uint_as_float(rv.y & 0xffff0000u);
@@ -789,11 +757,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvP& p, int bid, const i
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = v[k] > 0.0f ? v[k] : 0.0f;
       }
-      uint4 o;
-      o.x = pack_bf16x2(v[0], v[1]);
-      o.y = pack_bf16x2(v[2], v[3]);
-      o.z = pack_bf16x2(v[4], v[5]);
-      o.w = pack_bf16x2(v[6], v[7]);
+      const uint4 o = pack8_bf16_hw(v);
       if (oks[ps]) *(uint4*)(e_y + pixs[ps] * e_ncols + col) = o;
       if constexpr (CHAIN > 0) {
         // (this pass's fp32 rows have been read: the bf16 row takes the first 128 bytes of the same staging row)
@@ -881,8 +845,22 @@ static int thr_t64() { return (int)tuning(MXDET_TUNE_T64); }
 static int thr_t128() { return (int)tuning(MXDET_TUNE_T128); }
 static int thr_par64() { return (int)tuning(MXDET_TUNE_PAR64); }
 
-template <int BM, int BN, int WM, int WN, int NS, bool DGRAD, bool PAR = false, int TAPS = 0, int CHAIN = 0>
+// The tile shapes, each written once: BM x BN tile, WM x WN waves, NS-deep ring. Every launch below names one of them.
+template <int BM_, int BN_, int WM_, int WN_, int NS_>
+struct Tile { static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, NS = NS_; };
+using T128x64 = Tile<128, 64, 4, 1, 2>;
+using T128x128 = Tile<128, 128, 2, 2, 2>;
+using T64x128 = Tile<64, 128, 2, 2, 2>;
+using T64x64 = Tile<64, 64, 2, 2, 3>;
+using T128x128w8 = Tile<128, 128, 2, 4, 2>;     // 8 waves, 64x32 per wave
+using T256x256 = Tile<256, 256, 2, 4, 2>;       // 8 waves, 128x64 per wave, 128 KiB
+using T128x128s4 = Tile<128, 128, 2, 2, 4>;     // forced cfg 3 only
+// grouped launches: cfg number -> tile. The plan (tile counts) and the launch (instantiation) both expand this list.
+#define MXDET_GROUPED_TILES(X) X(0, T128x64) X(1, T128x128) X(2, T64x128) X(3, T64x64)
+
+template <class T, bool DGRAD, bool PAR = false, int TAPS = 0, int CHAIN = 0>
 static int launch_cfg(ConvP& p, hipStream_t s) {
+  constexpr int BM = T::BM, BN = T::BN, WM = T::WM, WN = T::WN, NS = T::NS;
   if (PAR) {   // rows grouped by parity class: tiles never straddle two classes
     int t = 0;
     for (int c = 0; c < 4; ++c) {
@@ -918,20 +896,19 @@ static int launch(ConvP& p, hipStream_t s) {
   const int K = p.KH * p.KW * p.C;
   // forced tile configurations (mxdet_debug_force_conv_cfg: tools/sweep_cfg_all.py, tools/check_cfg.py). 3..8, 15: the
   // run-time-geometry loop; 40..49: the static-tap loop (the caller passes a stride-1 1x1 / 3x3 layer)
-#define MXDET_FORCE_ST(BM, BN, WM, WN, NS)                                                  \
-  (p.KH * p.KW == 1 ? launch_cfg<BM, BN, WM, WN, NS, DGRAD, false, 1>(p, s) : launch_cfg<BM, BN, WM, WN, NS, DGRAD, false, 9>(p, s))
+#define MXDET_FORCE_ST(T) (p.KH * p.KW == 1 ? launch_cfg<T, DGRAD, false, 1>(p, s) : launch_cfg<T, DGRAD, false, 9>(p, s))
   switch (force) {
-    case 3: return launch_cfg<128, 128, 2, 2, 4, DGRAD>(p, s);
-    case 5: return launch_cfg<64, 64, 2, 2, 3, DGRAD>(p, s);
-    case 6: return launch_cfg<64, 128, 2, 2, 2, DGRAD>(p, s);
-    case 7: return launch_cfg<128, 128, 2, 2, 2, DGRAD>(p, s);
-    case 8: return launch_cfg<128, 64, 4, 1, 2, DGRAD>(p, s);
-    case 15: return launch_cfg<256, 256, 2, 4, 2, DGRAD>(p, s);   // 8 waves, 128x64 per wave, 128 KiB
-    case 40: return MXDET_FORCE_ST(64, 64, 2, 2, 3);
-    case 41: return MXDET_FORCE_ST(64, 128, 2, 2, 2);
-    case 45: return MXDET_FORCE_ST(128, 128, 2, 2, 2);
-    case 46: return MXDET_FORCE_ST(128, 64, 4, 1, 2);
-    case 49: return MXDET_FORCE_ST(128, 128, 2, 4, 2);            // 8 waves, 64x32 per wave
+    case 3: return launch_cfg<T128x128s4, DGRAD>(p, s);
+    case 5: return launch_cfg<T64x64, DGRAD>(p, s);
+    case 6: return launch_cfg<T64x128, DGRAD>(p, s);
+    case 7: return launch_cfg<T128x128, DGRAD>(p, s);
+    case 8: return launch_cfg<T128x64, DGRAD>(p, s);
+    case 15: return launch_cfg<T256x256, DGRAD>(p, s);
+    case 40: return MXDET_FORCE_ST(T64x64);
+    case 41: return MXDET_FORCE_ST(T64x128);
+    case 45: return MXDET_FORCE_ST(T128x128);
+    case 46: return MXDET_FORCE_ST(T128x64);
+    case 49: return MXDET_FORCE_ST(T128x128w8);
     default: break;
   }
 #undef MXDET_FORCE_ST
@@ -940,10 +917,10 @@ static int launch(ConvP& p, hipStream_t s) {
   // (a forward 3x3 may be strided: its tap displacements do not depend on the stride; a strided data gradient may not)
   const int st = ((p.stride != 1 && (DGRAD || taps == 1)) || tuning(MXDET_TUNE_STATIC_TAPS) == 0) ? 0
                  : (taps == 1 && p.pad == 0) ? 1 : (p.KH == 3 && p.KW == 3 && p.pad == 1) ? 9 : 0;
-#define MXDET_LAUNCH_ST(BM, BN, WM, WN, NS)                                                        \
-  (st == 1 ? launch_cfg<BM, BN, WM, WN, NS, DGRAD, false, 1>(p, s)                                 \
-           : st == 9 ? launch_cfg<BM, BN, WM, WN, NS, DGRAD, false, 9>(p, s)                       \
-                     : launch_cfg<BM, BN, WM, WN, NS, DGRAD>(p, s))
+#define MXDET_LAUNCH_ST(T)                                      \
+  (st == 1 ? launch_cfg<T, DGRAD, false, 1>(p, s)               \
+           : st == 9 ? launch_cfg<T, DGRAD, false, 9>(p, s)     \
+                     : launch_cfg<T, DGRAD>(p, s))
   if constexpr (DGRAD) {
     if (p.stride == 2 && force == 0) {
       // stride-2 data gradient: parity-grouped rows, only the taps that exist (a quarter of the MACs)
@@ -954,12 +931,12 @@ static int launch(ConvP& p, hipStream_t s) {
         p.par_hc[par] = p.Hd > h0 ? (p.Hd - h0 + 1) / 2 : 0;
         p.par_wc[par] = p.Wd > w0 ? (p.Wd - w0 + 1) / 2 : 0;
       }
-      if (p.Ncols <= 64) return launch_cfg<128, 64, 4, 1, 2, true, true>(p, s);
-      if (t64 >= thr_par64()) return launch_cfg<64, 128, 2, 2, 2, true, true>(p, s);
-      return launch_cfg<64, 64, 2, 2, 3, true, true>(p, s);
+      if (p.Ncols <= 64) return launch_cfg<T128x64, true, true>(p, s);
+      if (t64 >= thr_par64()) return launch_cfg<T64x128, true, true>(p, s);
+      return launch_cfg<T64x64, true, true>(p, s);
     }
   }
-  if (p.Ncols <= 64) return MXDET_LAUNCH_ST(128, 64, 4, 1, 2);
+  if (p.Ncols <= 64) return MXDET_LAUNCH_ST(T128x64);
   if (t128 >= thr_t128() && K > 256) {
     // Largest layers: 256x256 tiles (one 8-wave workgroup per CU, half the LDS-DMA pieces per MFMA of the 128x128
     // tile) for as many whole rounds of the chip's 256 CUs as the layer has; the remaining rows -- a partial round
@@ -970,7 +947,7 @@ static int launch(ConvP& p, hipStream_t s) {
     if (rounds >= 1 && p.Ncols % 256 == 0) {
       ConvP big = p;
       big.tiles_m = (int)(rounds * 256 / tn);
-      int rc = launch_cfg<256, 256, 2, 4, 2, DGRAD>(big, s);
+      int rc = launch_cfg<T256x256, DGRAD>(big, s);
       if (rc) return rc;
       p.m_begin = big.tiles_m * 256;
       if (p.m_begin >= p.M) return rc;
@@ -978,9 +955,9 @@ static int launch(ConvP& p, hipStream_t s) {
     // the remaining rows (a partial round of 256x256 tiles would idle most CUs for a whole tile time): small tiles,
     // so that every CU gets a share of the tail (measured: 64x64 tiles 208 workgroups, vs 128x128 tiles 52 workgroups)
     switch ((int)tuning(MXDET_TUNE_TAIL)) {
-      case 1: return MXDET_LAUNCH_ST(64, 128, 2, 2, 2);
-      case 2: return MXDET_LAUNCH_ST(64, 64, 2, 2, 3);
-      default: return MXDET_LAUNCH_ST(128, 128, 2, 2, 2);
+      case 1: return MXDET_LAUNCH_ST(T64x128);
+      case 2: return MXDET_LAUNCH_ST(T64x64);
+      default: return MXDET_LAUNCH_ST(T128x128);
     }
   }
   // one partial round of 256 x 256 tiles that still covers most of the chip, with a long enough reduction to pay for the
@@ -988,13 +965,13 @@ static int launch(ConvP& p, hipStream_t s) {
   {
     const long long t256 = (long long)(p.M / 256) * (p.Ncols / 256);
     if (p.M % 256 == 0 && p.Ncols % 256 == 0 && t256 >= 160 && t256 <= 256 && K >= 1024 && p.m_begin == 0)
-      return launch_cfg<256, 256, 2, 4, 2, DGRAD>(p, s);
+      return launch_cfg<T256x256, DGRAD>(p, s);
   }
   // many rows, short reduction: 128 x 128 tiles of eight waves (64 x 32 per wave) -- half the LDS-DMA bytes per MFMA of
   // the 64 x 128 tile (the small tiles' K loop is bound by what a CU's vector-memory path takes in, ~64 B/clk)
-  if (st != 0 && p.Ncols >= 128 && t128 >= tuning(MXDET_TUNE_T128W)) return MXDET_LAUNCH_ST(128, 128, 2, 4, 2);
-  if (t64 >= thr_t64()) return MXDET_LAUNCH_ST(64, 128, 2, 2, 2);
-  return MXDET_LAUNCH_ST(64, 64, 2, 2, 3);
+  if (st != 0 && p.Ncols >= 128 && t128 >= tuning(MXDET_TUNE_T128W)) return MXDET_LAUNCH_ST(T128x128w8);
+  if (t64 >= thr_t64()) return MXDET_LAUNCH_ST(T64x128);
+  return MXDET_LAUNCH_ST(T64x64);
 #undef MXDET_LAUNCH_ST
 }
 
@@ -1011,6 +988,28 @@ static int validate(const mxdet_conv_desc_t* d, const char* who) {
                     (long long)d->N * d->Ho * d->Wo * d->Cout < (1ll << 31),
                 MXDET_ESHAPE, "%s: tensor exceeds 2^31 elements", who);
   return MXDET_OK;
+}
+
+// Descriptor -> ConvP, everything that depends on the descriptor alone; the operands (x, w, bias, res, mask / bits_in, y,
+// the chain and split-K fields) are the caller's. Forward: the source is the layer's input, rows are output pixels.
+static void fill_fwd(ConvP& p, const mxdet_conv_desc_t* d) {
+  memset(&p, 0, sizeof(p));
+  p.N = d->N; p.Hs = d->H; p.Ws = d->W; p.C = d->Cin;
+  p.Hd = d->Ho; p.Wd = d->Wo; p.Ncols = d->Cout;
+  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
+  p.relu = d->relu; p.res_up = d->res_upsample;
+  p.M = d->N * d->Ho * d->Wo;
+  p.pf = d->prefetch; p.pf_bytes = d->prefetch ? d->prefetch_bytes : 0;
+  p.bits_out = (unsigned char*)d->relu_bits;
+}
+// Data gradient: the source is the output gradient, rows are input pixels; ReLU is the caller's mask / bits_in operand.
+static void fill_dgrad(ConvP& p, const mxdet_conv_desc_t* d) {
+  memset(&p, 0, sizeof(p));
+  p.N = d->N; p.Hs = d->Ho; p.Ws = d->Wo; p.C = d->Cout;
+  p.Hd = d->H; p.Wd = d->W; p.Ncols = d->Cin;
+  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
+  p.M = d->N * d->H * d->W;
+  p.pf = d->prefetch; p.pf_bytes = d->prefetch ? d->prefetch_bytes : 0;
 }
 
 }  // namespace mxdet
@@ -1038,15 +1037,8 @@ extern "C" int mxdet_conv2d_fwd(const mxdet_conv_desc_t* d, const uint16_t* x, c
   MXDET_REQUIRE(d->Cout % 8 == 0, MXDET_ESHAPE, "conv2d_fwd: Cout %d must be a multiple of 8", d->Cout);
   MXDET_REQUIRE(x && w && y, MXDET_EINVAL, "conv2d_fwd: null pointer");
   ConvP p;
-  memset(&p, 0, sizeof(p));
-  p.x = x; p.w = w; p.bias = bias; p.res = residual; p.mask = nullptr; p.y = y;
-  p.N = d->N; p.Hs = d->H; p.Ws = d->W; p.C = d->Cin;
-  p.Hd = d->Ho; p.Wd = d->Wo; p.Ncols = d->Cout;
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
-  p.relu = d->relu; p.res_up = d->res_upsample;
-  p.M = d->N * d->Ho * d->Wo;
-  p.pf = d->prefetch; p.pf_bytes = d->prefetch ? d->prefetch_bytes : 0;
-  p.bits_out = (unsigned char*)d->relu_bits;
+  fill_fwd(p, d);
+  p.x = x; p.w = w; p.bias = bias; p.res = residual; p.y = y;
   MXDET_REQUIRE(!d->relu_bits || d->Cout % 8 == 0, MXDET_ESHAPE, "conv2d_fwd: relu_bits needs Cout %% 8 == 0");
   return launch<false>(p, as_stream(stream));
 }
@@ -1074,21 +1066,15 @@ extern "C" int mxdet_conv2d_fwd_chain(const mxdet_conv_desc_t* d, const uint16_t
   MXDET_REQUIRE(x && w && w2 && y2, MXDET_EINVAL, "conv2d_fwd_chain: null pointer");
   MXDET_REQUIRE((long long)d->N * d->Ho * d->Wo * cout2 < (1ll << 31), MXDET_ESHAPE, "conv2d_fwd_chain: output exceeds 2^31");
   ConvP p;
-  memset(&p, 0, sizeof(p));
-  p.x = x; p.w = w; p.bias = bias; p.y = nullptr;
-  p.N = d->N; p.Hs = d->H; p.Ws = d->W; p.C = d->Cin;
-  p.Hd = d->Ho; p.Wd = d->Wo; p.Ncols = d->Cout;
-  p.KH = 3; p.KW = 3; p.stride = 1; p.pad = 1;
-  p.relu = d->relu;
-  p.M = d->N * d->Ho * d->Wo;
-  p.pf = d->prefetch; p.pf_bytes = d->prefetch ? d->prefetch_bytes : 0;
+  fill_fwd(p, d);                         // (3x3 / 1 / 1, no res_upsample, no relu_bits: checked above)
+  p.x = x; p.w = w; p.bias = bias;        // no y: the 3x3's tile never leaves the workgroup
   p.chain_w = w2; p.chain_bias = bias2; p.chain_res = residual2; p.chain_y = y2; p.chain_relu = relu2;
   if (w3 != nullptr) {
     MXDET_REQUIRE(cout3 == 64 && y3 != nullptr, MXDET_ESHAPE, "conv2d_fwd_chain: the third convolution needs cout3 == 64 (got %d) and y3",
                   cout3);
     p.chain3_w = w3; p.chain3_bias = bias3; p.chain3_y = y3; p.chain3_relu = relu3;
   }
-  return launch_cfg<128, 64, 4, 1, 2, false, false, 9, 256>(p, as_stream(stream));
+  return launch_cfg<T128x64, false, false, 9, 256>(p, as_stream(stream));
 }
 
 // ---- split-K forward for long reductions on few rows (FC6: 1,024 rois x 12,544 features x 1,024 outputs) ----------------
@@ -1117,19 +1103,16 @@ conv_splitk_fold_kernel(const float* __restrict__ partial, int ksplit, long long
     v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w; v[4] += b.x; v[5] += b.y; v[6] += b.z; v[7] += b.w;
   }
   if (res) {
-    const uint4 rv = *(const uint4*)(res + i);
-    v[0] += __uint_as_float(rv.x << 16); v[1] += __uint_as_float(rv.x & 0xffff0000u);
-    v[2] += __uint_as_float(rv.y << 16); v[3] += __uint_as_float(rv.y & 0xffff0000u);
-    v[4] += __uint_as_float(rv.z << 16); v[5] += __uint_as_float(rv.z & 0xffff0000u);
-    v[6] += __uint_as_float(rv.w << 16); v[7] += __uint_as_float(rv.w & 0xffff0000u);
+    float rf[8];
+    unpack8_bf16(*(const uint4*)(res + i), rf);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] += rf[k];
   }
   if (relu) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) v[k] = v[k] > 0.0f ? v[k] : 0.0f;
   }
-  uint4 o;
-  o.x = pack_bf16x2(v[0], v[1]); o.y = pack_bf16x2(v[2], v[3]); o.z = pack_bf16x2(v[4], v[5]); o.w = pack_bf16x2(v[6], v[7]);
-  *(uint4*)(y + i) = o;
+  *(uint4*)(y + i) = pack8_bf16_hw(v);
 }
 }  // namespace mxdet
 
@@ -1153,12 +1136,10 @@ extern "C" int mxdet_conv2d_fwd_splitk(const mxdet_conv_desc_t* d, const uint16_
   const size_t need = mxdet_conv2d_fwd_splitk_workspace_bytes(d, ksplit);
   MXDET_REQUIRE(workspace && workspace_bytes >= need, MXDET_EWORKSPACE, "conv2d_fwd_splitk: workspace %zu < %zu", workspace_bytes, need);
   ConvP p;
-  memset(&p, 0, sizeof(p));
-  p.x = x; p.w = w; p.bias = nullptr; p.res = nullptr; p.mask = nullptr; p.y = y;
-  p.N = d->N; p.Hs = d->H; p.Ws = d->W; p.C = d->Cin;
-  p.Hd = d->Ho; p.Wd = d->Wo; p.Ncols = d->Cout;
-  p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
-  p.M = d->N * d->Ho * d->Wo;
+  fill_fwd(p, d);                         // (1x1 / 1 / 0, no res_upsample: checked above)
+  p.x = x; p.w = w; p.y = y;
+  // the split kernel writes raw sums: bias, residual and ReLU belong to the fold kernel; no relu_bits, no prefetch hint here
+  p.relu = 0; p.bits_out = nullptr; p.pf = nullptr; p.pf_bytes = 0;
   p.ksplit = ksplit; p.partial = (float*)workspace;
   // tile: 64 x 64 (three workgroups per CU), or 128 x 128 (half the L2 -> LDS bytes per flop: the K loop of the small
   // tile is bound by that path) when the layer still fills the chip with them (tuning key SPLITK_TILE: 0 / 1 / 2 = 128 x 128
@@ -1168,9 +1149,9 @@ extern "C" int mxdet_conv2d_fwd_splitk(const mxdet_conv_desc_t* d, const uint16_
   const long long tiles = (long long)ceil_div(p.M, BT) * ceil_div(p.Ncols, BT);
   MXDET_REQUIRE(tiles % 8 == 0, MXDET_ESHAPE, "conv2d_fwd_splitk: the tile count (%lld) must be a multiple of 8", tiles);
   hipStream_t s = as_stream(stream);
-  if (big == 1) rc = launch_cfg<128, 128, 2, 2, 2, false, false, 1>(p, s);
-  else if (big == 2) rc = launch_cfg<128, 128, 2, 4, 2, false, false, 1>(p, s);
-  else rc = launch_cfg<64, 64, 2, 2, 3, false, false, 1>(p, s);
+  if (big == 1) rc = launch_cfg<T128x128, false, false, 1>(p, s);
+  else if (big == 2) rc = launch_cfg<T128x128w8, false, false, 1>(p, s);
+  else rc = launch_cfg<T64x64, false, false, 1>(p, s);
   if (rc || route_probe_on()) return rc;
   const long long total = (long long)p.M * p.Ncols;
   hipLaunchKernelGGL(conv_splitk_fold_kernel, dim3((unsigned)ceil_div<long long>(total / 8, 256)), dim3(256), 0, s,
@@ -1188,24 +1169,19 @@ extern "C" int mxdet_conv2d_dgrad(const mxdet_conv_desc_t* d, const uint16_t* dy
   MXDET_REQUIRE(d->Cin % 8 == 0, MXDET_ESHAPE, "conv2d_dgrad: Cin %d must be a multiple of 8", d->Cin);
   MXDET_REQUIRE(dy && wt && dx, MXDET_EINVAL, "conv2d_dgrad: null pointer");
   ConvP p;
-  memset(&p, 0, sizeof(p));
-  p.x = dy; p.w = wt; p.bias = nullptr; p.y = dx;
+  fill_dgrad(p, d);
+  p.x = dy; p.w = wt; p.y = dx;
   p.res = residual ? residual : (d->accumulate ? dx : nullptr);
   p.mask = (d->relu && !d->relu_bits) ? relu_mask : nullptr;
   p.bits_in = d->relu ? (const unsigned char*)d->relu_bits : nullptr;
   MXDET_REQUIRE(!d->relu || relu_mask || d->relu_bits, MXDET_EINVAL, "conv2d_dgrad: relu set without relu_mask / relu_bits");
-  p.N = d->N; p.Hs = d->Ho; p.Ws = d->Wo; p.C = d->Cout;
-  p.Hd = d->H; p.Wd = d->W; p.Ncols = d->Cin;
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
-  p.relu = 0; p.res_up = 0;
-  p.M = d->N * d->H * d->W;
-  p.pf = d->prefetch; p.pf_bytes = d->prefetch ? d->prefetch_bytes : 0;
   return launch<true>(p, as_stream(stream));
 }
 
 // ---- grouped convolutions -------------------------------------------------------------------------------------------
-template <int BM, int BN, int WM, int WN, int NS, bool DGRAD>
+template <class T, bool DGRAD>
 static void launch_grouped_cfg(const ConvG* table, int n, int grid, hipStream_t s, int tapclass) {
+  constexpr int BM = T::BM, BN = T::BN, WM = T::WM, WN = T::WN, NS = T::NS;
   // tapclass: 0 = any geometry, 1 = every item a stride-1 1x1, 2 = every item a stride-1 3x3 (static-tap K loop)
   if (route_probe_on()) {
     const int32_t rec[kRouteWords] = {MXDET_ROUTE_CONV_GROUPED, BM, BN, WM, WN, NS, DGRAD, 0, tapclass == 1 ? 1 : tapclass == 2 ? 9 : 0,
@@ -1224,8 +1200,6 @@ static void launch_grouped_cfg(const ConvG* table, int n, int grid, hipStream_t 
                        0, s, table, n);
 }
 
-static const int kGroupedTiles[4][2] = {{128, 64}, {128, 128}, {64, 128}, {64, 64}};   // cfg -> BM, BN
-
 extern "C" size_t mxdet_conv2d_grouped_table_bytes(int32_t n) { return n > 0 ? (size_t)n * sizeof(ConvG) : 0; }
 
 extern "C" int mxdet_conv2d_grouped_plan(const mxdet_conv_item_t* items, int32_t n, int32_t kind, void* table_host,
@@ -1243,33 +1217,21 @@ extern "C" int mxdet_conv2d_grouped_plan(const mxdet_conv_item_t* items, int32_t
     int rc = validate(d, "conv2d_grouped_plan");
     if (rc) return rc;
     ConvP& p = t[i].p;
-    memset(&t[i], 0, sizeof(ConvG));
+    if (kind == 0) fill_fwd(p, d); else fill_dgrad(p, d);      // (block0 / nblocks: below, once the tile is chosen)
     MXDET_REQUIRE(items[i].src && items[i].filt && items[i].dst, MXDET_EINVAL, "conv2d_grouped_plan: item %d: null pointer", i);
     if (kind == 0) {
       MXDET_REQUIRE(d->Cin % 64 == 0 && d->Cout % 8 == 0, MXDET_ESHAPE, "conv2d_grouped_plan: item %d: Cin %% 64, Cout %% 8", i);
       p.x = (const uint16_t*)items[i].src; p.w = (const uint16_t*)items[i].filt; p.bias = items[i].bias;
-      p.res = (const uint16_t*)items[i].residual; p.mask = nullptr; p.y = (uint16_t*)items[i].dst;
-      p.bits_out = (unsigned char*)d->relu_bits;
-      p.N = d->N; p.Hs = d->H; p.Ws = d->W; p.C = d->Cin;
-      p.Hd = d->Ho; p.Wd = d->Wo; p.Ncols = d->Cout;
-      p.relu = d->relu; p.res_up = d->res_upsample;
-      p.M = d->N * d->Ho * d->Wo;
+      p.res = (const uint16_t*)items[i].residual; p.y = (uint16_t*)items[i].dst;
     } else {
       MXDET_REQUIRE(d->Cout % 64 == 0 && d->Cin % 8 == 0, MXDET_ESHAPE, "conv2d_grouped_plan: item %d: Cout %% 64, Cin %% 8", i);
       MXDET_REQUIRE(d->stride == 1, MXDET_ESHAPE, "conv2d_grouped_plan: item %d: strided data gradients are not grouped", i);
       MXDET_REQUIRE(!d->relu || items[i].relu_mask || d->relu_bits, MXDET_EINVAL, "conv2d_grouped_plan: item %d: relu without mask", i);
-      p.x = (const uint16_t*)items[i].src; p.w = (const uint16_t*)items[i].filt; p.bias = nullptr;
-      p.y = (uint16_t*)items[i].dst;
+      p.x = (const uint16_t*)items[i].src; p.w = (const uint16_t*)items[i].filt; p.y = (uint16_t*)items[i].dst;
       p.res = items[i].residual ? (const uint16_t*)items[i].residual : (d->accumulate ? (const uint16_t*)items[i].dst : nullptr);
       p.mask = (d->relu && !d->relu_bits) ? (const uint16_t*)items[i].relu_mask : nullptr;
       p.bits_in = d->relu ? (const unsigned char*)d->relu_bits : nullptr;
-      p.N = d->N; p.Hs = d->Ho; p.Ws = d->Wo; p.C = d->Cout;
-      p.Hd = d->H; p.Wd = d->W; p.Ncols = d->Cin;
-      p.relu = 0; p.res_up = 0;
-      p.M = d->N * d->H * d->W;
     }
-    p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
-    p.pf = d->prefetch; p.pf_bytes = d->prefetch ? d->prefetch_bytes : 0;
     {
       const int tc = (d->stride != 1 && (kind == 1 || d->KH * d->KW == 1)) ? 0
                      : (d->KH == 1 && d->KW == 1 && d->pad == 0) ? 1 : (d->KH == 3 && d->KW == 3 && d->pad == 1) ? 2 : 0;
@@ -1287,7 +1249,12 @@ extern "C" int mxdet_conv2d_grouped_plan(const mxdet_conv_item_t* items, int32_t
   else if (t128_max >= thr_t128() && kmax > 256) cfg = 1;
   else if (t64 >= thr_t64()) cfg = 2;
   else cfg = 3;
-  const int BM = kGroupedTiles[cfg][0], BN = kGroupedTiles[cfg][1];
+  int BM = 0, BN = 0;
+  switch (cfg) {
+#define X(k, T) case k: BM = T::BM; BN = T::BN; break;
+    MXDET_GROUPED_TILES(X)
+#undef X
+  }
   long long blocks = 0;
   for (int i = 0; i < n; ++i) {
     ConvP& p = t[i].p;
@@ -1313,20 +1280,14 @@ extern "C" int mxdet_conv2d_grouped(const void* table_dev, int32_t n, int32_t ki
   hipStream_t s = as_stream(stream);
   const int tc = cfg >> 2;
   cfg &= 3;
-  if (kind == 0) {
-    switch (cfg) {
-      case 0: launch_grouped_cfg<128, 64, 4, 1, 2, false>(t, n, grid, s, tc); break;
-      case 1: launch_grouped_cfg<128, 128, 2, 2, 2, false>(t, n, grid, s, tc); break;
-      case 2: launch_grouped_cfg<64, 128, 2, 2, 2, false>(t, n, grid, s, tc); break;
-      default: launch_grouped_cfg<64, 64, 2, 2, 3, false>(t, n, grid, s, tc); break;
-    }
-  } else {
-    switch (cfg) {
-      case 0: launch_grouped_cfg<128, 64, 4, 1, 2, true>(t, n, grid, s, tc); break;
-      case 1: launch_grouped_cfg<128, 128, 2, 2, 2, true>(t, n, grid, s, tc); break;
-      case 2: launch_grouped_cfg<64, 128, 2, 2, 2, true>(t, n, grid, s, tc); break;
-      default: launch_grouped_cfg<64, 64, 2, 2, 3, true>(t, n, grid, s, tc); break;
-    }
+  switch (cfg) {
+#define X(k, T)                                                            \
+    case k:                                                                \
+      if (kind == 0) launch_grouped_cfg<T, false>(t, n, grid, s, tc);      \
+      else launch_grouped_cfg<T, true>(t, n, grid, s, tc);                 \
+      break;
+    MXDET_GROUPED_TILES(X)
+#undef X
   }
   if (route_probe_on()) return MXDET_OK;
   return check_launch("conv2d_grouped");

@@ -64,13 +64,6 @@ __device__ __forceinline__ DSample deform_sample(const DeformArgs& a, const uint
   return s;
 }
 
-__device__ __forceinline__ void unpack8_bf16(const uint4& v, float* f) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-
 // the four corner rows (8 channels from c0) of a valid sample; corners outside [0,H) x [0,W) read as zero
 __device__ __forceinline__ void load_corners(const DeformArgs& a, const uint16_t* __restrict__ xn, const DSample& s,
                                              int c0, float* v1, float* v2, float* v3, float* v4) {

@@ -91,18 +91,6 @@ __device__ __forceinline__ DAxis dpool_axis(float v, int L) {
   return x;
 }
 
-__device__ __forceinline__ void dp_unpack8(const uint4& v, float* f) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-
-__device__ __forceinline__ void dp_unpack4(const uint2& v, float* f) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-}
-
 // ---- forward: one workgroup per roi; work item = (bin, 8-channel group), channel group fastest -------------------------
 __global__ void __launch_bounds__(256)
 dpool_fwd_kernel(DPoolArgs a, const float* __restrict__ rois, const int32_t* __restrict__ levels,
@@ -126,10 +114,10 @@ dpool_fwd_kernel(DPoolArgs a, const float* __restrict__ rois, const int32_t* __r
         const DAxis x = dpool_axis(ws + (float)iw * g.sub_w, g.W);
         if (!x.valid) continue;
         float v11[8], v12[8], v21[8], v22[8];
-        dp_unpack8(*(const uint4*)(feat + ((long long)y.lo * g.W + x.lo) * a.C + cg * 8), v11);
-        dp_unpack8(*(const uint4*)(feat + ((long long)y.hi * g.W + x.lo) * a.C + cg * 8), v12);
-        dp_unpack8(*(const uint4*)(feat + ((long long)y.lo * g.W + x.hi) * a.C + cg * 8), v21);
-        dp_unpack8(*(const uint4*)(feat + ((long long)y.hi * g.W + x.hi) * a.C + cg * 8), v22);
+        unpack8_bf16(*(const uint4*)(feat + ((long long)y.lo * g.W + x.lo) * a.C + cg * 8), v11);
+        unpack8_bf16(*(const uint4*)(feat + ((long long)y.hi * g.W + x.lo) * a.C + cg * 8), v12);
+        unpack8_bf16(*(const uint4*)(feat + ((long long)y.lo * g.W + x.hi) * a.C + cg * 8), v21);
+        unpack8_bf16(*(const uint4*)(feat + ((long long)y.hi * g.W + x.hi) * a.C + cg * 8), v22);
         const float w11 = (1.0f - x.d) * (1.0f - y.d), w12 = (1.0f - x.d) * y.d;
         const float w21 = x.d * (1.0f - y.d), w22 = x.d * y.d;
 #pragma unroll
@@ -176,7 +164,7 @@ dpool_bwd_trans_kernel(DPoolArgs a, long long R, const float* __restrict__ rois,
   float gx = 0.0f, gy = 0.0f, gm = 0.0f;
   for (int c0 = lane * 4; c0 < a.C; c0 += 256) {
     float d[4];
-    dp_unpack4(*(const uint2*)(drow + c0), d);
+    unpack4_bf16(*(const uint2*)(drow + c0), d);
     for (int ih = 0; ih < a.S; ++ih) {
       const DAxis y = dpool_axis(hs + (float)ih * g.sub_h, g.H);
       if (!y.valid) continue;
@@ -184,10 +172,10 @@ dpool_bwd_trans_kernel(DPoolArgs a, long long R, const float* __restrict__ rois,
         const DAxis x = dpool_axis(ws + (float)iw * g.sub_w, g.W);
         if (!x.valid) continue;
         float u00[4], u01[4], u10[4], u11[4];       // MXNet's names: u01 = (y1, x0), u10 = (y0, x1)
-        dp_unpack4(*(const uint2*)(feat + ((long long)y.lo * g.W + x.lo) * a.C + c0), u00);
-        dp_unpack4(*(const uint2*)(feat + ((long long)y.hi * g.W + x.lo) * a.C + c0), u01);
-        dp_unpack4(*(const uint2*)(feat + ((long long)y.lo * g.W + x.hi) * a.C + c0), u10);
-        dp_unpack4(*(const uint2*)(feat + ((long long)y.hi * g.W + x.hi) * a.C + c0), u11);
+        unpack4_bf16(*(const uint2*)(feat + ((long long)y.lo * g.W + x.lo) * a.C + c0), u00);
+        unpack4_bf16(*(const uint2*)(feat + ((long long)y.hi * g.W + x.lo) * a.C + c0), u01);
+        unpack4_bf16(*(const uint2*)(feat + ((long long)y.lo * g.W + x.hi) * a.C + c0), u10);
+        unpack4_bf16(*(const uint2*)(feat + ((long long)y.hi * g.W + x.hi) * a.C + c0), u11);
         const float w00 = (1.0f - x.d) * (1.0f - y.d), w01 = (1.0f - x.d) * y.d;
         const float w10 = x.d * (1.0f - y.d), w11 = x.d * y.d;
         // coinciding corners (integer or clamped position): the derivative is exactly 0, not a rounding residue
@@ -425,7 +413,7 @@ dpool_gather_kernel(DPoolArgs a, DpGrid gr, int R, const DpRoiRec* __restrict__ 
           const float ws = dp_readlane_f(e.ws, b), hs = dp_readlane_f(e.hs, b), sc = dp_readlane_f(e.scale, b);
           float go[4] = {0.0f, 0.0f, 0.0f, 0.0f};
           if (live) {
-            dp_unpack4(*(const uint2*)(dout + ((long long)r * a.NB + b) * a.C + c0), go);
+            unpack4_bf16(*(const uint2*)(dout + ((long long)r * a.NB + b) * a.C + c0), go);
 #pragma unroll
             for (int k = 0; k < 4; ++k) go[k] = go[k] * sc;
           }
@@ -456,7 +444,7 @@ dpool_gather_kernel(DPoolArgs a, DpGrid gr, int R, const DpRoiRec* __restrict__ 
     float v[4] = {acc[j][0], acc[j][1], acc[j][2], acc[j][3]};
     if (a.acc) {
       float old[4];
-      dp_unpack4(*(const uint2*)o, old);
+      unpack4_bf16(*(const uint2*)o, old);
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] = v[k] + old[k];
     }

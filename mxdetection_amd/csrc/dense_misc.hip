@@ -8,8 +8,6 @@
 
 namespace mxdet {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(8))) short s16x8_t;
 
 // ---------------------------------------------------------------------------------------------
@@ -342,20 +340,6 @@ stem_pool_kernel(const T* __restrict__ img, int N, int H, int W, int Ho, int Wo,
 }
 
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void unpack8f(const uint4& v, float* f) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-__device__ __forceinline__ uint4 pack8f(const float* v) {
-  uint4 o;
-  o.x = (unsigned)f32_to_bf16_bits(v[0]) | ((unsigned)f32_to_bf16_bits(v[1]) << 16);
-  o.y = (unsigned)f32_to_bf16_bits(v[2]) | ((unsigned)f32_to_bf16_bits(v[3]) << 16);
-  o.z = (unsigned)f32_to_bf16_bits(v[4]) | ((unsigned)f32_to_bf16_bits(v[5]) << 16);
-  o.w = (unsigned)f32_to_bf16_bits(v[6]) | ((unsigned)f32_to_bf16_bits(v[7]) << 16);
-  return o;
-}
 
 __global__ void maxpool3x3s2_kernel(const uint16_t* __restrict__ x, int N, int H, int W, int C, int Ho,
                                     int Wo, uint16_t* __restrict__ y) {
@@ -379,12 +363,12 @@ __global__ void maxpool3x3s2_kernel(const uint16_t* __restrict__ x, int N, int H
       if (wi < 0 || wi >= W) continue;
       uint4 v = *(const uint4*)(x + (((long long)n * H + hi) * W + wi) * C + cg * 8);
       float f[8];
-      unpack8f(v, f);
+      unpack8_bf16(v, f);
 #pragma unroll
       for (int k = 0; k < 8; ++k) m[k] = f[k] > m[k] ? f[k] : m[k];
     }
   }
-  *(uint4*)(y + pix * C + cg * 8) = pack8f(m);
+  *(uint4*)(y + pix * C + cg * 8) = pack8_bf16_exact(m);
 }
 
 __global__ void subsample2_kernel(const uint16_t* __restrict__ x, int N, int H, int W, int C, int Ho,
@@ -416,7 +400,7 @@ __global__ void upsample2_bwd_kernel(const uint16_t* __restrict__ dfine, int N, 
   float s[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) s[k] = 0.0f;
-  if (accumulate) unpack8f(*(const uint4*)(dcoarse + pix * C + cg * 8), s);
+  if (accumulate) unpack8_bf16(*(const uint4*)(dcoarse + pix * C + cg * 8), s);
   for (int dh = 0; dh < 2; ++dh) {
     int hf = 2 * hc + dh;
     if (hf >= Hf) continue;
@@ -424,12 +408,12 @@ __global__ void upsample2_bwd_kernel(const uint16_t* __restrict__ dfine, int N, 
       int wf = 2 * wc + dw;
       if (wf >= Wf) continue;
       float f[8];
-      unpack8f(*(const uint4*)(dfine + (((long long)n * Hf + hf) * Wf + wf) * C + cg * 8), f);
+      unpack8_bf16(*(const uint4*)(dfine + (((long long)n * Hf + hf) * Wf + wf) * C + cg * 8), f);
 #pragma unroll
       for (int k = 0; k < 8; ++k) s[k] += f[k];
     }
   }
-  *(uint4*)(dcoarse + pix * C + cg * 8) = pack8f(s);
+  *(uint4*)(dcoarse + pix * C + cg * 8) = pack8_bf16_exact(s);
 }
 
 // adjoint of subsample2: dx = 0 except dx[n,2i,2j,:] = dy[n,i,j,:]  (+)=
@@ -447,14 +431,14 @@ __global__ void subsample2_bwd_kernel(const uint16_t* __restrict__ dy, int N, in
   float s[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) s[k] = 0.0f;
-  if (accumulate) unpack8f(*(const uint4*)(dx + pix * C + cg * 8), s);
+  if (accumulate) unpack8_bf16(*(const uint4*)(dx + pix * C + cg * 8), s);
   if (!(hi & 1) && !(wi & 1) && (hi >> 1) < Ho && (wi >> 1) < Wo) {
     float f[8];
-    unpack8f(*(const uint4*)(dy + (((long long)n * Ho + (hi >> 1)) * Wo + (wi >> 1)) * C + cg * 8), f);
+    unpack8_bf16(*(const uint4*)(dy + (((long long)n * Ho + (hi >> 1)) * Wo + (wi >> 1)) * C + cg * 8), f);
 #pragma unroll
     for (int k = 0; k < 8; ++k) s[k] += f[k];
   }
-  *(uint4*)(dx + pix * C + cg * 8) = pack8f(s);
+  *(uint4*)(dx + pix * C + cg * 8) = pack8_bf16_exact(s);
 }
 
 __global__ void add_bf16_kernel(const uint4* __restrict__ a, const uint4* __restrict__ b, long long n8,
@@ -462,11 +446,11 @@ __global__ void add_bf16_kernel(const uint4* __restrict__ a, const uint4* __rest
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n8) return;
   float fa[8], fb[8];
-  unpack8f(a[i], fa);
-  unpack8f(b[i], fb);
+  unpack8_bf16(a[i], fa);
+  unpack8_bf16(b[i], fb);
 #pragma unroll
   for (int k = 0; k < 8; ++k) fa[k] += fb[k];
-  out[i] = pack8f(fa);
+  out[i] = pack8_bf16_exact(fa);
 }
 
 __global__ void relu_bwd_kernel(const uint4* __restrict__ dy, const uint4* __restrict__ y, long long n8,
@@ -474,11 +458,11 @@ __global__ void relu_bwd_kernel(const uint4* __restrict__ dy, const uint4* __res
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n8) return;
   float g[8], a[8];
-  unpack8f(dy[i], g);
-  unpack8f(y[i], a);
+  unpack8_bf16(dy[i], g);
+  unpack8_bf16(y[i], a);
 #pragma unroll
   for (int k = 0; k < 8; ++k) g[k] = a[k] > 0.0f ? g[k] : 0.0f;
-  dx[i] = pack8f(g);
+  dx[i] = pack8_bf16_exact(g);
 }
 
 __global__ void f32_to_bf16_kernel(const float* __restrict__ x, long long n, int accumulate,
@@ -490,11 +474,11 @@ __global__ void f32_to_bf16_kernel(const float* __restrict__ x, long long n, int
     float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     if (accumulate) {
       float o[8];
-      unpack8f(*(const uint4*)(y + i), o);
+      unpack8_bf16(*(const uint4*)(y + i), o);
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] += o[k];
     }
-    *(uint4*)(y + i) = pack8f(v);
+    *(uint4*)(y + i) = pack8_bf16_exact(v);
   } else {
     for (long long j = i; j < n; ++j) {
       float v = x[j];

@@ -40,15 +40,6 @@ struct GnGeom {
   int relu;
 };
 
-__device__ __forceinline__ void unpack8(const uint4& v, float (&f)[8]) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  return make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7]));
-}
 // Keeps a register-resident vector packed between two passes: without it hipcc carries the 8 unpacked floats of every
 // vector (and values derived from them) across the block reduction and spills; re-unpacking is two ALU ops per value.
 __device__ __forceinline__ void keep_packed(uint4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
@@ -140,7 +131,7 @@ __global__ void __launch_bounds__(TB) gn_fwd_kernel(GnGeom a, const uint16_t* __
 #pragma unroll
   for (int i = 0; i < VPT; ++i) {   // padding vectors are zero: they add nothing
     float f[8];
-    unpack8(xv[i], f);
+    unpack8_bf16(xv[i], f);
     s[0] += ((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7]));
   }
   group_sums<1>(a, sh, t, cv, active, s, r);
@@ -153,7 +144,7 @@ __global__ void __launch_bounds__(TB) gn_fwd_kernel(GnGeom a, const uint16_t* __
   for (int i = 0; i < VPT; ++i) {
     if (p0 + i * a.PR < pend) {
       float f[8];
-      unpack8(xv[i], f);
+      unpack8_bf16(xv[i], f);
       float q = 0.f;
 #pragma unroll
       for (int k = 0; k < 8; ++k) { const float d = f[k] - mean; q += d * d; }
@@ -190,13 +181,13 @@ __global__ void __launch_bounds__(TB) gn_fwd_kernel(GnGeom a, const uint16_t* __
     const int p = p0 + i * a.PR;
     if (p < pend) {
       float f[8];
-      unpack8(xv[i], f);
+      unpack8_bf16(xv[i], f);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const float v = gn_affine((f[k] - mean) * rstd, ga[k], be[k]);
         f[k] = a.relu ? fmaxf(v, 0.f) : v;
       }
-      *reinterpret_cast<uint4*>(y + sbase + GN_VOFF(p)) = pack8(f);
+      *reinterpret_cast<uint4*>(y + sbase + GN_VOFF(p)) = pack8_bf16_hw(f);
     }
   }
 }
@@ -257,13 +248,13 @@ __global__ void __launch_bounds__(kGnBlock) gn_apply_kernel(GnGeom a, const uint
     const int p = p0 + i * a.PR;
     if (p < pend) {
       float f[8];
-      unpack8(xv[i], f);
+      unpack8_bf16(xv[i], f);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const float v = gn_affine((f[k] - mean) * rstd, ga[k], be[k]);
         f[k] = a.relu ? fmaxf(v, 0.f) : v;
       }
-      *reinterpret_cast<uint4*>(y + sbase + GN_VOFF(p)) = pack8(f);
+      *reinterpret_cast<uint4*>(y + sbase + GN_VOFF(p)) = pack8_bf16_hw(f);
     }
   }
 }
@@ -318,10 +309,10 @@ __global__ void __launch_bounds__(TB) gn_bwd_kernel(GnGeom a, const uint16_t* __
 #pragma unroll
       for (int i = 0; i < VPT; ++i) {
         float f[8];
-        unpack8(xv[i], f);
+        unpack8_bf16(xv[i], f);
 #pragma unroll
         for (int k = 0; k < 8; ++k) f[k] = gn_affine((f[k] - mean) * rstd, ga[k], be[k]);
-        const uint4 yv = pack8(f);
+        const uint4 yv = pack8_bf16_hw(f);
         gv_[i].x &= positive_mask(yv.x); gv_[i].y &= positive_mask(yv.y);
         gv_[i].z &= positive_mask(yv.z); gv_[i].w &= positive_mask(yv.w);
       }
@@ -336,8 +327,8 @@ __global__ void __launch_bounds__(TB) gn_bwd_kernel(GnGeom a, const uint16_t* __
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
       float f[8], d[8];
-      unpack8(xv[i], f);
-      unpack8(gv_[i], d);
+      unpack8_bf16(xv[i], f);
+      unpack8_bf16(gv_[i], d);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const float xh = (f[k] - mean) * rstd;
@@ -376,14 +367,14 @@ __global__ void __launch_bounds__(TB) gn_bwd_kernel(GnGeom a, const uint16_t* __
       const int p = p0 + i * a.PR;
       if (active && p < pend) {
         float f[8], d[8];
-        unpack8(xv[i], f);
-        unpack8(gv_[i], d);
+        unpack8_bf16(xv[i], f);
+        unpack8_bf16(gv_[i], d);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           const float xh = (f[k] - mean) * rstd;
           f[k] = rstd * (d[k] * ga[k] - (c2 + xh * c1));
         }
-        *reinterpret_cast<uint4*>(dx + sbase + GN_VOFF(p)) = pack8(f);
+        *reinterpret_cast<uint4*>(dx + sbase + GN_VOFF(p)) = pack8_bf16_hw(f);
       }
       __builtin_amdgcn_sched_barrier(0);
     }

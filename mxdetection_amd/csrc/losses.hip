@@ -455,8 +455,8 @@ retina_loss_vec_kernel(const uint16_t* __restrict__ cls, const uint16_t* __restr
       if (lab > 0) {
         const float4 t = targets[gi];
         const uint2 dv = *(const uint2*)d;
-        const float dd[4] = {__uint_as_float(dv.x << 16), __uint_as_float(dv.x & 0xffff0000u),
-                             __uint_as_float(dv.y << 16), __uint_as_float(dv.y & 0xffff0000u)};
+        float dd[4];
+        unpack4_bf16(dv, dd);
         const float tt[4] = {t.x, t.y, t.z, t.w};
         unsigned short gb[4];
 #pragma unroll

@@ -75,13 +75,6 @@ __device__ __forceinline__ Taps bilinear_taps(float y, float x, int H, int W) {
   return t;
 }
 
-__device__ __forceinline__ void unpack8(const uint4& v, float* f) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-
 // forward: one workgroup per roi; work item = (bin, 8-channel group), channel group fastest.
 __global__ void __launch_bounds__(256)
 roi_align_fwd_kernel(FeatPyr f, int C, const float* __restrict__ rois,
@@ -113,7 +106,7 @@ roi_align_fwd_kernel(FeatPyr f, int C, const float* __restrict__ rois,
         const uint4 v3 = *(const uint4*)(feat + ((long long)t.yh * g.W + t.xl) * C + cg * 8);
         const uint4 v4 = *(const uint4*)(feat + ((long long)t.yh * g.W + t.xh) * C + cg * 8);
         float a[8], b[8], c[8], d[8];
-        unpack8(v1, a); unpack8(v2, b); unpack8(v3, c); unpack8(v4, d);
+        unpack8_bf16(v1, a); unpack8_bf16(v2, b); unpack8_bf16(v3, c); unpack8_bf16(v4, d);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           float s = t.w1 * a[k];
@@ -362,6 +355,8 @@ roi_align_bwd_gather_kernel(FeatPyr f, RoiRows rr, int C, const RoiTab* __restri
             const int xl = __builtin_amdgcn_readlane(xl_, sx), xh = __builtin_amdgcn_readlane(xh_, sx);
             const float hx = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(hx_), sx));
             const float lx = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(lx_), sx));
+            // (here and at the two accumulate sites below the half-vector unpack stays spelled out: with unpack4_bf16
+            // hipcc emits different code for the gather and segment kernels)
             float go[4] = {__uint_as_float(gv.x << 16), __uint_as_float(gv.x & 0xffff0000u),
                            __uint_as_float(gv.y << 16), __uint_as_float(gv.y & 0xffff0000u)};
             // grad / count: a power-of-two count (sampling_ratio 1, 2, 4) divides exactly as a multiplication

@@ -98,11 +98,7 @@ __device__ __forceinline__ void wgrad3_tile(const WgradP& p, int b, unsigned cha
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid >> 1, wn = wid & 1;
-  {
-    const int nwg = p.t3_nwg;
-    int q = nwg >> 3, r = nwg & 7, xcd = b & 7, idx = b >> 3;
-    b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  b = xcd_tile_order(b, p.t3_nwg);
   // kh fastest: the three workgroups of a (dy tile, x tile) sit next to each other in one XCD's queue; then the ci
   // tiles (they share the dy tile), then the co tiles, the pixel range slowest
   const int kh = b % 3; b /= 3;

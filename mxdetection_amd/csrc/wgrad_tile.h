@@ -5,11 +5,6 @@
 
 namespace mxdet {
 
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-
 #ifndef MXDET_WGRAD_BKP
 #define MXDET_WGRAD_BKP 32
 #endif
@@ -48,9 +43,6 @@ __device__ __forceinline__ s16x4_t tr_read(const unsigned char* lds_base, int by
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
       (__attribute__((address_space(3))) s16x4_t*)(lds_base + byte_off));
 }
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 // One 32-pixel MFMA k-step of a stage (HH = which 32 rows of the stage's images): 16 transposed fragment reads, 16 MFMAs.
 // Fragment reads in inline asm: behind the ds_read_tr builtin hipcc cannot tell that the read does not touch the ring
@@ -123,8 +115,6 @@ __device__ __forceinline__ void wgrad_tile(const WgradP& p, int b, unsigned char
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid >> 1, wn = wid & 1;
-  // XCD-aware order with the tap fastest: the KH*KW workgroups that share one (dy tile, shifted x tile)
-  // pair sit next to each other in one XCD's queue and hit that XCD's L2 for 8 of 9 reads.
   if (b >= p.nwg_main) {
     // bias-gradient workgroups (appended to the grid, they stream dy while the MFMA workgroups compute):
     // column sums of this split's pixel range for one 128-channel co tile, fixed order
@@ -137,11 +127,10 @@ __device__ __forceinline__ void wgrad_tile(const WgradP& p, int b, unsigned char
     float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (co < p.Cout)
       for (int m = m0 + r0; m < m1; m += 16) {
-        uint4 v = *(const uint4*)(p.dy + (size_t)m * p.Cout + co);
-        s[0] += __uint_as_float(v.x << 16); s[1] += __uint_as_float(v.x & 0xffff0000u);
-        s[2] += __uint_as_float(v.y << 16); s[3] += __uint_as_float(v.y & 0xffff0000u);
-        s[4] += __uint_as_float(v.z << 16); s[5] += __uint_as_float(v.z & 0xffff0000u);
-        s[6] += __uint_as_float(v.w << 16); s[7] += __uint_as_float(v.w & 0xffff0000u);
+        const uint4 v = *(const uint4*)(p.dy + (size_t)m * p.Cout + co);
+        float f[8];
+        unpack8_bf16(v, f);
+        for (int k = 0; k < 8; ++k) s[k] += f[k];
       }
     float* red = (float*)&smem[0][0][0];                  // [16 rows][128 ch]
 #pragma unroll
@@ -157,11 +146,9 @@ __device__ __forceinline__ void wgrad_tile(const WgradP& p, int b, unsigned char
     }
     return;
   }
-  {
-    const int nwg = p.nwg_main;
-    int q = nwg >> 3, r = nwg & 7, xcd = b & 7, idx = b >> 3;
-    b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  // (with the tap fastest: the KH*KW workgroups that share one (dy tile, shifted x tile) pair sit next to each other in
+  // one XCD's queue and hit that XCD's L2 for 8 of 9 reads)
+  b = xcd_tile_order(b, p.nwg_main);
   const int ntaps = p.KH * p.KW;
   const int tap = b % ntaps; b /= ntaps;
   // the operand with more channels is the one to share inside an XCD: its tile index moves slowest, so the workgroups
