@@ -255,7 +255,8 @@ int mxdet_smooth_l1_bwd(const float* pred, const float* target, const float* wei
 
 /* Sigmoid focal loss (RetinaNet): logits [n,C] (dtype f32|bf16), labels[n] int32 (-1 ignore,
  * 0 background, c in 1..C foreground class c), normaliser = max(1, #foreground) computed on device.
- * loss_out[1] fp32 (sum / normaliser, fixed reduction order); grad written in the logits dtype.
+ * loss_out[1] fp32 (sum / normaliser, fixed reduction order); grad written in the logits dtype: exactly the n*C
+ * elements (zeros for ignored rows), scaled by grad_scale.
  * workspace: mxdet_loss_workspace_bytes(n). */
 size_t mxdet_loss_workspace_bytes(int64_t n);
 int mxdet_focal_loss(const void* logits, int32_t dtype, const int32_t* labels, int64_t n, int32_t C,
@@ -301,7 +302,9 @@ int mxdet_loss_finalize(const float* partial, int32_t count, int32_t ncomp, floa
 
 /* Box-head losses fused fwd+bwd. cls_logits: [R,num_classes] (dtype), softmax CE with ignore label
  * -1, normalised by norm; bbox_pred [R,4*num_reg] vs targets/weights, smooth-L1(sigma) * norm.
- * loss_out[2] = (cls, reg); grads written in the logits dtype scaled by loss_scale. */
+ * loss_out[2] = (cls, reg); grads written in the logits dtype scaled by loss_scale: columns [0,num_classes) of every
+ * grad_cls row and [0,reg_dim) of every grad_reg row (zeros for ignored rows / zero weights); columns from there up to
+ * ld_cls / ld_reg are left untouched, so both may be column views of one fused buffer. */
 int mxdet_rcnn_loss(const void* cls_logits, const void* bbox_pred, int32_t dtype, int32_t ld_cls,
                     int32_t ld_reg, const int32_t* labels, const float* bbox_targets,
                     const float* bbox_weights, int64_t R, int32_t num_classes, int32_t reg_dim,

@@ -213,6 +213,8 @@ DEBUG_SYMBOLS = ("mxdet_debug_force_conv_cfg", "mxdet_debug_force_wgrad_ksplit",
 TUNING_KEYS = {"T64": 0, "T128": 1, "PAR64": 2, "WG_TARGET": 3, "WG_MINSTEPS": 4, "WG_MAXSTEPS": 5, "T3_ENABLE": 6,
                "T3_TARGET": 7, "T3_MINSTEPS": 8, "T3_NS": 9, "TAIL": 10, "WG_NS": 11, "ROI_TABLE": 12, "ROI_ROWS": 13, "STATIC_TAPS": 14,
                "T128W": 15, "T3_MIX": 16, "SPLITK_TILE": 17, "T3_PER_ITEM": 18}
+# word 0 of a route-probe record (MXDET_ROUTE_* in include/mxdet_debug.h)
+ROUTE_KINDS = {"CONV": 1, "WGRAD": 2, "CONV_GROUPED": 3, "WGRAD_GROUPED": 4, "RETINA_LOSS": 5}
 
 _lib = None
 

@@ -27,13 +27,19 @@ __device__ __forceinline__ float softplus_neg_abs(float z) {
   float az = z < 0.0f ? -z : z;
   return mxdet_logf(1.0f + mxdet_expf(-az));
 }
-// both at once from ONE exp(-|z|): bit-identical to the two functions above (they evaluate the same exponential)
-__device__ __forceinline__ void sigmoid_softplus(float z, float& p, float& sp) {
+// p = sigmoid(z), q = 1 - p and sp = log(1 + exp(-|z|)) from ONE exp(-|z|), each with its full relative accuracy at large |z|:
+// q is the other quotient of the same division, not 1.0f - p (which cancels once p is near 1), and sp keeps the part of t that
+// 1 + t rounds away (log1p: log(d) * t / (d - 1); d - 1 is exact, and sp = t once d rounds to 1). The focal terms
+// (1-p)^gamma * log p and p^gamma * log(1-p) of a well-classified element are products of exactly these small numbers.
+__device__ __forceinline__ void sigmoid_softplus(float z, float& p, float& q, float& sp) {
   const float az = z < 0.0f ? -z : z;
   const float t = mxdet_expf(-az);
   const float d = 1.0f + t;
-  sp = mxdet_logf(d);
-  p = z >= 0.0f ? 1.0f / d : t / d;
+  const float dm1 = d - 1.0f;
+  sp = dm1 == 0.0f ? t : mxdet_logf(d) * (t / dm1);
+  const float big = 1.0f / d, small = t / d;
+  p = z >= 0.0f ? big : small;
+  q = z >= 0.0f ? small : big;
 }
 __device__ __forceinline__ float sigmoidf_det(float z) {
   // 1/(1+exp(-z)) evaluated on the stable side
@@ -90,20 +96,19 @@ focal_kernel(const void* __restrict__ logits, int dtype, const int32_t* __restri
     float z = load_as_f32(logits, i, dtype);
     float g = 0.0f;
     if (lab >= 0) {
-      float p, sp;
-      sigmoid_softplus(z, p, sp);
+      float p, q, sp;
+      sigmoid_softplus(z, p, q, sp);
       // log(p) = -(max(-z,0) + sp); log(1-p) = -(max(z,0) + sp)
       float logp = -((z < 0.0f ? -z : 0.0f) + sp);
       float log1mp = -((z > 0.0f ? z : 0.0f) + sp);
       if (lab == c + 1) {
-        float q = 1.0f - p;
         float mod = (gamma == 2.0f) ? q * q : mxdet_expf(gamma * mxdet_logf(q > 1e-30f ? q : 1e-30f));
         acc += -alpha * mod * logp;
         g = -alpha * mod * (q - gamma * p * logp);
       } else {
         float mod = (gamma == 2.0f) ? p * p : mxdet_expf(gamma * mxdet_logf(p > 1e-30f ? p : 1e-30f));
         acc += -(1.0f - alpha) * mod * log1mp;
-        g = (1.0f - alpha) * mod * (p - gamma * (1.0f - p) * log1mp);
+        g = (1.0f - alpha) * mod * (p - gamma * q * log1mp);
       }
     }
     store_from_f32(grad, i, dtype, g * inv_norm * grad_scale);
@@ -417,20 +422,19 @@ retina_loss_vec_kernel(const uint16_t* __restrict__ cls, const uint16_t* __restr
         for (int h = 0; h < 2; ++h) {
           const int c = ck * 8 + 2 * k + h;
           const float x = h ? __uint_as_float(zw[k] & 0xffff0000u) : __uint_as_float(zw[k] << 16);
-          float p, sp;
-          sigmoid_softplus(x, p, sp);
+          float p, q, sp;
+          sigmoid_softplus(x, p, q, sp);
           const float logp = -((x < 0.0f ? -x : 0.0f) + sp);
           const float log1mp = -((x > 0.0f ? x : 0.0f) + sp);
           float g;
           if (lab == c + 1) {
-            const float q = 1.0f - p;
             const float mod = (gamma == 2.0f) ? q * q : mxdet_expf(gamma * mxdet_logf(q > 1e-30f ? q : 1e-30f));
             lc += -alpha * mod * logp;
             g = -alpha * mod * (q - gamma * p * logp);
           } else {
             const float mod = (gamma == 2.0f) ? p * p : mxdet_expf(gamma * mxdet_logf(p > 1e-30f ? p : 1e-30f));
             lc += -(1.0f - alpha) * mod * log1mp;
-            g = (1.0f - alpha) * mod * (p - gamma * (1.0f - p) * log1mp);
+            g = (1.0f - alpha) * mod * (p - gamma * q * log1mp);
           }
           packed |= (unsigned)f32_to_bf16_bits(g * inv * loss_scale) << (16 * h);
         }
@@ -503,19 +507,18 @@ retina_loss_kernel(const uint16_t* __restrict__ cls, const uint16_t* __restrict_
       float g = 0.0f;
       if (lab >= 0) {
         float x = bf16_bits_to_f32(z[c]);
-        float p, sp;
-        sigmoid_softplus(x, p, sp);
+        float p, q, sp;
+        sigmoid_softplus(x, p, q, sp);
         float logp = -((x < 0.0f ? -x : 0.0f) + sp);
         float log1mp = -((x > 0.0f ? x : 0.0f) + sp);
         if (lab == c + 1) {
-          float q = 1.0f - p;
           float mod = (gamma == 2.0f) ? q * q : mxdet_expf(gamma * mxdet_logf(q > 1e-30f ? q : 1e-30f));
           lc += -alpha * mod * logp;
           g = -alpha * mod * (q - gamma * p * logp);
         } else {
           float mod = (gamma == 2.0f) ? p * p : mxdet_expf(gamma * mxdet_logf(p > 1e-30f ? p : 1e-30f));
           lc += -(1.0f - alpha) * mod * log1mp;
-          g = (1.0f - alpha) * mod * (p - gamma * (1.0f - p) * log1mp);
+          g = (1.0f - alpha) * mod * (p - gamma * q * log1mp);
         }
       }
       gz[c] = f32_to_bf16_bits(g * inv * loss_scale);
@@ -582,6 +585,11 @@ extern "C" int mxdet_retina_loss_level(const uint16_t* cls, const uint16_t* reg,
   // 16-byte path: whole 8-channel chunks per anchor and 16-B / 8-B aligned rows
   const bool vec = (C % 8 == 0) && (ld_cls % 8 == 0) && (ld_reg % 4 == 0) && (((uintptr_t)cls | (uintptr_t)grad_cls) % 16 == 0) &&
                    (((uintptr_t)reg | (uintptr_t)grad_reg) % 8 == 0);
+  if (route_probe_on()) {   // mxdet_debug_route_probe: say which form would run, touch nothing
+    const int32_t rec[kRouteWords] = {MXDET_ROUTE_RETINA_LOSS, vec ? 1 : 0, blocks};
+    route_record(rec);
+    return MXDET_OK;
+  }
   if (vec)
     hipLaunchKernelGGL(retina_loss_vec_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), cls, reg, N, H * W, A, C,
                        ld_cls, ld_reg, cls_labels, (const float4*)bbox_targets, (long long)A_total, (long long)level_offset,
