@@ -311,6 +311,44 @@ int mxdet_rcnn_loss(const void* cls_logits, const void* bbox_pred, int32_t dtype
                     float sigma, float norm, float loss_scale, float* loss_out, void* grad_cls,
                     void* grad_reg, void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
 
+/* IoU-family box losses on the DECODED box. Per element: a box b (roi / anchor), a ground-truth box g and
+ * four raw deltas d; the prediction is b decoded by d * stds ("+1" convention, means 0, dw / dh clamped at
+ * MXDET_BBOX_XFORM_CLIP, no image clip), evaluated relative to b's corner (x1, y1). L = 1 - IoU (MXDET_IOU_LOSS_IOU),
+ * + (C - U) / C with C the enclosing box's area (_GIOU), or + rho^2 / (cw^2 + ch^2) with rho the centre distance and
+ * cw, ch the enclosing box's sides (_DIOU). No eps: the union is positive for every finite input. At an exact tie of a
+ * max / min pair the gradient is the mean of the two one-sided gradients. stds are passed by value as four floats.
+ * No entry synchronises with the host or uses atomics (capturable; sums in fixed order). */
+#define MXDET_IOU_LOSS_IOU 0
+#define MXDET_IOU_LOSS_GIOU 1
+#define MXDET_IOU_LOSS_DIOU 2
+/* The unfused primitive. boxes / gt [n,4] f32 (16-byte aligned), deltas and grad_deltas rows of ld >= 4 elements (dtype
+ * f32 | bf16), weight [n] or NULL. loss[i] = weight[i] * L_i; grad_deltas[i, 0..3] = weight[i] * grad_scale * dL_i / dd
+ * (columns 4 .. ld are left untouched). n == 0 returns MXDET_OK. */
+int mxdet_box_iou_loss(const float* boxes, const float* gt, const void* deltas, int32_t dtype, int32_t ld,
+                       const float* weight, int64_t n, int32_t kind, float std_x, float std_y, float std_w, float std_h,
+                       float grad_scale, float* loss, void* grad_deltas, mxdet_stream_t stream);
+/* mxdet_rcnn_loss with the regression term replaced: for labels[r] > 0 the box is rois[r, 1..4] ([R,5], column 0 = image),
+ * the ground truth gt_boxes[image, matched_gt[r], 0..3] ([N,G_max,5]) and the deltas columns 4 * label .. 4 * label + 3 of
+ * the bbox_pred row (reg_dim == 4 * num_classes); loss_out[1] = sum reg_weight * norm * L. grad_reg: those four columns
+ * and zeros in every other column < reg_dim of every row. loss_out[0] and grad_cls are bit-identical to mxdet_rcnn_loss.
+ * A roi whose image or match index lies outside gt_boxes regresses nothing. */
+int mxdet_rcnn_loss_iou(const void* cls_logits, const void* bbox_pred, int32_t dtype, int32_t ld_cls, int32_t ld_reg,
+                        const int32_t* labels, const float* rois, const int32_t* matched_gt, const float* gt_boxes,
+                        int32_t N, int32_t G_max, int64_t R, int32_t num_classes, int32_t reg_dim, int32_t kind,
+                        float std_x, float std_y, float std_w, float std_h, float reg_weight, float norm, float loss_scale,
+                        float* loss_out, void* grad_cls, void* grad_reg, void* workspace, size_t workspace_bytes,
+                        mxdet_stream_t stream);
+/* mxdet_retina_loss_level with the regression term replaced: for cls_labels > 0 the box is anchors[global anchor index]
+ * ([A_total,4] f32, 16-byte aligned), the ground truth gt_boxes[n, matched_gt[n, anchor], 0..3]; the term is
+ * reg_weight * L / max(1, *num_fg). Same grid, partial layout (mxdet_retina_loss_num_partials) and vector / scalar split
+ * as mxdet_retina_loss_level; partial[2i] and grad_cls are bit-identical to it. */
+int mxdet_retina_loss_level_iou(const uint16_t* cls, const uint16_t* reg, int32_t N, int32_t H, int32_t W, int32_t A,
+                                int32_t C, int32_t ld_cls, int32_t ld_reg, const int32_t* cls_labels, const float* anchors,
+                                const int32_t* matched_gt, const float* gt_boxes, int32_t G_max, int64_t A_total,
+                                int64_t level_offset, float alpha, float gamma, int32_t kind, float std_x, float std_y,
+                                float std_w, float std_h, float reg_weight, const int32_t* num_fg, float loss_scale,
+                                uint16_t* grad_cls, uint16_t* grad_reg, float* partial, mxdet_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * core/mask + mask_heads (README.md:18, :30) -- Mask R-CNN.
  * mask targets: for roi r (batch, box) with matched GT g = matched_gt[r] and class labels[r] > 0, resample the

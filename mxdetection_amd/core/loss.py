@@ -90,3 +90,60 @@ def retina_loss_level(cls, reg, A, C, cls_labels, bbox_targets, level_offset, al
                                       ptr(bbox_targets), cls_labels.shape[1], level_offset, alpha, gamma, sigma,
                                       ptr(num_fg), loss_scale, ptr(grad_cls), ptr(grad_reg), ptr(partial), stream_ptr()),
           "retina_loss_level")
+
+
+# ---- IoU / GIoU / DIoU losses on the decoded box (include/mxdet.h) ----
+IOU_LOSS_KINDS = _lib.IOU_LOSS_KINDS
+REG_LOSSES = ("smooth_l1",) + tuple(IOU_LOSS_KINDS)
+
+
+def check_reg_loss(reg_loss, reg_loss_weight):
+    """The regression-loss options of the box heads and the RetinaNet head, checked before anything is allocated."""
+    if reg_loss not in REG_LOSSES:
+        raise ValueError("reg_loss must be one of %s (got %r)" % (", ".join(REG_LOSSES), reg_loss))
+    w = reg_loss_weight
+    if isinstance(w, bool) or not isinstance(w, (int, float)) or not w > 0:
+        raise ValueError("reg_loss_weight must be a positive number (got %r)" % (w,))
+    if reg_loss == "smooth_l1" and w != 1:
+        raise ValueError("reg_loss_weight = %r needs an IoU-family reg_loss: smooth_l1 takes no weight" % (w,))
+
+
+def box_iou_loss(boxes, gt, deltas, kind="giou", stds=(1.0, 1.0, 1.0, 1.0), weight=None, grad_scale=1.0, loss=None,
+                 grad_deltas=None):
+    """Unfused IoU-family loss fwd+bwd: boxes / gt [n,4] f32, deltas [n,ld>=4] (f32|bf16; may be a column view of a wider
+    buffer). Returns (loss [n] f32, grad_deltas like deltas; only columns 0..3 are written)."""
+    lib = _lib.load()
+    n = boxes.shape[0]
+    if loss is None:
+        loss = torch.empty((n,), dtype=torch.float32, device=boxes.device)
+    ld = deltas.stride(0) if n > 1 else max(4, deltas.shape[1])
+    if grad_deltas is None:     # same leading dimension as deltas
+        grad_deltas = torch.zeros((n, ld), dtype=deltas.dtype, device=deltas.device)[:, :deltas.shape[1]]
+    check(lib.mxdet_box_iou_loss(ptr(boxes), ptr(gt), ptr(deltas), _DT[deltas.dtype], ld, ptr(weight), n,
+                                 IOU_LOSS_KINDS[kind], stds[0], stds[1], stds[2], stds[3], grad_scale, ptr(loss),
+                                 ptr(grad_deltas), stream_ptr()), "box_iou_loss")
+    return loss, grad_deltas
+
+
+def rcnn_loss_iou(cls_logits, bbox_pred, labels, rois, matched_gt, gt_boxes, num_classes, reg_dim, ld_cls, ld_reg, kind,
+                  stds, reg_weight, norm, loss_scale, grad_cls, grad_reg, loss_out, workspace):
+    """rcnn_loss with an IoU-family regression term on the decoded box: rois [R,5], matched_gt [R], gt_boxes [N,G,5]."""
+    lib = _lib.load()
+    R = labels.numel()
+    check(lib.mxdet_rcnn_loss_iou(ptr(cls_logits), ptr(bbox_pred), _DT[cls_logits.dtype], ld_cls, ld_reg, ptr(labels),
+                                  ptr(rois), ptr(matched_gt), ptr(gt_boxes), gt_boxes.shape[0], gt_boxes.shape[1], R,
+                                  num_classes, reg_dim, IOU_LOSS_KINDS[kind], stds[0], stds[1], stds[2], stds[3], reg_weight,
+                                  norm, loss_scale, ptr(loss_out), ptr(grad_cls), ptr(grad_reg), ptr(workspace),
+                                  workspace.numel(), stream_ptr()), "rcnn_loss_iou")
+
+
+def retina_loss_level_iou(cls, reg, A, C, cls_labels, anchors, matched_gt, gt_boxes, level_offset, alpha, gamma, kind, stds,
+                          reg_weight, num_fg, loss_scale, grad_cls, grad_reg, partial):
+    """retina_loss_level with an IoU-family box term: anchors [A_total,4], matched_gt [N,A_total], gt_boxes [N,G,5]."""
+    lib = _lib.load()
+    N, H, W, ld_cls = cls.shape
+    check(lib.mxdet_retina_loss_level_iou(ptr(cls), ptr(reg), N, H, W, A, C, ld_cls, reg.shape[3], ptr(cls_labels),
+                                          ptr(anchors), ptr(matched_gt), ptr(gt_boxes), gt_boxes.shape[1],
+                                          cls_labels.shape[1], level_offset, alpha, gamma, IOU_LOSS_KINDS[kind], stds[0],
+                                          stds[1], stds[2], stds[3], reg_weight, ptr(num_fg), loss_scale, ptr(grad_cls),
+                                          ptr(grad_reg), ptr(partial), stream_ptr()), "retina_loss_level_iou")

@@ -21,7 +21,11 @@ from ..utils.layers import ConvLayer, GroupNormLayer, cached_buf
 class BBoxHead:
     def __init__(self, in_features, arena, ws, device, gen, num_classes=81, fc_dim=1024, rois_per_image=512,
                  fg_fraction=0.25, fg_thresh=0.5, bg_hi=0.5, bg_lo=0.0, stds=(0.1, 0.1, 0.2, 0.2), sigma=1.0,
-                 seed=99):
+                 seed=99, reg_loss="smooth_l1", reg_loss_weight=1.0):
+        """reg_loss: 'smooth_l1' on the encoded deltas (core.loss.rcnn_loss), or 'iou' / 'giou' / 'diou' on the decoded
+        box times reg_loss_weight (core.loss.rcnn_loss_iou; the head still predicts deltas, inference is the same)."""
+        L_.check_reg_loss(reg_loss, reg_loss_weight)
+        self.reg_loss, self.reg_loss_weight = reg_loss, float(reg_loss_weight)
         kw = dict(arena=arena, ws=ws, device=device, gen=gen)
         self.nc = num_classes
         self.reg_dim = 4 * num_classes
@@ -63,10 +67,12 @@ class BBoxHead:
         self.loss_ws = L_.loss_workspace(R, self.device)
 
     def sample(self, rois, num_rois, gt_boxes, step, image_offset, step_dev=None):
-        """proposal-target: returns rois [N*R,5] and keeps labels / targets / weights for the loss."""
+        """proposal-target: returns rois [N*R,5] and keeps labels / targets / weights (and the ground truth, which the
+        IoU-family losses read on the device) for the loss."""
         out = B_.sample_rois(rois, num_rois, gt_boxes, self.R, self.fg_fraction, self.fg_thresh, self.bg_hi, self.bg_lo,
                              self.nc, False, (0.0, 0.0, 0.0, 0.0), self.stds, self.seed, step, image_offset, step_dev)
         self.rois, self.labels, self.tgt, self.wgt, self.matched, self.num_fg = out
+        self.gt_boxes = gt_boxes
         return self.rois.view(-1, 5)
 
     def forward(self, pooled):
@@ -91,8 +97,13 @@ class BBoxHead:
         o2 = self.o.view(R, self.ld)
         self.go = self._buf("go", (R, 1, 1, self.ld), zero=True)   # padding columns stay zero forever
         g2 = self.go.view(R, self.ld)
-        L_.rcnn_loss(o2, o2[:, self.nc:], self.labels, self.tgt, self.wgt, self.nc, self.reg_dim, self.ld, self.ld,
-                     self.sigma, 1.0 / R, loss_scale, g2, g2[:, self.nc:], self.loss, self.loss_ws)
+        if self.reg_loss == "smooth_l1":
+            L_.rcnn_loss(o2, o2[:, self.nc:], self.labels, self.tgt, self.wgt, self.nc, self.reg_dim, self.ld, self.ld,
+                         self.sigma, 1.0 / R, loss_scale, g2, g2[:, self.nc:], self.loss, self.loss_ws)
+        else:
+            L_.rcnn_loss_iou(o2, o2[:, self.nc:], self.labels, self.rois, self.matched, self.gt_boxes, self.nc, self.reg_dim,
+                             self.ld, self.ld, self.reg_loss, self.stds, self.reg_loss_weight, 1.0 / R, loss_scale, g2,
+                             g2[:, self.nc:], self.loss, self.loss_ws)
         return self.loss
 
     def backward(self):

@@ -6,19 +6,21 @@ def build_detector(cfg, device="cuda"):
     from . import FasterRCNN, RetinaNet
     net, tr = cfg.network, cfg.TRAIN
     dcn = dict(dcn_stages=tuple(net.dcn_stages), dcn_modulated=bool(net.dcn_modulated), dcn_groups=int(net.dcn_groups))
+    reg = dict(reg_loss=str(net.reg_loss), reg_loss_weight=net.reg_loss_weight)
     if net.type in ("faster_rcnn", "mask_rcnn"):
         dpool = dict(roi_pool=str(net.roi_pool), dpool_trans_std=float(net.dpool_trans_std),
                      dpool_sample_per_part=int(net.dpool_sample_per_part), dpool_offset_fcs=int(net.dpool_offset_fcs))
         heads = dict(bbox_head=str(net.bbox_head), head_norm=str(net.head_norm), gn_groups=net.gn_groups)
         model = FasterRCNN(device, depth=net.backbone_depth, num_classes=net.num_classes, seed=net.seed,
                            rois_per_image=tr.batch_rois, pre_nms_top_n=tr.rpn_pre_nms_top_n,
-                           post_nms_top_n=tr.rpn_post_nms_top_n, with_mask=(net.type == "mask_rcnn"), **dcn, **dpool, **heads)
+                           post_nms_top_n=tr.rpn_post_nms_top_n, with_mask=(net.type == "mask_rcnn"), **dcn, **dpool, **heads,
+                           **reg)
     elif net.type == "retinanet":
         if net.roi_pool != "roi_align":
             raise ValueError("network.roi_pool = %r: retinanet has no RoI branch" % (net.roi_pool,))
         if net.bbox_head != "2fc" or net.head_norm != "none":
             raise ValueError("network.bbox_head / network.head_norm: retinanet has no RoI heads")
-        model = RetinaNet(device, depth=net.backbone_depth, num_classes=net.num_classes - 1, seed=net.seed, **dcn)
+        model = RetinaNet(device, depth=net.backbone_depth, num_classes=net.num_classes - 1, seed=net.seed, **dcn, **reg)
     else:
         raise ValueError("unknown network.type %r" % (net.type,))
     if net.pretrained:

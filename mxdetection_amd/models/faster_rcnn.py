@@ -9,6 +9,7 @@ import os
 
 import torch
 
+from ..core.loss import check_reg_loss
 from .backbones import ResNet
 from .bbox_heads import BBoxHead, ConvFCBBoxHead
 from .mask_heads import FCNMaskHead
@@ -38,15 +39,18 @@ class FasterRCNN(DetectorBase):
     def __init__(self, device="cuda", depth=50, num_classes=81, seed=7, rpn_seed=99, rois_per_image=512,
                  pre_nms_top_n=2000, post_nms_top_n=2000, with_mask=False, dcn_stages=(), dcn_modulated=True,
                  dcn_groups=1, roi_pool="roi_align", dpool_trans_std=0.1, dpool_sample_per_part=4, dpool_offset_fcs=3,
-                 bbox_head="2fc", head_norm="none", gn_groups=32):
+                 bbox_head="2fc", head_norm="none", gn_groups=32, reg_loss="smooth_l1", reg_loss_weight=1.0):
         """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
         roi_pool: the box branch's RoI pooling -- 'roi_align', or deformable RoI pooling with its offset head, 'dpool'
         (v1) / 'mdpool' (v2, modulated) (roi_extractors.DeformRoIExtractor, options dpool_*). The mask branch keeps its
         14x14 RoIAlign.
         bbox_head: '2fc' (two FCs) or '4conv1fc' (four 3x3 convs + one FC). head_norm: 'none' or 'gn' -- GroupNorm with
         gn_groups groups after every conv of the 4conv1fc box head and of the mask head (bbox_heads.ConvFCBBoxHead,
-        mask_heads.FCNMaskHead)."""
+        mask_heads.FCNMaskHead).
+        reg_loss / reg_loss_weight: the box head's regression loss -- 'smooth_l1' on the encoded deltas, or 'iou' / 'giou' /
+        'diou' on the decoded box times reg_loss_weight (bbox_heads.BBoxHead). The RPN keeps smooth-L1."""
         check_head_options(bbox_head, head_norm, gn_groups, with_mask)
+        check_reg_loss(reg_loss, reg_loss_weight)
         if roi_pool not in ("roi_align", "dpool", "mdpool"):
             raise ValueError("roi_pool must be 'roi_align', 'dpool' or 'mdpool' (got %r)" % (roi_pool,))
         self.roi_pool = roi_pool
@@ -68,10 +72,12 @@ class FasterRCNN(DetectorBase):
         self.mark_mask = self.arena.size
         if bbox_head == "4conv1fc":
             self.bbox_head = ConvFCBBoxHead(7 * 7 * 256, self.arena, self.ws, device, gen, norm=head_norm, gn_groups=gn_groups,
-                                            num_classes=num_classes, rois_per_image=rois_per_image, seed=rpn_seed)
+                                            num_classes=num_classes, rois_per_image=rois_per_image, seed=rpn_seed,
+                                            reg_loss=reg_loss, reg_loss_weight=reg_loss_weight)
         else:
             self.bbox_head = BBoxHead(7 * 7 * 256, self.arena, self.ws, device, gen, num_classes=num_classes,
-                                      rois_per_image=rois_per_image, seed=rpn_seed)
+                                      rois_per_image=rois_per_image, seed=rpn_seed, reg_loss=reg_loss,
+                                      reg_loss_weight=reg_loss_weight)
         self.dpool = None
         if roi_pool != "roi_align":
             # the offset head belongs to the head bucket: its backward runs in the slot of the RoI extractor's

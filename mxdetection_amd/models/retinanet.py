@@ -2,6 +2,7 @@
 on hand-written HIP kernels, same arena / graph / data-parallel machinery as Faster R-CNN."""
 import torch
 
+from ..core.loss import check_reg_loss
 from .backbones import ResNet
 from .necks.fpn import RetinaFPN
 from .rpn_heads.retina_head import RetinaHead
@@ -9,12 +10,17 @@ from .utils.detector import DetectorBase
 
 
 class RetinaNet(DetectorBase):
-    def __init__(self, device="cuda", depth=101, num_classes=80, seed=7, dcn_stages=(), dcn_modulated=True, dcn_groups=1):
-        """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet)."""
+    def __init__(self, device="cuda", depth=101, num_classes=80, seed=7, dcn_stages=(), dcn_modulated=True, dcn_groups=1,
+                 reg_loss="smooth_l1", reg_loss_weight=1.0):
+        """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
+        reg_loss / reg_loss_weight: the head's box loss -- 'smooth_l1', or 'iou' / 'giou' / 'diou' on the decoded box times
+        reg_loss_weight (rpn_heads.RetinaHead)."""
+        check_reg_loss(reg_loss, reg_loss_weight)
         gen = torch.Generator().manual_seed(seed)
         self._init_base(device)
         self.strides = [8, 16, 32, 64, 128]
-        self.head = RetinaHead(256, self.strides, self.arena, self.ws, device, gen, num_classes=num_classes)
+        self.head = RetinaHead(256, self.strides, self.arena, self.ws, device, gen, num_classes=num_classes,
+                               reg_loss=reg_loss, reg_loss_weight=reg_loss_weight)
         self.mark_head = self.arena.size
         self.neck = RetinaFPN([512, 1024, 2048], 256, self.arena, self.ws, device, gen)
         self.mark_fpn = self.arena.size

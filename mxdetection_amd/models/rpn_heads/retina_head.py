@@ -18,7 +18,11 @@ from ..utils.layers import ConvLayer, cached_buf
 class RetinaHead:
     def __init__(self, channels, strides, arena, ws, device, gen, num_classes=80, num_convs=4, ratios=(0.5, 1.0, 2.0),
                  octave_scales=(1.0, 2.0 ** (1.0 / 3.0), 2.0 ** (2.0 / 3.0)), anchor_scale=4.0, fg_thresh=0.5,
-                 bg_thresh=0.4, alpha=0.25, gamma=2.0, sigma=3.0, prior=0.01):
+                 bg_thresh=0.4, alpha=0.25, gamma=2.0, sigma=3.0, prior=0.01, reg_loss="smooth_l1", reg_loss_weight=1.0):
+        """reg_loss: 'smooth_l1' on the encoded deltas (core.loss.retina_loss_level), or 'iou' / 'giou' / 'diou' on the
+        decoded box times reg_loss_weight (core.loss.retina_loss_level_iou; stds 1, as the inference decode)."""
+        L_.check_reg_loss(reg_loss, reg_loss_weight)
+        self.reg_loss, self.reg_loss_weight = reg_loss, float(reg_loss_weight)
         kw = dict(arena=arena, ws=ws, device=device, gen=gen)
         self.A, self.Cn = len(ratios) * len(octave_scales), num_classes
         self.ld_cls = (self.A * num_classes + 63) // 64 * 64
@@ -98,13 +102,19 @@ class RetinaHead:
         labels, matched, targets, _ = A_.assign_anchor(self.anchors, gt_boxes, im_info, self.fg_thresh, self.bg_thresh,
                                                        1.0e6, 0, 0.5, 0, 0, 0, self.at_ws, self.at_out)
         L_.anchor_class_labels(labels, matched, gt_boxes, self.cls_labels, self.num_fg)
+        self.matched = matched
         self.gco, self.gbo = [], []
         off = 0
         for l in range(len(self.co)):
             gc = self._buf("gco%d" % l, self.co[l].shape, zero=True)     # padding channels stay zero
             gb = self._buf("gbo%d" % l, self.bo[l].shape, zero=True)
-            L_.retina_loss_level(self.co[l], self.bo[l], self.A, self.Cn, self.cls_labels, targets, self.level_offsets[l],
-                                 self.alpha, self.gamma, self.sigma, self.num_fg, loss_scale, gc, gb, self.partial[2 * off:])
+            if self.reg_loss == "smooth_l1":
+                L_.retina_loss_level(self.co[l], self.bo[l], self.A, self.Cn, self.cls_labels, targets, self.level_offsets[l],
+                                     self.alpha, self.gamma, self.sigma, self.num_fg, loss_scale, gc, gb, self.partial[2 * off:])
+            else:
+                L_.retina_loss_level_iou(self.co[l], self.bo[l], self.A, self.Cn, self.cls_labels, self.anchors, matched, gt_boxes,
+                                         self.level_offsets[l], self.alpha, self.gamma, self.reg_loss, (1.0, 1.0, 1.0, 1.0),
+                                         self.reg_loss_weight, self.num_fg, loss_scale, gc, gb, self.partial[2 * off:])
             off += self.nparts[l]
             self.gco.append(gc)
             self.gbo.append(gb)

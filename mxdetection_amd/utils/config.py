@@ -47,6 +47,8 @@ DEFAULTS = {
         "bbox_head": "2fc",               # box head trunk: 2fc | 4conv1fc (four 3x3 convs + one FC)
         "head_norm": "none",              # none | gn: GroupNorm after every conv of the 4conv1fc box head and of the mask head
         "gn_groups": 32,                  # GroupNorm groups (256 / gn_groups must be a multiple of 8)
+        "reg_loss": "smooth_l1",          # box regression loss of the box head / the RetinaNet head: smooth_l1 | iou | giou | diou
+        "reg_loss_weight": 1.0,           # weight of an IoU-family reg_loss (on the decoded box); smooth_l1 takes none. The RPN keeps smooth-L1
         "dpool_offset_fcs": 3,            # FCs of the offset head (1: Deformable-ConvNets' FPN head, 3: DCN v2 / mmdetection)
     },
     "dataset": {
