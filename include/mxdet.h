@@ -87,6 +87,40 @@ int mxdet_detection_postprocess(const void* cls_logits, const void* bbox_pred, i
                                 float* dets, int32_t* num_dets, void* workspace, size_t workspace_bytes,
                                 mxdet_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * ops (README.md:24) + core/evaluation (README.md:20) -- Soft-NMS (Bodla et al. 2017), the test-time alternative to
+ * greedy NMS (TEST.SOFT_NMS / nms.type=soft_nms of the toolboxes of this lineage). DESIGN.md 5g.
+ * One list of candidates (box, score, id), ids unique within the list:
+ *   a candidate is live while score > min_score (strict, as score_thresh above);
+ *   repeat until max_keep selections are made or nothing is live:
+ *     select the live candidate with the largest (score, then lower id); output it with its CURRENT score; remove it;
+ *     for every other live candidate: o = mxdet_iou(selected, candidate); score = score * w, where
+ *       method 0 (hard):     w = o > nms_thresh ? 0 : 1
+ *       method 1 (linear):   w = o > nms_thresh ? 1 - o : 1
+ *       method 2 (Gaussian): t = o * o; t = t / sigma; w = mxdet_expf(-t)
+ *   each step one fp32 operation in this order, no FMA contraction. mxdet_expf(-0.0f) == 1.0f exactly, so a box that
+ *   does not overlap the selected one keeps its score bits under every method.
+ * The selected (score, id) keys strictly decrease along a list's output (scores only decay; intended for
+ * min_score >= 0 -- with a negative min_score a candidate suppressed by method 0 stays live at score 0).
+ *
+ * mxdet_soft_nms_batched: B independent lists, boxes [B,n_max,4], scores [B,n_max], the first counts[b] entries of list
+ * b valid, in any order; id = position in the list; n_max <= 4096. keep_idx [B,max_keep] receives the selected
+ * positions in selection order (padding -1), keep_scores [B,max_keep] their scores at selection (padding 0),
+ * num_keep [B] their number. method outside 0..2, or sigma <= 0 with method 2: MXDET_EINVAL. */
+int mxdet_soft_nms_batched(const float* boxes, const float* scores, const int32_t* counts, int32_t B, int32_t n_max,
+                           int32_t method, float nms_thresh, float sigma, float min_score, int32_t max_keep,
+                           int32_t* keep_idx, float* keep_scores, int32_t* num_keep, mxdet_stream_t stream);
+/* mxdet_detection_postprocess with its per-class greedy NMS replaced by Soft-NMS: per image and foreground class the
+ * candidates with score > score_thresh form one list (id = roi index, min_score = score_thresh, max_keep =
+ * max_per_image -- a later selection of a class cannot reach the image's best max_per_image); then the max_per_image best
+ * over all classes by (score at selection desc, roi asc, class asc). dets carries the score at selection. Same
+ * workspace as mxdet_detection_postprocess. */
+int mxdet_detection_postprocess_soft(const void* cls_logits, const void* bbox_pred, int32_t dtype, int32_t ld_cls,
+                                     int32_t ld_reg, const float* rois, const int32_t* num_rois, const float* im_info,
+                                     int32_t N, int32_t rois_per_image, int32_t num_classes, const float* means,
+                                     const float* stds, float score_thresh, float nms_thresh, int32_t max_per_image,
+                                     float* dets, int32_t* num_dets, void* workspace, size_t workspace_bytes,
+                                     int32_t method, float sigma, mxdet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * rpn_heads + ops (README.md:28, :24) -- pyramid proposal generation.
@@ -611,6 +645,12 @@ size_t mxdet_retina_detect_workspace_bytes(const mxdet_pyramid_t* p, int32_t N, 
 int mxdet_retina_detect(const mxdet_pyramid_t* p, int32_t N, const float* im_info, int32_t pre_nms_top_n,
                         float score_thresh, float nms_thresh, int32_t max_per_image, float* dets, int32_t* num_dets,
                         void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
+/* mxdet_retina_detect with Soft-NMS per class (semantics at mxdet_soft_nms_batched; id = candidate rank in the merged
+ * list, min_score = score_thresh, max_keep = max_per_image). Same workspace as mxdet_retina_detect. */
+int mxdet_retina_detect_soft(const mxdet_pyramid_t* p, int32_t N, const float* im_info, int32_t pre_nms_top_n,
+                             float score_thresh, float nms_thresh, int32_t max_per_image, float* dets,
+                             int32_t* num_dets, void* workspace, size_t workspace_bytes, int32_t method, float sigma,
+                             mxdet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * process_data (README.md:23) -- the step in front of the path.

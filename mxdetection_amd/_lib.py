@@ -97,17 +97,24 @@ SIGNATURES = {
     "mxdet_generate_anchors": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mxdet_nms_batched_workspace_bytes": (c_sz, [c_i32, c_i32]),
     "mxdet_nms_batched": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_soft_nms_batched": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp,
+                                       c_vp]),
     "mxdet_pixel_shuffle2_inv_relu": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mxdet_mask_paste_workspace_bytes": (c_sz, [c_i64, c_i32]),
     "mxdet_mask_paste": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_sz, c_vp]),
     "mxdet_retina_detect_workspace_bytes": (c_sz, [c_vp, c_i32, c_i32]),
     "mxdet_retina_detect": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_retina_detect_soft": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp, c_sz, c_i32, c_f32,
+                                         c_vp]),
     "mxdet_debug_preprocess_direct": (c_i32, [c_i32]),
     "mxdet_image_preprocess": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "mxdet_polygon_masks": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mxdet_detection_postprocess_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "mxdet_detection_postprocess": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                                             P(c_f32), P(c_f32), c_f32, c_f32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_detection_postprocess_soft": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
+                                                 P(c_f32), P(c_f32), c_f32, c_f32, c_i32, c_vp, c_vp, c_vp, c_sz, c_i32,
+                                                 c_f32, c_vp]),
     "mxdet_proposal_workspace_bytes": (c_sz, [P(PyramidT), c_i32, c_i32]),
     "mxdet_proposal": (c_i32, [P(PyramidT), c_i32, c_vp, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp,
                                c_vp, c_sz, c_vp]),

@@ -2,7 +2,8 @@
 
 SURVEY.md section 8f rank 3 ("the step immediately after the path"). The MXNet lineage runs `im_detect` ->
 per-class score threshold -> nms -> max_per_image in numpy on the host (README.md:37,41-44); here it is one C-ABI call
-(`mxdet_detection_postprocess`, csrc/postprocess.hip) that reuses the training path's batched NMS.
+(`mxdet_detection_postprocess`, csrc/postprocess.hip) that reuses the training path's batched NMS. `nms_method="linear"` /
+`"gaussian"` switch the per-class stage to Soft-NMS (`mxdet_*_soft`, csrc/soft_nms.hip).
 """
 import ctypes as C
 
@@ -10,6 +11,7 @@ import torch
 
 from .. import _lib
 from .._lib import check, ptr, stream_ptr
+from ..ops.nms import soft_nms_method
 
 _DT = {torch.float32: 0, torch.bfloat16: 1}
 
@@ -19,11 +21,14 @@ class DetectionPostprocess:
 
     cls_logits [N*R, >=C] and bbox_pred [N*R, >=4C] may be column views of one fused head output (leading dimensions are
     taken from the strides). Returns (dets [N, max_per_image, 6] f32 = x1,y1,x2,y2,score,class; num_dets [N] i32).
+    nms_method "hard" is greedy NMS (the bitmask kernels); "linear" / "gaussian" are Soft-NMS with the decayed score in
+    dets (soft_sigma: the Gaussian's sigma).
     """
 
     def __init__(self, num_classes=81, score_thresh=0.05, nms_thresh=0.5, max_per_image=100,
-                 means=(0.0, 0.0, 0.0, 0.0), stds=(0.1, 0.1, 0.2, 0.2)):
+                 means=(0.0, 0.0, 0.0, 0.0), stds=(0.1, 0.1, 0.2, 0.2), nms_method="hard", soft_sigma=0.5):
         self.C, self.score_thresh, self.nms_thresh, self.max_det = num_classes, score_thresh, nms_thresh, max_per_image
+        self.method, self.soft_sigma = soft_nms_method(nms_method), soft_sigma
         self.means = (C.c_float * 4)(*means)
         self.stds = (C.c_float * 4)(*stds)
         self._ws = None
@@ -41,11 +46,14 @@ class DetectionPostprocess:
             self._out = (torch.empty((N, self.max_det, 6), dtype=torch.float32, device=dev),
                          torch.empty((N,), dtype=torch.int32, device=dev))
         dets, num = self._out
-        check(lib.mxdet_detection_postprocess(ptr(cls_logits), ptr(bbox_pred), _DT[cls_logits.dtype],
-                                              cls_logits.stride(0), bbox_pred.stride(0), ptr(rois), ptr(num_rois),
-                                              ptr(im_info), N, R, self.C, self.means, self.stds, self.score_thresh,
-                                              self.nms_thresh, self.max_det, ptr(dets), ptr(num), ptr(self._ws),
-                                              self._ws.numel(), stream_ptr()), "detection_postprocess")
+        args = (ptr(cls_logits), ptr(bbox_pred), _DT[cls_logits.dtype], cls_logits.stride(0), bbox_pred.stride(0), ptr(rois),
+                ptr(num_rois), ptr(im_info), N, R, self.C, self.means, self.stds, self.score_thresh, self.nms_thresh,
+                self.max_det, ptr(dets), ptr(num), ptr(self._ws), self._ws.numel())
+        if self.method == 0:
+            check(lib.mxdet_detection_postprocess(*args, stream_ptr()), "detection_postprocess")
+        else:
+            check(lib.mxdet_detection_postprocess_soft(*args, self.method, self.soft_sigma, stream_ptr()),
+                  "detection_postprocess_soft")
         return dets, num
 
 
@@ -285,11 +293,12 @@ def detections_to_coco(dets, num_dets, image_ids, scales, class_to_cat=None):
 class RetinaDetect:
     """One-stage test-time detection on the device (mxdet_retina_detect): per-level top-k over (anchor, class) logits,
     decode, merge, sigmoid, per-class NMS, max_per_image. cls[l] bf16/f32 [N,H,W,>=A*C] (channel a*C + c), reg[l]
-    [N,H,W,>=4A] (channel a*4 + k), base[l] device f32 [A,4]."""
+    [N,H,W,>=4A] (channel a*4 + k), base[l] device f32 [A,4]. nms_method / soft_sigma as in DetectionPostprocess."""
 
     def __init__(self, num_classes, strides, base_anchors, pre_nms_top_n=1000, score_thresh=0.05, nms_thresh=0.5,
-                 max_per_image=100):
+                 max_per_image=100, nms_method="hard", soft_sigma=0.5):
         self.C, self.strides, self.base = num_classes, list(strides), base_anchors
+        self.method, self.soft_sigma = soft_nms_method(nms_method), soft_sigma
         self.pre_n, self.score_thresh, self.nms_thresh, self.max_det = pre_nms_top_n, score_thresh, nms_thresh, max_per_image
         self._ws = None
 
@@ -312,6 +321,10 @@ class RetinaDetect:
             self._ws = torch.empty((need,), dtype=torch.uint8, device=cls[0].device)
         dets = torch.empty((N, self.max_det, 6), dtype=torch.float32, device=cls[0].device)
         num = torch.empty((N,), dtype=torch.int32, device=cls[0].device)
-        check(lib.mxdet_retina_detect(C.byref(d), N, ptr(im_info), self.pre_n, self.score_thresh, self.nms_thresh, self.max_det,
-                                      ptr(dets), ptr(num), ptr(self._ws), self._ws.numel(), stream_ptr()), "retina_detect")
+        args = (C.byref(d), N, ptr(im_info), self.pre_n, self.score_thresh, self.nms_thresh, self.max_det, ptr(dets), ptr(num),
+                ptr(self._ws), self._ws.numel())
+        if self.method == 0:
+            check(lib.mxdet_retina_detect(*args, stream_ptr()), "retina_detect")
+        else:
+            check(lib.mxdet_retina_detect_soft(*args, self.method, self.soft_sigma, stream_ptr()), "retina_detect_soft")
         return dets, num

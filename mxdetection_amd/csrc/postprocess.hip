@@ -10,9 +10,13 @@
 //   (3) mxdet_nms_batched    : the bitmask NMS of boxes.hip over the N*(C-1) lists
 //   (4) det_merge_kernel     : per image, rank-merge of the per-class kept lists (binary searches in LDS) and cut
 //                              to max_per_image by (score desc, roi index asc, class asc)
+// The *_soft entries replace (3) by the Soft-NMS list kernel of soft_nms.hip: it leaves, per list, the
+// selected positions in keep_idx and their keys with the DECAYED scores in a corner of the bitmask workspace; (4) then
+// merges on those keys. A list's selections come out in descending key order, which is what the rank-merge needs.
 // Integer-exact (kept indices, classes) and bit-exact (scores, boxes) against oracle/mxdet_oracle.c.
 #include "common.h"
 #include "select.h"
+#include "soft_nms.h"
 
 namespace mxdet {
 
@@ -96,9 +100,12 @@ det_class_sort_kernel(const float* __restrict__ scores, const float4* __restrict
   if (threadIdx.x == 0) counts[b] = cnt;
 }
 
-// per image: merge the kept lists of all classes, keep the max_det best by (score desc, roi asc, class asc)
+// per image: merge the kept lists of all classes, keep the max_det best by (score desc, roi asc, class asc).
+// dkeys == null: entry j of list b carries the key skeys[b][keep_idx[b][j]] (hard NMS: the score it was sorted by);
+// else its key is dkeys[b*Rpi + j] (Soft-NMS: the score at selection).
 __global__ void __launch_bounds__(1024)
 det_merge_kernel(int C, int Rpi, int cap, int max_det, const unsigned long long* __restrict__ skeys,
+                 const unsigned long long* __restrict__ dkeys,
                  const float4* __restrict__ sboxes, const int32_t* __restrict__ keep_idx,
                  const int32_t* __restrict__ num_keep, float* __restrict__ dets, int32_t* __restrict__ num_dets) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -113,7 +120,7 @@ det_merge_kernel(int C, int Rpi, int cap, int max_det, const unsigned long long*
   for (int l = 0; l < L; ++l) {
     const int b = n * L + l;
     for (int j = threadIdx.x; j < nk[l]; j += blockDim.x) {
-      unsigned long long k = skeys[(size_t)b * Rpi + keep_idx[(size_t)b * Rpi + j]];
+      unsigned long long k = dkeys ? dkeys[(size_t)b * Rpi + j] : skeys[(size_t)b * Rpi + keep_idx[(size_t)b * Rpi + j]];
       unsigned i = 0xffffffffu - (unsigned)(k & 0xffffffffull);
       // same score key, low word orders by (roi index, class): unique over the whole image
       lk[(size_t)l * cap + j] = (k & 0xffffffff00000000ull) | (unsigned long long)(0xffffffffu - (i * (unsigned)C + (unsigned)(l + 1)));
@@ -241,14 +248,13 @@ extern "C" size_t mxdet_detection_postprocess_workspace_bytes(int32_t N, int32_t
   return det_carve(nullptr, N, rois_per_image, num_classes).total;
 }
 
-extern "C" int mxdet_detection_postprocess(const void* cls_logits, const void* bbox_pred, int32_t dtype,
-                                           int32_t ld_cls, int32_t ld_reg, const float* rois,
-                                           const int32_t* num_rois, const float* im_info, int32_t N,
-                                           int32_t rois_per_image, int32_t num_classes, const float* means,
-                                           const float* stds, float score_thresh, float nms_thresh,
-                                           int32_t max_per_image, float* dets, int32_t* num_dets,
-                                           void* workspace, size_t workspace_bytes, mxdet_stream_t stream) {
-  clear_error();
+// method < 0: greedy hard NMS on the bitmask kernels; 0..2: the Soft-NMS list kernel
+static int detection_postprocess_impl(const void* cls_logits, const void* bbox_pred, int32_t dtype, int32_t ld_cls,
+                                      int32_t ld_reg, const float* rois, const int32_t* num_rois, const float* im_info,
+                                      int32_t N, int32_t rois_per_image, int32_t num_classes, const float* means,
+                                      const float* stds, float score_thresh, float nms_thresh, int32_t max_per_image,
+                                      float* dets, int32_t* num_dets, void* workspace, size_t workspace_bytes,
+                                      int method, float sigma, mxdet_stream_t stream) {
   MXDET_REQUIRE(N > 0 && rois_per_image > 0 && num_classes > 1, MXDET_ESHAPE, "detection_postprocess: bad sizes");
   MXDET_REQUIRE(rois_per_image <= kDetMaxRois, MXDET_ESHAPE, "detection_postprocess: rois_per_image %d > %d",
                 rois_per_image, kDetMaxRois);
@@ -277,13 +283,50 @@ extern "C" int mxdet_detection_postprocess(const void* cls_logits, const void* b
                      w.counts);
   int rc = check_launch("detection_postprocess(score/sort)");
   if (rc) return rc;
-  rc = mxdet_nms_batched((const float*)w.sboxes, w.counts, nullptr, B, Rpi, nms_thresh, max_per_image, w.keep_idx,
-                         w.num_keep, w.nms_ws, w.nms_bytes, stream);
-  if (rc) return rc;
+  // Soft-NMS keeps the decayed keys of its selections ([B][Rpi], laid out like keep_idx) at the front of the bitmask
+  // workspace, which is at least 32 times that size
+  unsigned long long* dkeys = method < 0 ? nullptr : (unsigned long long*)w.nms_ws;
+  if (method < 0) {
+    rc = mxdet_nms_batched((const float*)w.sboxes, w.counts, nullptr, B, Rpi, nms_thresh, max_per_image, w.keep_idx,
+                           w.num_keep, w.nms_ws, w.nms_bytes, stream);
+    if (rc) return rc;
+  } else {
+    soft_nms_launch((const float4*)w.sboxes, nullptr, (const unsigned long long*)w.skeys, w.counts, B, Rpi, method,
+                    nms_thresh, sigma, score_thresh, max_per_image, Rpi, 0, w.keep_idx, nullptr, dkeys, w.num_keep, s);
+  }
   hipLaunchKernelGGL(det_merge_kernel, dim3(N), dim3(1024), merge_lds, s, C, Rpi, max_per_image, max_per_image,
-                     (const unsigned long long*)w.skeys, (const float4*)w.sboxes, (const int32_t*)w.keep_idx,
-                     (const int32_t*)w.num_keep, dets, num_dets);
+                     (const unsigned long long*)w.skeys, (const unsigned long long*)dkeys, (const float4*)w.sboxes,
+                     (const int32_t*)w.keep_idx, (const int32_t*)w.num_keep, dets, num_dets);
   return check_launch("detection_postprocess(merge)");
+}
+
+extern "C" int mxdet_detection_postprocess(const void* cls_logits, const void* bbox_pred, int32_t dtype,
+                                           int32_t ld_cls, int32_t ld_reg, const float* rois,
+                                           const int32_t* num_rois, const float* im_info, int32_t N,
+                                           int32_t rois_per_image, int32_t num_classes, const float* means,
+                                           const float* stds, float score_thresh, float nms_thresh,
+                                           int32_t max_per_image, float* dets, int32_t* num_dets,
+                                           void* workspace, size_t workspace_bytes, mxdet_stream_t stream) {
+  clear_error();
+  return detection_postprocess_impl(cls_logits, bbox_pred, dtype, ld_cls, ld_reg, rois, num_rois, im_info, N,
+                                    rois_per_image, num_classes, means, stds, score_thresh, nms_thresh, max_per_image,
+                                    dets, num_dets, workspace, workspace_bytes, -1, 0.0f, stream);
+}
+
+extern "C" int mxdet_detection_postprocess_soft(const void* cls_logits, const void* bbox_pred, int32_t dtype,
+                                                int32_t ld_cls, int32_t ld_reg, const float* rois,
+                                                const int32_t* num_rois, const float* im_info, int32_t N,
+                                                int32_t rois_per_image, int32_t num_classes, const float* means,
+                                                const float* stds, float score_thresh, float nms_thresh,
+                                                int32_t max_per_image, float* dets, int32_t* num_dets,
+                                                void* workspace, size_t workspace_bytes, int32_t method, float sigma,
+                                                mxdet_stream_t stream) {
+  clear_error();
+  MXDET_REQUIRE(method >= 0 && method <= 2, MXDET_EINVAL, "detection_postprocess_soft: method %d not in 0..2", method);
+  MXDET_REQUIRE(method != 2 || sigma > 0.0f, MXDET_EINVAL, "detection_postprocess_soft: sigma must be positive for method 2");
+  return detection_postprocess_impl(cls_logits, bbox_pred, dtype, ld_cls, ld_reg, rois, num_rois, im_info, N,
+                                    rois_per_image, num_classes, means, stds, score_thresh, nms_thresh, max_per_image,
+                                    dets, num_dets, workspace, workspace_bytes, method, sigma, stream);
 }
 
 static int retina_candidates_cap(const mxdet_pyramid_t* p, int pre_n) {
@@ -296,10 +339,10 @@ extern "C" size_t mxdet_retina_detect_workspace_bytes(const mxdet_pyramid_t* p, 
   return retina_carve(nullptr, p, N, pre_nms_top_n, retina_candidates_cap(p, pre_nms_top_n), p->classes).total;
 }
 
-extern "C" int mxdet_retina_detect(const mxdet_pyramid_t* p, int32_t N, const float* im_info, int32_t pre_nms_top_n,
-                                   float score_thresh, float nms_thresh, int32_t max_per_image, float* dets,
-                                   int32_t* num_dets, void* workspace, size_t workspace_bytes, mxdet_stream_t stream) {
-  clear_error();
+static int retina_detect_impl(const mxdet_pyramid_t* p, int32_t N, const float* im_info, int32_t pre_nms_top_n,
+                              float score_thresh, float nms_thresh, int32_t max_per_image, float* dets,
+                              int32_t* num_dets, void* workspace, size_t workspace_bytes, int method, float sigma,
+                              mxdet_stream_t stream) {
   MXDET_REQUIRE(p && im_info && dets && num_dets, MXDET_EINVAL, "retina_detect: null pointer");
   MXDET_REQUIRE(N > 0 && p->num_levels > 0 && p->classes >= 1 && pre_nms_top_n > 0, MXDET_ESHAPE, "retina_detect: bad sizes");
   const int C = p->classes, R = retina_candidates_cap(p, pre_nms_top_n), B = N * C;
@@ -322,11 +365,36 @@ extern "C" int mxdet_retina_detect(const mxdet_pyramid_t* p, int32_t N, const fl
                      (const int32_t*)w.cls, (const int32_t*)w.num, R, C + 1, Kpad, score_thresh, w.sboxes, w.skeys, w.counts);
   rc = check_launch("retina_detect(candidates/sort)");
   if (rc) return rc;
-  rc = mxdet_nms_batched((const float*)w.sboxes, w.counts, nullptr, B, R, nms_thresh, max_per_image, w.keep_idx,
-                         w.num_keep, w.nms_ws, w.nms_bytes, stream);
-  if (rc) return rc;
+  unsigned long long* dkeys = method < 0 ? nullptr : (unsigned long long*)w.nms_ws;
+  if (method < 0) {
+    rc = mxdet_nms_batched((const float*)w.sboxes, w.counts, nullptr, B, R, nms_thresh, max_per_image, w.keep_idx,
+                           w.num_keep, w.nms_ws, w.nms_bytes, stream);
+    if (rc) return rc;
+  } else {
+    soft_nms_launch((const float4*)w.sboxes, nullptr, (const unsigned long long*)w.skeys, w.counts, B, R, method,
+                    nms_thresh, sigma, score_thresh, max_per_image, R, 0, w.keep_idx, nullptr, dkeys, w.num_keep, s);
+  }
   hipLaunchKernelGGL(det_merge_kernel, dim3(N), dim3(1024), merge_lds, s, C + 1, R, max_per_image, max_per_image,
-                     (const unsigned long long*)w.skeys, (const float4*)w.sboxes, (const int32_t*)w.keep_idx,
-                     (const int32_t*)w.num_keep, dets, num_dets);
+                     (const unsigned long long*)w.skeys, (const unsigned long long*)dkeys, (const float4*)w.sboxes,
+                     (const int32_t*)w.keep_idx, (const int32_t*)w.num_keep, dets, num_dets);
   return check_launch("retina_detect(merge)");
+}
+
+extern "C" int mxdet_retina_detect(const mxdet_pyramid_t* p, int32_t N, const float* im_info, int32_t pre_nms_top_n,
+                                   float score_thresh, float nms_thresh, int32_t max_per_image, float* dets,
+                                   int32_t* num_dets, void* workspace, size_t workspace_bytes, mxdet_stream_t stream) {
+  clear_error();
+  return retina_detect_impl(p, N, im_info, pre_nms_top_n, score_thresh, nms_thresh, max_per_image, dets, num_dets,
+                            workspace, workspace_bytes, -1, 0.0f, stream);
+}
+
+extern "C" int mxdet_retina_detect_soft(const mxdet_pyramid_t* p, int32_t N, const float* im_info,
+                                        int32_t pre_nms_top_n, float score_thresh, float nms_thresh,
+                                        int32_t max_per_image, float* dets, int32_t* num_dets, void* workspace,
+                                        size_t workspace_bytes, int32_t method, float sigma, mxdet_stream_t stream) {
+  clear_error();
+  MXDET_REQUIRE(method >= 0 && method <= 2, MXDET_EINVAL, "retina_detect_soft: method %d not in 0..2", method);
+  MXDET_REQUIRE(method != 2 || sigma > 0.0f, MXDET_EINVAL, "retina_detect_soft: sigma must be positive for method 2");
+  return retina_detect_impl(p, N, im_info, pre_nms_top_n, score_thresh, nms_thresh, max_per_image, dets, num_dets,
+                            workspace, workspace_bytes, method, sigma, stream);
 }

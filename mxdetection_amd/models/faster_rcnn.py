@@ -228,9 +228,9 @@ class FasterRCNN(DetectorBase):
         return rpn_loss, rcnn_loss
 
     def predict(self, image, im_info, score_thresh=0.05, nms_thresh=0.5, max_per_image=100, with_masks=False,
-                mask_thresh=0.5):
+                mask_thresh=0.5, nms_method="hard", soft_sigma=0.5):
         """Inference: forward, proposals, box head, then softmax / decode / per-class NMS / top-k on the GPU
-        (core/evaluation, SURVEY.md section 8f rank 3). Returns (dets [N,max_per_image,6] = x1,y1,x2,y2,score,class;
+        (core/evaluation, SURVEY.md section 8f rank 3); nms_method "linear" / "gaussian": Soft-NMS per class. Returns (dets [N,max_per_image,6] = x1,y1,x2,y2,score,class;
         num_dets [N]); with_masks (Mask R-CNN) adds the pasted-back instance masks [N,max_per_image,H,W] u8 in the
         frame of the network input: mask head on the detected boxes, sigmoid, bilinear resize into the box, threshold."""
         from ..core.evaluation import DetectionPostprocess
@@ -243,10 +243,10 @@ class FasterRCNN(DetectorBase):
         pooled = self.roi_extractor.forward(P, rois.view(-1, 5))
         o = self.bbox_head.forward(pooled)
         o2 = o.view(o.shape[0], -1)
-        key = (score_thresh, nms_thresh, max_per_image)
+        key = (score_thresh, nms_thresh, max_per_image, nms_method, soft_sigma)
         if getattr(self, "_post_key", None) != key:
             self._post = DetectionPostprocess(self.bbox_head.nc, score_thresh, nms_thresh, max_per_image,
-                                              stds=self.bbox_head.stds)
+                                              stds=self.bbox_head.stds, nms_method=nms_method, soft_sigma=soft_sigma)
             self._post_key = key
         dets, num = self._post(o2[:, :self.bbox_head.nc], o2[:, self.bbox_head.nc:], rois.view(-1, 5), num_rois, im_info)
         if not with_masks:

@@ -48,19 +48,20 @@ class RetinaNet(DetectorBase):
         self.dC = [None] + [torch.empty(s, dtype=torch.bfloat16, device=dev) for s in c_shapes[1:]]
         self.planned = key
 
-    def predict(self, image, im_info, score_thresh=0.05, nms_thresh=0.5, max_per_image=100, pre_nms_top_n=1000):
+    def predict(self, image, im_info, score_thresh=0.05, nms_thresh=0.5, max_per_image=100, pre_nms_top_n=1000,
+                nms_method="hard", soft_sigma=0.5):
         """Inference: forward, then per-level top-k / decode / per-class NMS / top-k on the GPU (core/evaluation
-        RetinaDetect). Returns (dets [N,max_per_image,6] = x1,y1,x2,y2,score,class in 1..C; num_dets [N])."""
+        RetinaDetect; nms_method "linear" / "gaussian": Soft-NMS per class). Returns (dets [N,max_per_image,6] = x1,y1,x2,y2,score,class in 1..C; num_dets [N])."""
         from ..core.evaluation import RetinaDetect
         N, _, H, W = image.shape
         g_max = self.planned[3] if self.planned is not None and self.planned[:3] == (N, H, W) else 100
         self.plan(N, H, W, g_max)
         P = self.neck.forward(self.backbone.forward(image)[1:])
         co, bo = self.head.forward(P)
-        key = (score_thresh, nms_thresh, max_per_image, pre_nms_top_n)
+        key = (score_thresh, nms_thresh, max_per_image, pre_nms_top_n, nms_method, soft_sigma)
         if getattr(self, "_det_key", None) != key:
             self._det = RetinaDetect(self.head.Cn, self.strides, self.head.base, pre_nms_top_n, score_thresh, nms_thresh,
-                                     max_per_image)
+                                     max_per_image, nms_method=nms_method, soft_sigma=soft_sigma)
             self._det_key = key
         return self._det(co, bo, im_info)
 

@@ -75,6 +75,8 @@ DEFAULTS = {
     "TEST": {
         "batch_images": 2, "score_thresh": 0.05, "nms": 0.5, "max_per_image": 100,
         "bbox_means": [0.0, 0.0, 0.0, 0.0], "bbox_stds": [0.1, 0.1, 0.2, 0.2],
+        "nms_method": "hard",             # per-class stage: "hard" (greedy NMS) | "linear" | "gaussian" (Soft-NMS)
+        "soft_sigma": 0.5,                # sigma of the Gaussian Soft-NMS weight exp(-iou^2 / sigma)
     },
 }
 

@@ -38,9 +38,10 @@ def main():
     for k, batch in enumerate(loader):
         if segm:
             dets, num, masks = model.predict(batch["image"], batch["im_info"], te.score_thresh, te.nms, te.max_per_image,
-                                             with_masks=True)
+                                             with_masks=True, nms_method=te.nms_method, soft_sigma=te.soft_sigma)
         else:
-            dets, num = model.predict(batch["image"], batch["im_info"], te.score_thresh, te.nms, te.max_per_image)
+            dets, num = model.predict(batch["image"], batch["im_info"], te.score_thresh, te.nms, te.max_per_image,
+                                      nms_method=te.nms_method, soft_sigma=te.soft_sigma)
         ids = [int(i) for i in order[k]]
         fresh = [n for n, i in enumerate(ids) if i not in seen]          # the last batch wraps around
         scales = batch["im_info"][:, 2].cpu().numpy().tolist()
