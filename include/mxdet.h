@@ -177,6 +177,49 @@ int mxdet_anchor_target(const float* anchors, int64_t A_total, const float* gt_b
                         mxdet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * core/anchor (README.md:16) -- ATSS anchor assignment (Adaptive Training Sample Selection, Zhang et al., CVPR 2020)
+ * for the dense head: the alternative to mxdet_anchor_target's max-IoU rule with batch_size <= 0. DESIGN.md 5h.
+ * Inputs:
+ *   anchors[A_total,4]   fp32, the head's global order (level, y, x, a).
+ *   level_offsets[L+1]   level l owns anchors [off[l], off[l+1]).
+ *   gt_boxes[N,G_max,5]  rows with class < 0 are padding, anywhere in the list.
+ *   topk = k.
+ * Every step below is one fp32 operation in the order written, without FMA contraction.
+ *   1. Centres. Anchor centre cx = 0.5f*(x1+x2), cy = 0.5f*(y1+y2). Ground-truth centre the same.
+ *   2. Distance key. dx = cx-gx; dy = cy-gy; d = dx*dx + dy*dy (a product, a product and one add; no square root:
+ *      ranking needs none).
+ *   3. Candidates of (image n, valid GT g, level l): the min(k, n_l) anchors of the level with the smallest
+ *      (d, anchor index) -- a total order on the float bit pattern of d, which is non-negative; ties go to the lower
+ *      global anchor index. There is no inside-image filter (RetinaNet already runs with allowed_border = 1e6).
+ *   4. Statistics of g. Take all its candidates over the levels in ascending global anchor index, with
+ *      v_i = mxdet_iou(anchor_i, gt_g) (the +1 convention):
+ *        s = ((v_0 + v_1) + v_2) + ...;  mean = s / (float)count;
+ *        ss = sum in the same order of t = v_i - mean; t*t;
+ *        var = count > 1 ? ss / (float)(count-1) : 0   (the unbiased form, as the published code's .std()).
+ *   5. Positive candidates. The threshold test is v_i >= mean and (v_i-mean)*(v_i-mean) >= var -- the squared form of
+ *      v_i >= mean + std, chosen so that no square root has to agree between CPU and GPU. The centre test is
+ *      min(cx-gx1, cy-gy1, gx2-cx, gy2-cy) > 0.01f. A candidate is positive when both hold.
+ *   6. Conflicts. An anchor positive for several ground-truth boxes goes to the one with the largest IoU, by float
+ *      bits; ties go to the lower GT index.
+ *   7. Outputs, with the shapes and meaning of mxdet_anchor_target (mxdet_anchor_class_labels and both
+ *      mxdet_retina_loss_level* entries consume them unchanged):
+ *        labels[N,A_total]         1 for positive, 0 for everything else; never -1 (ATSS has no ignore band); an image
+ *                                  without a valid GT is all 0.
+ *        matched_gt[N,A_total]     g for positives, -1 otherwise.
+ *        bbox_targets[N,A_total,4] mxdet_encode(anchor, gt) for positives, 0 otherwise.
+ *        matched_iou[N,A_total]    optional, may be NULL: the IoU with the matched GT, 0 otherwise.
+ * Limits: 1 <= topk <= 16, 1 <= L <= 8, G_max <= 1024, every level non-empty, offsets ascending from 0 with
+ * off[L] == A_total; violations return MXDET_ESHAPE / MXDET_EINVAL (topk, null pointers) from the host check before any
+ * launch, with a message naming the argument. level_offsets is a HOST array, read at call time and passed by value to
+ * the kernels (no device copy, no retained pointer). No allocation, no host synchronisation: the result is a pure
+ * function of the inputs, so a captured graph replays it with new gt_boxes contents. */
+size_t mxdet_atss_assign_workspace_bytes(int32_t N, int64_t A_total, int32_t G_max);
+int mxdet_atss_assign(const float* anchors, int64_t A_total, const int64_t* level_offsets /* host, L+1 */, int32_t L,
+                      const float* gt_boxes, int32_t N, int32_t G_max, int32_t topk,
+                      int32_t* labels, int32_t* matched_gt, float* bbox_targets, float* matched_iou /* may be NULL */,
+                      void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * core/bbox (README.md:17) -- proposal-target: RoI sampling for the box head.
  * Candidates of image n = its first num_rois[n] proposals followed by its valid GT boxes.
  * fg: max IoU >= fg_thresh; bg: bg_lo <= max IoU < bg_hi. Sample min(fg_fraction*rois_per_image,

@@ -1,4 +1,6 @@
 """core/anchor (/root/reference/README.md:16): anchor generation and anchor<->GT target assignment."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -65,3 +67,41 @@ def assign_anchor(anchors, gt_boxes, im_info, fg_thresh=0.7, bg_thresh=0.3, allo
                                   ptr(matched), ptr(targets), ptr(max_iou), ptr(workspace.buf), workspace.nbytes,
                                   stream_ptr()), "anchor_target")
     return labels, matched, targets, max_iou
+
+
+class AtssWorkspace:
+    """Caller-owned scratch for atss_assign: one 64-bit word per (image, anchor)."""
+
+    def __init__(self, N, A_total, G_max, device):
+        lib = _lib.load()
+        nbytes = lib.mxdet_atss_assign_workspace_bytes(N, A_total, G_max)
+        self.buf = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+        self.nbytes = nbytes
+
+
+def atss_assign(anchors, level_offsets, gt_boxes, topk=9, workspace=None, out=None):
+    """ATSS targets for the dense head (include/mxdet.h: mxdet_atss_assign). anchors [A,4] in the head's global order,
+    level_offsets: L+1 host integers (level l owns anchors [off[l], off[l+1])), gt_boxes [N,G,5].
+
+    Returns (labels [N,A] i32 in {0,1}, matched_gt [N,A] i32, bbox_targets [N,A,4] f32, matched_iou [N,A] f32), the
+    shapes and meaning of assign_anchor's; out may carry None in the last place (no matched_iou).
+    """
+    lib = _lib.load()
+    N, G = gt_boxes.shape[0], gt_boxes.shape[1]
+    A = anchors.shape[0]
+    dev = anchors.device
+    if workspace is None:
+        workspace = AtssWorkspace(N, A, G, dev)
+    if out is None:
+        labels = torch.empty((N, A), dtype=torch.int32, device=dev)
+        matched = torch.empty((N, A), dtype=torch.int32, device=dev)
+        targets = torch.empty((N, A, 4), dtype=torch.float32, device=dev)
+        matched_iou = torch.empty((N, A), dtype=torch.float32, device=dev)
+    else:
+        labels, matched, targets, matched_iou = out
+    offs = [int(o) for o in level_offsets]
+    off_arr = (ctypes.c_int64 * len(offs))(*offs)
+    check(lib.mxdet_atss_assign(ptr(anchors), A, off_arr, len(offs) - 1, ptr(gt_boxes), N, G, int(topk), ptr(labels),
+                                ptr(matched), ptr(targets), ptr(matched_iou), ptr(workspace.buf), workspace.nbytes,
+                                stream_ptr()), "atss_assign")
+    return labels, matched, targets, matched_iou

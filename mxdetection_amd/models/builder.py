@@ -8,6 +8,9 @@ def build_detector(cfg, device="cuda"):
     dcn = dict(dcn_stages=tuple(net.dcn_stages), dcn_modulated=bool(net.dcn_modulated), dcn_groups=int(net.dcn_groups))
     reg = dict(reg_loss=str(net.reg_loss), reg_loss_weight=net.reg_loss_weight)
     if net.type in ("faster_rcnn", "mask_rcnn"):
+        if net.assigner != "max_iou":
+            raise ValueError("network.assigner = %r: %s keeps the RPN's sampler (atss is a retinanet option)"
+                             % (net.assigner, net.type))
         dpool = dict(roi_pool=str(net.roi_pool), dpool_trans_std=float(net.dpool_trans_std),
                      dpool_sample_per_part=int(net.dpool_sample_per_part), dpool_offset_fcs=int(net.dpool_offset_fcs))
         heads = dict(bbox_head=str(net.bbox_head), head_norm=str(net.head_norm), gn_groups=net.gn_groups)
@@ -20,7 +23,9 @@ def build_detector(cfg, device="cuda"):
             raise ValueError("network.roi_pool = %r: retinanet has no RoI branch" % (net.roi_pool,))
         if net.bbox_head != "2fc" or net.head_norm != "none":
             raise ValueError("network.bbox_head / network.head_norm: retinanet has no RoI heads")
-        model = RetinaNet(device, depth=net.backbone_depth, num_classes=net.num_classes - 1, seed=net.seed, **dcn, **reg)
+        model = RetinaNet(device, depth=net.backbone_depth, num_classes=net.num_classes - 1, seed=net.seed, **dcn, **reg,
+                          assigner=str(net.assigner), atss_topk=net.atss_topk, anchor_ratios=tuple(net.anchor_ratios),
+                          anchor_scales_per_octave=net.anchor_scales_per_octave, anchor_scale=float(net.anchor_scale))
     else:
         raise ValueError("unknown network.type %r" % (net.type,))
     if net.pretrained:

@@ -5,22 +5,42 @@ import torch
 from ..core.loss import check_reg_loss
 from .backbones import ResNet
 from .necks.fpn import RetinaFPN
-from .rpn_heads.retina_head import RetinaHead
+from .rpn_heads.retina_head import RetinaHead, check_assigner
 from .utils.detector import DetectorBase
+
+
+def check_anchor_setting(anchor_ratios, anchor_scales_per_octave, anchor_scale):
+    """-> (ratios, octave_scales) of RetinaHead. The defaults give the head's own defaults bit for bit."""
+    ratios = tuple(float(r) for r in anchor_ratios)
+    if not ratios or any(not r > 0.0 for r in ratios):
+        raise ValueError("anchor_ratios = %r: expected a non-empty list of positive numbers" % (anchor_ratios,))
+    n = anchor_scales_per_octave
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 8:
+        raise ValueError("anchor_scales_per_octave = %r: expected an integer in 1..8" % (n,))
+    if not float(anchor_scale) > 0.0:
+        raise ValueError("anchor_scale = %r: expected a positive number" % (anchor_scale,))
+    return ratios, tuple(2.0 ** (float(i) / n) for i in range(n))
 
 
 class RetinaNet(DetectorBase):
     def __init__(self, device="cuda", depth=101, num_classes=80, seed=7, dcn_stages=(), dcn_modulated=True, dcn_groups=1,
-                 reg_loss="smooth_l1", reg_loss_weight=1.0):
+                 reg_loss="smooth_l1", reg_loss_weight=1.0, assigner="max_iou", atss_topk=9, anchor_ratios=(0.5, 1.0, 2.0),
+                 anchor_scales_per_octave=3, anchor_scale=4.0):
         """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
         reg_loss / reg_loss_weight: the head's box loss -- 'smooth_l1', or 'iou' / 'giou' / 'diou' on the decoded box times
-        reg_loss_weight (rpn_heads.RetinaHead)."""
+        reg_loss_weight (rpn_heads.RetinaHead).
+        assigner / atss_topk: 'max_iou' (thresholds 0.5 / 0.4) or 'atss' (core.anchor.atss_assign).
+        anchor_ratios / anchor_scales_per_octave / anchor_scale: the head's anchors per cell -- every ratio at the sizes
+        anchor_scale * 2^(i / scales_per_octave) * stride, i < scales_per_octave (ATSS as published: (1.0,), 1, 8.0)."""
         check_reg_loss(reg_loss, reg_loss_weight)
+        check_assigner(assigner, atss_topk)
+        ratios, octave_scales = check_anchor_setting(anchor_ratios, anchor_scales_per_octave, anchor_scale)
         gen = torch.Generator().manual_seed(seed)
         self._init_base(device)
         self.strides = [8, 16, 32, 64, 128]
         self.head = RetinaHead(256, self.strides, self.arena, self.ws, device, gen, num_classes=num_classes,
-                               reg_loss=reg_loss, reg_loss_weight=reg_loss_weight)
+                               ratios=ratios, octave_scales=octave_scales, anchor_scale=float(anchor_scale),
+                               reg_loss=reg_loss, reg_loss_weight=reg_loss_weight, assigner=assigner, atss_topk=atss_topk)
         self.mark_head = self.arena.size
         self.neck = RetinaFPN([512, 1024, 2048], 256, self.arena, self.ws, device, gen)
         self.mark_fpn = self.arena.size

@@ -1,5 +1,6 @@
 """RetinaNet dense head: two 4-conv towers (class / box) shared across P3..P7, 9 anchors per cell, sigmoid focal loss
-and smooth-L1 box loss on every anchor (no sampling, no proposals).
+and smooth-L1 box loss on every anchor (no sampling, no proposals). Targets: max-IoU assignment with fixed thresholds, or
+ATSS (`assigner="atss"`, core.anchor.atss_assign; its published setting is one square anchor of scale 8 per cell).
 
 Declared slot: the reference only names `rpn_heads` / `bbox_heads` for dense heads (/root/reference/README.md:28-29);
 RetinaNet is BASELINE.json config 5. Class logits are padded 9*80 = 720 -> 768 channels and deltas 36 -> 64 so that
@@ -15,13 +16,27 @@ from ...ops import dense
 from ..utils.layers import ConvLayer, cached_buf
 
 
+ASSIGNERS = ("max_iou", "atss")
+
+
+def check_assigner(assigner, atss_topk=9):
+    if assigner not in ASSIGNERS:
+        raise ValueError("assigner = %r: expected one of %s" % (assigner, ", ".join(ASSIGNERS)))
+    if isinstance(atss_topk, bool) or not isinstance(atss_topk, int) or not 1 <= atss_topk <= 16:
+        raise ValueError("atss_topk = %r: expected an integer in 1..16" % (atss_topk,))
+
+
 class RetinaHead:
     def __init__(self, channels, strides, arena, ws, device, gen, num_classes=80, num_convs=4, ratios=(0.5, 1.0, 2.0),
                  octave_scales=(1.0, 2.0 ** (1.0 / 3.0), 2.0 ** (2.0 / 3.0)), anchor_scale=4.0, fg_thresh=0.5,
-                 bg_thresh=0.4, alpha=0.25, gamma=2.0, sigma=3.0, prior=0.01, reg_loss="smooth_l1", reg_loss_weight=1.0):
-        """reg_loss: 'smooth_l1' on the encoded deltas (core.loss.retina_loss_level), or 'iou' / 'giou' / 'diou' on the
+                 bg_thresh=0.4, alpha=0.25, gamma=2.0, sigma=3.0, prior=0.01, reg_loss="smooth_l1", reg_loss_weight=1.0,
+                 assigner="max_iou", atss_topk=9):
+        """assigner: 'max_iou' (fg_thresh / bg_thresh) or 'atss' (the atss_topk nearest anchors per level and GT).
+        reg_loss: 'smooth_l1' on the encoded deltas (core.loss.retina_loss_level), or 'iou' / 'giou' / 'diou' on the
         decoded box times reg_loss_weight (core.loss.retina_loss_level_iou; stds 1, as the inference decode)."""
         L_.check_reg_loss(reg_loss, reg_loss_weight)
+        check_assigner(assigner, atss_topk)
+        self.assigner, self.atss_topk = assigner, int(atss_topk)
         self.reg_loss, self.reg_loss_weight = reg_loss, float(reg_loss_weight)
         kw = dict(arena=arena, ws=ws, device=device, gen=gen)
         self.A, self.Cn = len(ratios) * len(octave_scales), num_classes
@@ -66,7 +81,7 @@ class RetinaHead:
             self.level_offsets.append(self.level_offsets[-1] + H * W * self.A)
         At = self.anchors.shape[0]
         dev = self.device
-        self.at_ws = A_.AnchorTargetWorkspace(N, At, g_max, dev)
+        self.at_ws = (A_.AtssWorkspace if self.assigner == "atss" else A_.AnchorTargetWorkspace)(N, At, g_max, dev)
         self.at_out = (torch.empty((N, At), dtype=torch.int32, device=dev), torch.empty((N, At), dtype=torch.int32, device=dev),
                        torch.empty((N, At, 4), dtype=torch.float32, device=dev), torch.empty((N, At), dtype=torch.float32, device=dev))
         self.cls_labels = torch.empty((N, At), dtype=torch.int32, device=dev)
@@ -99,8 +114,12 @@ class RetinaHead:
         return self.co, self.bo
 
     def loss_and_grad(self, gt_boxes, im_info, loss_scale=1.0):
-        labels, matched, targets, _ = A_.assign_anchor(self.anchors, gt_boxes, im_info, self.fg_thresh, self.bg_thresh,
-                                                       1.0e6, 0, 0.5, 0, 0, 0, self.at_ws, self.at_out)
+        if self.assigner == "atss":
+            labels, matched, targets, _ = A_.atss_assign(self.anchors, self.level_offsets, gt_boxes, self.atss_topk,
+                                                         self.at_ws, self.at_out)
+        else:
+            labels, matched, targets, _ = A_.assign_anchor(self.anchors, gt_boxes, im_info, self.fg_thresh, self.bg_thresh,
+                                                           1.0e6, 0, 0.5, 0, 0, 0, self.at_ws, self.at_out)
         L_.anchor_class_labels(labels, matched, gt_boxes, self.cls_labels, self.num_fg)
         self.matched = matched
         self.gco, self.gbo = [], []

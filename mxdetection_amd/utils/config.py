@@ -49,6 +49,11 @@ DEFAULTS = {
         "gn_groups": 32,                  # GroupNorm groups (256 / gn_groups must be a multiple of 8)
         "reg_loss": "smooth_l1",          # box regression loss of the box head / the RetinaNet head: smooth_l1 | iou | giou | diou
         "reg_loss_weight": 1.0,           # weight of an IoU-family reg_loss (on the decoded box); smooth_l1 takes none. The RPN keeps smooth-L1
+        "assigner": "max_iou",            # retinanet targets: max_iou (thresholds 0.5 / 0.4) | atss (Zhang et al. 2020). The RPN keeps its sampler
+        "atss_topk": 9,                   # ATSS: candidates per ground-truth box and pyramid level (1..16)
+        "anchor_ratios": [0.5, 1.0, 2.0],  # retinanet anchors per cell: these h/w ratios ...
+        "anchor_scales_per_octave": 3,    # ... times this many sizes per octave ...
+        "anchor_scale": 4.0,              # ... starting at anchor_scale * stride (ATSS as published: [1.0], 1, 8.0)
         "dpool_offset_fcs": 3,            # FCs of the offset head (1: Deformable-ConvNets' FPN head, 3: DCN v2 / mmdetection)
     },
     "dataset": {
