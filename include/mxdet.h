@@ -586,6 +586,52 @@ int mxdet_filter_transpose(const uint16_t* w, int32_t Cout, int32_t KH, int32_t 
 int mxdet_filter_transpose_batched(const void* descs_dev, int32_t ndesc, int32_t total_tiles,
                                    mxdet_stream_t stream);
 
+/* Sparse backward of the RPN head (3x3 conv C -> C + ReLU, fused 1x1 C -> Ch): the RPN loss leaves at most
+ * smax = N * batch_size cells with a non-zero gradient row, and only those are multiplied. Pyramid of num_levels levels,
+ * level l being [N, H[l], W[l], *] channels-last tensors; the global id of cell (n, l, h, w) is
+ *   n * CT + coff[l] + h * W[l] + w,  coff[l] = sum of H*W over the levels before l, CT = coff[num_levels]
+ * (the anchor index of mxdet_anchor_target divided by A). C % 64 == 0, Ch == 64, smax <= 8192.
+ *
+ * mxdet_rpn_sparse_list: a cell is active if one of its A labels (labels [N, CT*A] i32) is >= 0. Writes
+ *   list [2*smax] i32: the active cell ids in ascending order in [0, S), -1 in [S, smax) (the upper half is scratch);
+ *   state [2] i32: state[0] = S (active cells past smax are dropped: the sampler never produces them);
+ *   map [N*CT] i32: the slot of every active cell, -1 elsewhere (rewritten in full by every call).
+ * mxdet_rpn_sparse_backward runs the parts named in `parts`, in this order, S read from state on the device:
+ *   ZERO   every level with accumulate[l] == 0 is cleared;
+ *   DT     dts [smax, C] bf16: row s = the 1x1 data gradient of gh's row of cell list[s] (wt_out [C, Ch], the transposed
+ *          filter), masked by the cell's ReLU bits (tbits[l] u8 [N,H,W,C/8], or t[l] > 0 where tbits[l] is NULL); ghs
+ *          [smax, Ch] = those gh rows; rows past S are zero. The bits are those of mxdet_conv2d_dgrad.
+ *   DTMAP  (with DT) the dense maps dt[l] [N,H,W,C] are cleared and the listed rows written into them as well: the
+ *          operand of the dense weight gradient (mxdet_conv2d_wgrad*), bit for bit what mxdet_conv2d_dgrad writes.
+ *   WGRAD  dw_out [Ch,1,1,C], db_out [Ch], dw_conv [C,3,3,C], db_conv [C] (f32, overwritten): sums over the slots in slot
+ *          order, 32 per MFMA step; needs DT's outputs.
+ *   DGRAD  the 3x3 / stride 1 / pad 1 data gradient (wt_conv [C,3,3,C] transposed filter) of dts scattered to its cells,
+ *          written to (accumulate[l]: added to) the pixels of dP[l] that have an active cell in their 3x3 neighbourhood,
+ *          each once, with the bits mxdet_conv2d_dgrad gives them; other pixels are not touched. */
+#define MXDET_RPN_SPARSE_MAX_LEVELS 8
+#define MXDET_RPN_SPARSE_ZERO 1
+#define MXDET_RPN_SPARSE_DT 2
+#define MXDET_RPN_SPARSE_WGRAD 4
+#define MXDET_RPN_SPARSE_DGRAD 8
+#define MXDET_RPN_SPARSE_DTMAP 16
+typedef struct {
+  int32_t num_levels, N, A, C, Ch, smax;
+  int32_t H[MXDET_RPN_SPARSE_MAX_LEVELS], W[MXDET_RPN_SPARSE_MAX_LEVELS];
+  int32_t accumulate[MXDET_RPN_SPARSE_MAX_LEVELS];
+  const void* P[MXDET_RPN_SPARSE_MAX_LEVELS];      /* bf16 [N,H,W,C]: the head's input */
+  const void* t[MXDET_RPN_SPARSE_MAX_LEVELS];      /* bf16 [N,H,W,C]: relu(conv(P)) */
+  const void* tbits[MXDET_RPN_SPARSE_MAX_LEVELS];  /* u8 [N,H,W,C/8] or NULL */
+  const void* gh[MXDET_RPN_SPARSE_MAX_LEVELS];     /* bf16 [N,H,W,Ch]: d(loss)/d(head output) */
+  void* dP[MXDET_RPN_SPARSE_MAX_LEVELS];           /* bf16 [N,H,W,C] */
+  void* dt[MXDET_RPN_SPARSE_MAX_LEVELS];           /* bf16 [N,H,W,C] or NULL (DTMAP) */
+} mxdet_rpn_sparse_t;
+int mxdet_rpn_sparse_list(const mxdet_rpn_sparse_t* d, const int32_t* labels, int32_t* list, int32_t* state,
+                          int32_t* map, mxdet_stream_t stream);
+int mxdet_rpn_sparse_backward(const mxdet_rpn_sparse_t* d, const int32_t* list, const int32_t* state,
+                              const int32_t* map, const uint16_t* wt_out, const uint16_t* wt_conv, uint16_t* dts,
+                              uint16_t* ghs, float* dw_out, float* db_out, float* dw_conv, float* db_conv,
+                              int32_t parts, mxdet_stream_t stream);
+
 /* Deformable convolution (DCN v1 / v2), MXNet role contrib.DeformableConvolution (Deformable-ConvNets'
  * deformable_im2col semantics; dilation 1, 3x3 kernels only: anything else is MXDET_ESHAPE).
  * x bf16 [N,H,W,C]; off bf16 [N,Ho,Wo,off_channels] (off_channels % 8 == 0) with G = groups deformable groups:

@@ -82,6 +82,13 @@ class GnDescT(C.Structure):
                 ("accumulate", c_i32)]
 
 
+class RpnSparseT(C.Structure):
+    """mxdet_rpn_sparse_t (include/mxdet.h)."""
+    _fields_ = [("num_levels", c_i32), ("N", c_i32), ("A", c_i32), ("C", c_i32), ("Ch", c_i32), ("smax", c_i32),
+                ("H", c_i32 * 8), ("W", c_i32 * 8), ("accumulate", c_i32 * 8),
+                ("P", c_vp * 8), ("t", c_vp * 8), ("tbits", c_vp * 8), ("gh", c_vp * 8), ("dP", c_vp * 8), ("dt", c_vp * 8)]
+
+
 WgradItemT._fields_ = [("desc", ConvDescT), ("x", c_vp), ("dy", c_vp), ("dw", c_vp), ("db", c_vp)]
 ConvItemT._fields_ = [("desc", ConvDescT), ("src", c_vp), ("filt", c_vp), ("bias", c_vp), ("residual", c_vp),
                       ("relu_mask", c_vp), ("dst", c_vp)]
@@ -183,6 +190,9 @@ SIGNATURES = {
     "mxdet_conv2d_wgrad_grouped_parts": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_sz, c_vp]),
     "mxdet_debug_force_conv_cfg": (c_i32, [c_i32]),
     "mxdet_debug_force_wgrad_ksplit": (c_i32, [c_i32]),
+    "mxdet_rpn_sparse_list": (c_i32, [P(RpnSparseT), c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mxdet_rpn_sparse_backward": (c_i32, [P(RpnSparseT), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                          c_i32, c_vp]),
     "mxdet_filter_transpose": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mxdet_filter_transpose_batched": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
     "mxdet_deform_im2col": (c_i32, [P(DeformDescT), c_vp, c_vp, c_vp, c_vp]),

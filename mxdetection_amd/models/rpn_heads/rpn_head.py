@@ -13,12 +13,18 @@ from ...core import anchor as A_
 from ...core import loss as L_
 from ...ops import dense
 from ...ops.proposal import PyramidProposal
+from ...ops import rpn_sparse as RS
+from ...ops.rpn_sparse import MAX_SLOTS, RPNSparse
 from ..utils.layers import ConvLayer, cached_buf
 
 HEAD_CPAD = 64   # fused cls+reg output channels padded so that dgrad's reduction dim is a multiple of 64
 
 
 RELU_BITS = os.environ.get("MXDET_TUNE_RELU_BITS", "1") == "1"
+# backward over the sampled anchors' cells only (ops/rpn_sparse.py). 0: the dense kernels; 1: sparse
+# data gradients, the dense weight-gradient kernels on a scattered dt map (every result bit-identical to 0); 2: the weight
+# gradients over the slots as well (faster; they differ from 0 in fp32 summation order)
+RPN_SPARSE = int(os.environ.get("MXDET_TUNE_RPN_SPARSE", "1"))
 
 
 class RPNHead:
@@ -65,6 +71,20 @@ class RPNHead:
         self.nparts = [L_.rpn_loss_num_partials(N, H, W) for (H, W) in self.level_shapes]
         self.partial = torch.zeros((2 * sum(self.nparts),), dtype=torch.float32, device=self.device)
         self.loss = torch.zeros((2,), dtype=torch.float32, device=self.device)
+        # the loss leaves at most batch_size sampled anchors per image with a gradient: that many slots
+        smax = N * self.batch_size
+        self.sparse = (RPNSparse(self.level_shapes, N, self.A, self.C, HEAD_CPAD, smax, self.device)
+                       if RPN_SPARSE and 0 < smax <= MAX_SLOTS else None)
+        self.sparse_wgrad = int(RPN_SPARSE) == 2
+        self.dt_map = None
+        if self.sparse is not None and not self.sparse_wgrad:
+            # dense dt maps for the dense weight gradient, one flat buffer (cleared by one launch), levels are views
+            sizes = [s[0] * s[1] * s[2] * s[3] for s in p_shapes]
+            flat = self._buf("dt_map", (sum(sizes),))
+            self.dt_map, off = [], 0
+            for s, n in zip(p_shapes, sizes):
+                self.dt_map.append(flat[off:off + n].view(tuple(s)))
+                off += n
 
     def forward(self, P):
         """The largest level keeps its own launches (it fills the chip and has its own tile path); the remaining levels
@@ -93,6 +113,8 @@ class RPNHead:
                                                  self.batch_size, self.fg_fraction, self.seed, step, image_offset,
                                                  self.at_ws, self.at_out, step_dev)
         self._assigned = (labels, targets)
+        if self.sparse is not None:
+            self.sparse.build_list(labels)
 
     def loss_and_grad(self, gt_boxes, im_info, step, image_offset, loss_scale=1.0, step_dev=None, assigned=False):
         """Assign anchors (unless assign_targets() already ran for this step), compute the RPN losses and
@@ -116,6 +138,8 @@ class RPNHead:
     def backward(self, dP, dP_has_grad, flush=True):
         """Adds the RPN branch's gradient into dP[l] (overwrites where dP_has_grad[l] is False). flush=False leaves the
         recorded weight gradients pending in the workspace: the caller issues them later (ws.flush())."""
+        if self.sparse is not None:
+            return self._backward_sparse(dP, dP_has_grad, flush)
         L = len(self.h)
         dt = [self._buf("dt%d" % l, self.t[l].shape) for l in range(L)]
         grouped = self.out.ws.grouping     # grouped form: the plan sums the levels of a shared filter itself
@@ -130,5 +154,27 @@ class RPNHead:
         self.conv.backward_data(dt[0], self.P[0].shape, accumulate=dP_has_grad[0], out=dP[0])
         dense.conv2d_group("dgrad", [self.conv.dgrad_call(dt[l], self.P[l].shape, accumulate=dP_has_grad[l], out=dP[l])
                                      for l in range(1, L)], self.device)
+        if flush:
+            self.out.ws.flush()
+
+    def _backward_sparse(self, dP, dP_has_grad, flush=True):
+        """The same gradients from the active cells alone (assign_targets listed them): dP is cleared where it holds
+        nothing yet, then compact rpn.out data-gradient rows and the rpn.conv data gradient of the touched pixels.
+        Weight gradients: the dense kernels as in backward(), rpn.conv's on a dt map that holds the listed rows and zeros
+        (same operands bit for bit, so same results); or (sparse_wgrad) sums over the slots straight into the arena,
+        nothing recorded in the workspace."""
+        g = self.out.arena
+        grads = (g.view(self.out.wi, "g"), g.view(self.out.bi, "g"), g.view(self.conv.wi, "g"), g.view(self.conv.bi, "g"))
+        if self.sparse_wgrad:
+            self.sparse.backward(self.P, self.t, self.tbits, self.gh, dP, dP_has_grad, self.out.wt, self.conv.wt, *grads)
+            return
+        L = len(self.h)
+        grouped = self.out.ws.grouping
+        for l in range(L):
+            self.out.backward_weight(self.t[l], self.gh[l], accumulate=(l > 0) and not grouped)
+        self.sparse.backward(self.P, self.t, self.tbits, self.gh, dP, dP_has_grad, self.out.wt, self.conv.wt, *grads,
+                             parts=RS.ZERO | RS.DT | RS.DTMAP | RS.DGRAD, dt=self.dt_map)
+        for l in range(L):
+            self.conv.backward_weight(self.P[l], self.dt_map[l], accumulate=(l > 0) and not grouped)
         if flush:
             self.out.ws.flush()
