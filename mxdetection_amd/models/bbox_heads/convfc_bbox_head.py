@@ -43,7 +43,7 @@ class BBoxHead:
         """The layers in front of fc_out, registered in backward completion order."""
         self.fc2 = ConvLayer("bbox.fc2", fc_dim, fc_dim, 1, **kw)
         self.fc1 = ConvLayer("bbox.fc1", in_features, fc_dim, 1, **kw)
-        # checkpoint layout (DetectorBase._to_mx): fully connected layers are stored 2-D; fc1's input is the pooled
+        # checkpoint layout (CheckpointMixin._to_mx): fully connected layers are stored 2-D; fc1's input is the pooled
         # [7,7,C] block flattened (H, W, C) here and (C, H, W) in an MXNet FullyConnected after a Flatten of NCHW
         pooled = 7
         self.fc1.fc_in_hwc = (pooled, pooled, in_features // (pooled * pooled)) if in_features % (pooled * pooled) == 0 else ()

@@ -5,8 +5,6 @@ HIP kernel reached through the C-ABI; torch supplies device memory, streams and 
 Assembles the plugin parts the reference declares (/root/reference/README.md:27-32). The training loop
 itself is not declared anywhere in the reference tree; this is the build's own.
 """
-import os
-
 import torch
 
 from ..core.loss import check_reg_loss
@@ -62,8 +60,6 @@ class FasterRCNN(DetectorBase):
         # RoIAlign backward: deterministic gather form (no atomics, no fp32 accumulators, writes the bf16 maps directly);
         # False selects the fp32-atomic scatter form (310 us + zero-fill + finalize at the benchmark shape)
         self.roi_bwd_gather = True
-        # anchor assignment at the start of the step, on the branch stream (see forward_backward): +0.9 % on the step
-        self.early_anchor_targets = os.environ.get("MXDET_TUNE_EARLY_ANCHORS", "1") == "1"
         self.mask_head = None
         if with_mask:   # Mask R-CNN (BASELINE.json config 4): the mask branch's backward runs first
             self.mask_head = FCNMaskHead(256, self.arena, self.ws, device, gen, num_classes=num_classes,
@@ -103,12 +99,6 @@ class FasterRCNN(DetectorBase):
             layers = self.mask_head.layers() + layers
             norms = self.mask_head.norm_layers() + norms
         self._finalize_params(layers, norm_layers=norms)
-        # arena offsets after each backbone stage (layer4, layer3, layer2) for bucketed all-reduce
-        self.stage_marks = {}
-        for si in (3, 2, 1):
-            last = self.backbone.stages[si][0].layers()[-1]
-            e = self.arena.entries[last.wi]
-            self.stage_marks[si] = e[2] + (e[3] + 63) // 64 * 64
 
     def plan(self, N, H, W, g_max):
         key = (N, H, W, g_max)
@@ -142,10 +132,11 @@ class FasterRCNN(DetectorBase):
         """image NCHW [N,3,H,W]; gt_boxes [N,G,5] f32 (class < 0 padding); im_info [N,3] f32."""
         N, _, H, W = image.shape
         self.plan(N, H, W, gt_boxes.shape[1])
-        early = self.early_anchor_targets and self.branch is not None
+        early = self.branch is not None
         if early:
             # anchor assignment needs the ground truth only: on the branch stream it runs underneath the backbone forward,
             # and the RPN branch proper starts with its losses and heavy convolutions instead of ~100 us of small kernels
+            # (+0.9 % on the step)
             with self._branch_ctx():
                 self.rpn_head.assign_targets(gt_boxes, im_info, step, image_offset, step_dev)
         C = self.backbone.forward(image)
@@ -157,7 +148,7 @@ class FasterRCNN(DetectorBase):
         # The RPN head's weight gradients leave the branch and run on the side stream, with the head bucket, underneath
         # the RoIAlign gather (+0.8 % on the step).
         defer_rpn = (self.roi_bwd_gather and self.ws.side is not None and self.ws_rpn.grouping and self.ws.grouping
-                     and self._bucket_here(0) and os.environ.get("MXDET_TUNE_DEFER_RPN_WGRAD", "1") == "1")
+                     and self._bucket_here(0))
         with self._branch_ctx():
             rpn_loss = self.rpn_head.loss_and_grad(gt_boxes, im_info, step, image_offset, step_dev=step_dev, assigned=early)
             self.rpn_head.backward(self.dP, [False] * 5, flush=not defer_rpn)
@@ -183,19 +174,13 @@ class FasterRCNN(DetectorBase):
             # lengthening the branch.) The gather is issued FIRST and the head bucket's weight gradients, update and filter
             # transposes behind it (round 3: with the three-tap weight-gradient kernel the gather beside a 2,000-workgroup
             # MFMA grid took 235-310 us instead of its 70-90 us alone; alone first, then the bucket beside the P2 data
-            # gradients, is +0.3 % on the step. MXDET_TUNE_ROI_FIRST=0: the round-2 order, bucket first)
+            # gradients, is +0.3 % on the step). Deformable RoI pooling needs this order: its offset head's weight gradients
+            # belong to the head bucket, so the bucket closes behind the extractor's backward.
             lo = 0
-            roi_first = os.environ.get("MXDET_TUNE_ROI_FIRST", "1") == "1"     # the gather first, alone; the bucket behind it
-            # deformable RoI pooling: its offset head's weight gradients belong to the head bucket, so the bucket closes
-            # behind the extractor's backward
-            roi_first = roi_first or self.dpool is not None
-            if self._bucket_here(0) and not roi_first:
-                self._reduce(0, self.mark_rpn, pre=self.ws_rpn if defer_rpn else None)
-                lo = self.mark_rpn
             self.roi_extractor.backward_gather(d_pooled.view(pooled.shape), self.dP[:4], accumulate=True)
             if self.with_mask:
                 self.mask_roi_extractor.backward_gather(d_mpooled, self.dP[:4], accumulate=True)
-            if self._bucket_here(0) and roi_first:
+            if self._bucket_here(0):
                 self._reduce(0, self.mark_rpn, pre=self.ws_rpn if defer_rpn else None)
                 lo = self.mark_rpn
         else:
@@ -211,18 +196,7 @@ class FasterRCNN(DetectorBase):
         if self._bucket_here(1):
             self._reduce(lo, self.mark_fpn)
             lo = self.mark_fpn
-        # where the next step's frozen front end may start: behind the backward of backbone stage `tail_at` (1 = where the
-        # data-gradient chain ends; 2 / 3 = one / two stages earlier, 4 = before the backbone's backward)
-        tail_at = int(os.environ.get("MXDET_TUNE_TAIL_AT", "1"))
-        if tail_at >= 4:
-            self._mark_tail()
-        for si in (3, 2, 1):
-            self._backbone_stage_backward(si)
-            if si == tail_at:
-                self._mark_tail()
-            if si == 1 or self._bucket_here(5 - si):       # reduce points 2 (layer4), 3 (layer3); layer2 always closes
-                self._reduce(lo, self.stage_marks[si])
-                lo = self.stage_marks[si]
+        self._backbone_backward(lo)
         if self.with_mask:
             return rpn_loss, rcnn_loss, mask_loss
         return rpn_loss, rcnn_loss
@@ -262,15 +236,3 @@ class FasterRCNN(DetectorBase):
         logits = self.mask_head.forward(mpooled)
         masks = M_.mask_paste(logits, flat, H, W, mask_thresh)
         return dets, num, masks.view(N, M, H, W)
-
-    def _backbone_stage_backward(self, si):
-        stage = self.backbone.stages[si]
-        ds = self.dC[si]
-        for bi in reversed(range(len(stage))):
-            b = stage[bi]
-            if bi > 0:
-                ds = b.backward(ds, b._buf("dx", b.x.shape), False)
-            elif b.need_dx:
-                b.backward(ds, self.dC[si - 1], True)
-            else:
-                b.backward(ds, None, False)

@@ -48,11 +48,6 @@ class RetinaNet(DetectorBase):
                                dcn_modulated=dcn_modulated, dcn_groups=dcn_groups)
         self._finalize_params(self.head.layers() + self.neck.layers() + self.backbone.layers())
         self.head.post_materialize()
-        self.stage_marks = {}
-        for si in (3, 2, 1):
-            last = self.backbone.stages[si][0].layers()[-1]
-            e = self.arena.entries[last.wi]
-            self.stage_marks[si] = e[2] + (e[3] + 63) // 64 * 64
 
     def plan(self, N, H, W, g_max):
         key = (N, H, W, g_max)
@@ -101,20 +96,5 @@ class RetinaNet(DetectorBase):
         if self._bucket_here(1):
             self._reduce(lo, self.mark_fpn)
             lo = self.mark_fpn
-        for si in (3, 2, 1):
-            stage = self.backbone.stages[si]
-            ds = self.dC[si]
-            for bi in reversed(range(len(stage))):
-                b = stage[bi]
-                if bi > 0:
-                    ds = b.backward(ds, b._buf("dx", b.x.shape), False)
-                elif b.need_dx:
-                    b.backward(ds, self.dC[si - 1], True)
-                else:
-                    b.backward(ds, None, False)
-            if si == 1:
-                self._mark_tail()
-            if si == 1 or self._bucket_here(5 - si):
-                self._reduce(lo, self.stage_marks[si])
-                lo = self.stage_marks[si]
+        self._backbone_backward(lo)
         return (loss,)

@@ -45,7 +45,7 @@ class DeformRoIExtractor:
             self.mask_fc = [None, ConvLayer("bbox.mask_fc2", fc_dim, (nb + 63) // 64 * 64, 1, zero_init=True,
                                             cout_real=nb, **kw)]
             self.mask_fc[0] = ConvLayer("bbox.mask_fc1", self.in_features, fc_dim, 1, **kw)
-        # checkpoint layout (DetectorBase._to_mx): 2-D FC weights, the pooled-input ones reordered from (H, W, C) to (C, H, W)
+        # checkpoint layout (CheckpointMixin._to_mx): 2-D FC weights, the pooled-input ones reordered from (H, W, C) to (C, H, W)
         for l in self.layers():
             l.fc_in_hwc = (self.pooled[0], self.pooled[1], channels) if l.cin == self.in_features else ()
         self.bufs = {}

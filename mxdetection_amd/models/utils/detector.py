@@ -2,12 +2,14 @@
 capture / replay of the whole step, side-stream weight gradients, optimizer step."""
 import contextlib
 import os
-import warnings
 
 import torch
 
+from ...utils.hipgraph import GraphEvent
+from .checkpoint import CheckpointMixin
 from .dp import BucketReducer, make_comm
 from .layers import ParamArena, Workspace
+from .schedule import CapturedStep, ReplayScratch, ScheduleRecorder, begin_capture, uncovered_ranges
 
 
 # TIMING-ONLY ablations (tools/ablate_step.sh): MXDET_ABL_SKIP=front,sgd,transpose,wgrad leaves the named component out of the
@@ -15,8 +17,10 @@ from .layers import ParamArena, Workspace
 # schedule, which the sum of its kernel durations overstates). Never set outside that tool.
 _PROBE_STREAMS = []          # candidate streams of DetectorBase._stream_clear_of_the_exchange
 _ABL = frozenset(t for t in os.environ.get("MXDET_ABL_SKIP", "").split(",") if t)
+Workspace.abl_skip = _ABL
 
-class DetectorBase:
+
+class DetectorBase(CheckpointMixin):
     def _init_base(self, device):
         self.device = device
         self.arena = ParamArena(device)
@@ -25,30 +29,30 @@ class DetectorBase:
         self.dist = None
         self.comm = None
         self.world = 1
-        self.segments = None
-        self._cap = False
-        self._cur_graph = None
+        self.captured = None      # CapturedStep, once capture() has run
+        self._rec = None          # ScheduleRecorder while capture() runs the step under stream capture
         self._tr_table = None
         self.static_extra = {}
-        # single GPU: no exchange to overlap, so everything behind the heads is ONE bucket (see _bucket_here)
-        self.bucket_merge = os.environ.get("MXDET_TUNE_BUCKETS", "123")
+        # Tuning switches: read here, once. MXDET_TUNE_BUCKETS names the reduce points that do NOT close a bucket (see
+        # _bucket_here). Single GPU: no exchange to overlap, so everything behind the heads is ONE bucket.
+        self._bucket_env = os.environ.get("MXDET_TUNE_BUCKETS")
+        self.bucket_merge = "123" if self._bucket_env is None else self._bucket_env
+        # Captured step, frozen front end as a graph of its own (capture()): the stem + frozen stages of batch k run on
+        # the front stream while step k-1 is still in its weight-gradient tail (they depend on the image only).
+        front = os.environ.get("MXDET_TUNE_FRONT_PIPE", "1")
+        if front not in ("0", "1"):
+            raise ValueError("MXDET_TUNE_FRONT_PIPE must be 0 or 1 (got %r)" % (front,))
+        self.front_pipeline = front == "1"
+        self.front_probe = os.environ.get("MXDET_TUNE_FRONT_PROBE", "1") == "1"
+        self.front_probe_tries = int(os.environ.get("MXDET_TUNE_FRONT_PROBE_TRIES", "4"))
+        # filter prefetch hints (_wire_prefetch): 0 none, 1 every launch, 2 not the grouped launches
+        self.prefetch = os.environ.get("MXDET_TUNE_PREFETCH", "1")
         self.branch = None
         self._upd = None          # (lr, momentum, wd) while a training step wants its buckets updated as they finish
         self._upd_done = []       # arena ranges already updated in this step
         self._tr_ranges = {}
-        self._buckets = []        # (lo, hi) of every bucket exchanged in the captured step
-        self._seen_buckets = set()
-        self._final_join_opt = False
-        self._cap_opt = None      # (lr, momentum, wd) while capturing per-bucket update graphs (N > 1)
+        self._seen_buckets = set()       # (lo, hi) of every bucket an eager step has exchanged
         self.opt_stream = None
-        # Captured step, frozen front end as a graph of its own (capture(): front_pipeline): the stem + frozen stages of
-        # batch k run on the front stream while step k-1 is still in its weight-gradient tail (they depend on the image
-        # only). _tail_event is recorded by a node of the main graph where that tail begins.
-        self.front_pipeline = os.environ.get("MXDET_TUNE_FRONT_PIPE", "1") != "0"
-        self._seg_markers = []    # capture: bucket markers of the open main segment (exchange schedule, see _reduce)
-        self._deferred = []       # capture: per-bucket graphs still to be captured (_capture_deferred)
-        self._front = None        # {"graphs": [g0, g1], "segments": [s0, s1], "losses": [l0, l1], "stream", "ready", "count"}
-        self._tail_event = None
 
     def _finalize_params(self, layers, frozen_layers=(), norm_layers=()):
         self.layers = layers
@@ -60,135 +64,12 @@ class DetectorBase:
         self.arena.refresh_bf16()
         self.refresh_transposed()
         self.reducer = BucketReducer(self.arena.g, None)
-
-    def export_params(self):
-        """name -> fp32 CPU tensor of every parameter as the kernels see it (bf16 filters, fp32 biases)."""
-        out = {"stem.weight": self.backbone.stem_w.float().cpu(), "stem.bias": self.backbone.stem_b.float().cpu()}
-        frozen = [l for st in self.backbone.stages for b in st for l in b.layers() if not l.trainable]
-        for l in self.layers + frozen:
-            out[l.name + ".weight"] = l.w_bf16.float().cpu()
-            if l.has_bias:
-                out[l.name + ".bias"] = l.bias_f32.float().cpu()
-        for l in getattr(self, "norm_layers", ()):
-            for name, idx in l.named_params():
-                out[name] = self.arena.view(idx, "w").float().cpu()
-        return out
-
-    # ---- checkpoints (SURVEY.md section 8f rank 1): MXNet NDArray-list container, MXNet tensor layouts ----
-
-    def _named_tensors(self):
-        """(name, kind, tensor, layer) of every stored parameter: trainable master weights (fp32 arena views), frozen
-        filters (bf16) and folded frozen-BN shifts (fp32). layer is the owning ConvLayer (None for the stem)."""
-        out = [("stem.weight", "frozen", self.backbone.stem_w, None), ("stem.bias", "frozen", self.backbone.stem_b, None)]
-        frozen = [l for st in self.backbone.stages for b in st for l in b.layers() if not l.trainable]
-        seen = set()
-        for l in list(self.layers) + frozen:
-            if id(l) in seen:
-                continue
-            seen.add(id(l))
-            if l.trainable:
-                out.append((l.name + ".weight", "w", self.arena.view(l.wi, "w"), l))
-                if l.train_bias:
-                    out.append((l.name + ".bias", "w", self.arena.view(l.bi, "w"), l))
-                elif l.has_bias:
-                    out.append((l.name + ".bias", "frozen", l.frozen_bias, l))
-            else:
-                out.append((l.name + ".weight", "frozen", l.w_bf16, l))
-                if l.has_bias:
-                    out.append((l.name + ".bias", "frozen", l.bias_f32, l))
-        for l in getattr(self, "norm_layers", ()):       # 1-D fp32 arrays under their own names (layer None: stored as is)
-            for name, idx in l.named_params():
-                out.append((name, "w", self.arena.view(idx, "w"), None))
-        return out
-
-    @staticmethod
-    def _to_mx(t, layer):
-        """This repo's tensor -> the array MXNet stores for the same parameter: alignment-padding output channels
-        (rows past cout_real: fused / padded head outputs) are dropped; convolution filters [O,KH,KW,I] -> OIHW;
-        fully connected layers (`fc_in_hwc` set: a 1x1 'convolution' over flattened features) -> 2-D [O, I], with the
-        input axis reordered from this repo's (H, W, C) flatten to MXNet's (C, H, W) when the input was spatial."""
-        real = layer.cout_real if layer is not None else t.shape[0]
-        t = t[:real].float()
-        if t.dim() == 4:
-            hwc = getattr(layer, "fc_in_hwc", None) if layer is not None else None
-            khwc = getattr(layer, "dcn_khwc", None) if layer is not None else None
-            if khwc is not None:          # deformable filter held as [O,1,1,9C]: stored as the 3x3 filter it is (OIHW)
-                t = t.reshape(t.shape[0], *khwc).permute(0, 3, 1, 2)
-            elif hwc is not None:
-                O = t.shape[0]
-                if len(hwc) == 3:
-                    t = t.reshape(O, *hwc).permute(0, 3, 1, 2)
-                t = t.reshape(O, -1)
-            else:
-                t = t.permute(0, 3, 1, 2)
-        return t.contiguous().cpu().numpy()
-
-    @staticmethod
-    def _from_mx(a, like, layer):
-        """Inverse of _to_mx onto a tensor shaped like `like` (padding channels zero)."""
-        src = torch.from_numpy(a).to(like.device)
-        if like.dim() == 4:
-            hwc = getattr(layer, "fc_in_hwc", None) if layer is not None else None
-            if getattr(layer, "dcn_khwc", None) is not None:
-                src = src.permute(0, 2, 3, 1).reshape(src.shape[0], *like.shape[1:])
-            elif hwc is not None:
-                O = src.shape[0]
-                if len(hwc) == 3:
-                    src = src.reshape(O, hwc[2], hwc[0], hwc[1]).permute(0, 2, 3, 1)
-                src = src.reshape(O, 1, 1, -1)
-            else:
-                src = src.permute(0, 2, 3, 1)
-        out = torch.zeros(like.shape, dtype=torch.float32, device=like.device)
-        assert tuple(src.shape[1:]) == tuple(like.shape[1:]) and src.shape[0] <= like.shape[0], \
-            "checkpoint %s vs model %s" % (tuple(src.shape), tuple(like.shape))
-        out[:src.shape[0]] = src
-        return out
-
-    def save_checkpoint(self, path):
-        """Write every parameter ("arg:<name>", fp32, in the layout MXNet keeps it in: convolution filters OIHW, fully
-        connected weights 2-D [out, C*H*W], alignment padding stripped -- see _to_mx) and the SGD momentum of the
-        trainable ones ("aux:momentum:<name>") as an MXNet 1.3.0 `.params` file (utils/params_io.py). The byte layout
-        of the container is this repo's reading of MXNet's NDArray::Save; no MXNet-written file exists here to pin it."""
-        from ...utils import save_params
-        blob = {}
-        by_name = {}
-        for name, kind, t, layer in self._named_tensors():
-            blob["arg:" + name] = self._to_mx(t, layer)
-            by_name[name] = layer
-        for i, e in enumerate(self.arena.entries):
-            blob["aux:momentum:" + e[0]] = self._to_mx(self.arena.view(i, "m"), by_name.get(e[0]))
-        save_params(path, blob)
-
-    def load_checkpoint(self, path, strict=True):
-        """Inverse of save_checkpoint; refreshes the bf16 / transposed working copies. Returns the names not found."""
-        from ...utils import load_params
-        blob = load_params(path)
-        missing = []
-        by_name = {}
-        for name, kind, t, layer in self._named_tensors():
-            by_name[name] = layer
-            a = blob.get("arg:" + name)
-            if a is None:
-                missing.append(name)
-                continue
-            t.copy_(self._from_mx(a, t, layer).to(t.dtype))
-        for i, e in enumerate(self.arena.entries):
-            a = blob.get("aux:momentum:" + e[0])
-            if a is not None:
-                m = self.arena.view(i, "m")
-                m.copy_(self._from_mx(a, m, by_name.get(e[0])))
-        if strict and missing:
-            raise KeyError("checkpoint lacks %d parameters, e.g. %s" % (len(missing), missing[:3]))
-        self.arena.refresh_bf16()
-        self.refresh_transposed()
-        return missing
-
-    def export_grads(self):
-        """name -> fp32 CPU gradient of every trainable parameter."""
-        return {e[0]: self.arena.view(i, "g").float().cpu() for i, e in enumerate(self.arena.entries)}
-
-    def num_params(self):
-        return sum(e[3] for e in self.arena.entries)
+        # arena offsets after each backbone stage (layer4, layer3, layer2) for bucketed all-reduce
+        self.stage_marks = {}
+        for si in (3, 2, 1):
+            last = self.backbone.stages[si][0].layers()[-1]
+            e = self.arena.entries[last.wi]
+            self.stage_marks[si] = e[2] + (e[3] + 63) // 64 * 64
 
     def refresh_transposed(self):
         """[Cout,KH,KW,Cin] -> [Cin,KH,KW,Cout] copies for dgrad: one batched launch for all trainable filters."""
@@ -220,37 +101,21 @@ class DetectorBase:
         if self.branch is None:
             yield
             return
-        cur = torch.cuda.current_stream()
-        if not self._cap:
-            self.branch.wait_stream(cur)
-            with torch.cuda.stream(self.branch):
+        if self._rec is not None:
+            with self._rec.branch():
                 yield
             return
-        self.ws.join()
-        self._seg_end()
-        self.segments.append(("fork",))
-        g = torch.cuda.CUDAGraph()
-        self.branch.wait_stream(cur)
+        self.branch.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.branch):
-            # own memory pool: this graph runs concurrently with the main segments, so temporaries allocated while
-            # capturing it must not share (time-multiplexed) memory with theirs
-            g.capture_begin(pool=self._pool_branch, capture_error_mode="thread_local")
             yield
-            g.capture_end()
-        cur.wait_stream(self.branch)
-        self.segments.append(("branch", g))
-        self._seg_begin()
 
     def _join_branch(self):
         if self.branch is None:
             return
-        if not self._cap:
+        if self._rec is not None:
+            self._rec.join_branch()
+        else:
             torch.cuda.current_stream().wait_stream(self.branch)
-            return
-        self.ws.join()            # a segment cannot end with weight-gradient work still forked
-        self._seg_end()
-        self.segments.append(("join",))
-        self._seg_begin()
 
     def enable_data_parallel(self, world_size):
         import torch.distributed as dist
@@ -262,7 +127,7 @@ class DetectorBase:
         self.reducer = BucketReducer(self.arena.g, dist, comm=self.comm)
         # with a gradient exchange the buckets stay fine (five: every all-reduce but the last overlaps the rest of
         # backward); their weight gradients run as side-stream graphs (_reduce), so fine buckets cost nothing here
-        self.bucket_merge = os.environ.get("MXDET_TUNE_BUCKETS", "")
+        self.bucket_merge = "" if self._bucket_env is None else self._bucket_env
 
     def broadcast_parameters(self, root=0):
         """Replicate rank `root`'s master weights (and refresh the bf16 / transposed working copies)."""
@@ -282,7 +147,7 @@ class DetectorBase:
 
     def _guard_replan(self, key):
         """plan() at a new input shape reallocates buffers a captured step holds by address."""
-        if self.segments is not None and self.planned is not None and self.planned != key:
+        if (self.captured is not None or self._rec is not None) and self.planned is not None and self.planned != key:
             raise RuntimeError("the captured training step holds the buffers planned for %s; a call at %s would free "
                                "them (build a second model for another input shape)" % (self.planned, key))
 
@@ -295,9 +160,12 @@ class DetectorBase:
     def _reduce(self, lo, hi, pre=None):
         """Close the gradient bucket [lo, hi). pre: another workspace whose recorded weight gradients belong to this
         bucket and go out first, on the same stream (the RPN head's, when they were not issued inside the branch)."""
-        side_graph = (self._cap and self.dist is not None and hi > lo and self.ws.side is not None and self.ws.grouping
-                      and bool(self.ws.pending) and os.environ.get("MXDET_TUNE_WGRAD_GRAPH", "1") == "1")
-        if not side_graph:
+        rec = self._rec
+        exchange = self.dist is not None and hi > lo
+        # under capture, with a side stream and grouping: the bucket's weight gradients become a side-stream graph
+        # (ScheduleRecorder.close_bucket) instead of being issued here
+        on_side = rec is not None and exchange and self.ws.side is not None and self.ws.grouping and bool(self.ws.pending)
+        if not on_side:
             if pre is not None:
                 pre.side = self.ws.side
                 pre.flush()
@@ -307,56 +175,37 @@ class DetectorBase:
                 # exchange the bucket's update follows its weight gradients ON the side stream and the main stream never
                 # waits (optimizer_step / segment ends join the side stream).
                 self.ws.join()
-        if self._cap:
-            if self.dist is not None and hi > lo and side_graph:
-                # No cut of the main graph: an event-record NODE marks the point where this bucket's dy / x exist, and the
-                # bucket's weight gradients (a graph of their own, replayed on the side stream behind that event), its
-                # all-reduce (issued from the side stream, behind them) and its update (a graph on the optimizer stream,
-                # behind the all-reduce's ticket) never touch the main stream. The two small graphs are captured after
-                # the main capture (_capture_deferred): the recorded weight-gradient calls are stashed here. (Before, the
-                # main stream was cut into a segment per bucket and every cut was a 14-32 us hole: -2.9 % at world 1.)
-                from ...utils.hipgraph import GraphEvent
-                k = len(self._buckets)
-                self._buckets.append((lo, hi))
-                ev = GraphEvent()
-                ev.record_node()
-                mw = ["wgrad", None, ev]
-                items_pre = []
-                if pre is not None:
-                    items_pre, pre.pending = pre.pending, []
-                items, self.ws.pending = self.ws.pending, []
-                self._deferred.append(("wgrad", mw, pre, items_pre, items))
-                self._seg_markers.append(mw)
-                self._seg_markers.append(("reduce", lo, hi, k, True))
-                if self._cap_opt is not None:
-                    mu = ["update", None, k]
-                    self._deferred.append(("update", mu, lo, hi))
-                    self._seg_markers.append(mu)
-            elif self.dist is not None and hi > lo:   # no side stream: cut the graph here, the all-reduce runs between segments
-                self._seg_end()
-                k = len(self._buckets)
-                self._buckets.append((lo, hi))
-                self.segments.append(("reduce", lo, hi, k, False))
-                if self._cap_opt is not None:
-                    # The bucket's update is a small graph of its own, replayed on the optimizer stream once that
-                    # stream has waited for the bucket's all-reduce: it overlaps the rest of backward exactly like
-                    # the single-GPU path, and the main stream never waits for a collective before the end of the step.
-                    g = torch.cuda.CUDAGraph()
-                    cur = torch.cuda.current_stream()
-                    self.opt_stream.wait_stream(cur)
-                    with torch.cuda.stream(self.opt_stream):
-                        g.capture_begin(pool=self._pool_opt, capture_error_mode="thread_local")
-                        self._apply_update(lo, hi, self._cap_opt, 1.0 / self.world)
-                        g.capture_end()
-                    cur.wait_stream(self.opt_stream)
-                    self.segments.append(("update", g, k))
-                self._seg_begin()
+        if rec is not None:
+            if exchange:
+                rec.close_bucket(lo, hi, pre, on_side)
         else:
             self.reducer.reduce(lo, hi)
             if hi > lo:
                 self._seen_buckets.add((lo, hi))
         if self._upd is not None and self.dist is None and hi > lo:
             self._update_range(lo, hi)
+
+    def _backbone_backward(self, lo):
+        """Backward of backbone stages 4..2 from dC, closing the gradient buckets that begin at arena offset lo."""
+        for si in (3, 2, 1):
+            self._backbone_stage_backward(si)
+            if si == 1:
+                self._mark_tail()                          # the data-gradient chain ends here
+            if si == 1 or self._bucket_here(5 - si):       # reduce points 2 (layer4), 3 (layer3); layer2 always closes
+                self._reduce(lo, self.stage_marks[si])
+                lo = self.stage_marks[si]
+
+    def _backbone_stage_backward(self, si):
+        stage = self.backbone.stages[si]
+        ds = self.dC[si]
+        for bi in reversed(range(len(stage))):
+            b = stage[bi]
+            if bi > 0:
+                ds = b.backward(ds, b._buf("dx", b.x.shape), False)
+            elif b.need_dx:
+                b.backward(ds, self.dC[si - 1], True)
+            else:
+                b.backward(ds, None, False)
 
     def _update_range(self, lo, hi):
         """SGD-momentum update + bf16 / transposed working copies of one finished bucket, on the weight-gradient stream:
@@ -390,36 +239,20 @@ class DetectorBase:
 
     # ---- hipGraph capture of the whole step (static shapes): removes ~450 host launches per step ----
 
-    def _seg_begin(self):
-        self._cur_graph = torch.cuda.CUDAGraph()
-        # thread_local: HIP calls of other threads (RCCL's watchdog, loader workers) must not invalidate the capture
-        self._cur_graph.capture_begin(pool=self._pool, capture_error_mode="thread_local")
+    @contextlib.contextmanager
+    def _weights_restored(self):
+        """Eager steps run in the body plan shapes and allocate buffers only: parameters, momentum and the bf16 /
+        transposed working copies are put back afterwards."""
+        snap = (self.arena.w.clone(), self.arena.m.clone())
+        yield
+        torch.cuda.synchronize()
+        self.arena.w.copy_(snap[0])
+        self.arena.m.copy_(snap[1])
+        self.arena.refresh_bf16()
+        self.refresh_transposed()
+        del snap
+        torch.cuda.synchronize()
 
-    def _seg_end(self):
-        """Close the current segment. A segment in which nothing was launched (the step opens with a fork to the branch
-        stream) is dropped instead of being replayed as an empty graph every step; torch reports that case with a
-        warning at capture_end, which is the only place the node count is visible from Python."""
-        with warnings.catch_warnings(record=True) as rec:
-            warnings.simplefilter("always")
-            self._cur_graph.capture_end()
-        empty = False
-        for w in rec:
-            if "Graph is empty" in str(w.message):
-                empty = True
-            else:
-                warnings.warn_explicit(w.message, w.category, w.filename, w.lineno)
-        if not empty:
-            self.segments.append(self._cur_graph)
-            self.segments.extend(self._seg_markers)      # bucket markers recorded inside this segment: handled after its launch
-            self._seg_markers = []
-        else:
-            assert not self._seg_markers, "bucket markers in an empty graph segment"
-            # kept alive, never replayed: destroying the only graph of a memory pool releases the pool, and the next
-            # capture_begin on it trips an allocator assertion
-            self._empty_graphs.append(self._cur_graph)
-        self._cur_graph = None
-
-    # ---- hipGraph capture of the whole step (static shapes): removes ~450 host launches per step ----
     def capture(self, image, gt_boxes, im_info, lr, image_offset=0, warmup=2, gt_masks=None, momentum=0.9, wd=1e-4):
         """Capture forward+backward+update into hipGraph segments (cut only at gradient all-reduces).
         The RNG step counter is read from device memory (step_dev), inputs from static buffers. momentum / wd are
@@ -433,29 +266,17 @@ class DetectorBase:
         self.step_dev = torch.zeros((1,), dtype=torch.int32, device=dev)
         self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=dev)   # replay(lr=...) rewrites it
         self._lr_host = lr
-        snap = (self.arena.w.clone(), self.arena.m.clone()) if warmup > 0 else None
-        for i in range(warmup):     # eager warm-up: plans shapes and allocates every buffer
-            self.train_step(*self.static_in, step=i, image_offset=image_offset, lr=lr, gt_masks=self.static_masks,
+
+        def eager_step(step):
+            self.train_step(*self.static_in, step=step, image_offset=image_offset, lr=lr, gt_masks=self.static_masks,
                             momentum=hyper[0], wd=hyper[1])
+        if warmup > 0:
+            with self._weights_restored():
+                for i in range(warmup):     # eager warm-up: plans shapes and allocates every buffer
+                    eager_step(i)
         torch.cuda.synchronize()
-        if snap is not None:
-            self.arena.w.copy_(snap[0])
-            self.arena.m.copy_(snap[1])
-            self.arena.refresh_bf16()
-            self.refresh_transposed()
-            del snap
-            torch.cuda.synchronize()
-        self._pool = torch.cuda.graph_pool_handle()
-        self._pool_branch = torch.cuda.graph_pool_handle()
-        self._pool_opt = torch.cuda.graph_pool_handle()
-        self._pool_w = torch.cuda.graph_pool_handle()
-        self.segments = []
-        self._empty_graphs = []
-        self._buckets = []
-        self._seg_markers = []
-        self._deferred = []
-        self._cap_opt = None
-        self._final_join_opt = False
+        cap = CapturedStep()
+        update_hyper = None       # (lr, momentum, wd) of per-bucket update graphs (N > 1)
         if self.dist is not None and self._seen_buckets:
             # buckets seen in the eager warm-up: their transpose tables are built here, outside any capture
             # The per-bucket updates get no stream of their own when the RPN branch has one: HIP multiplexes streams onto
@@ -464,107 +285,56 @@ class DetectorBase:
             # 375 vs 422 img/s for the schedule without an exchange). The branch stream is idle by the time the first
             # bucket closes (the branch is joined before the RoI backward) and must wait for the updates anyway before
             # the next step's RPN branch reads the weights.
-            self.opt_stream = self.branch if (self.branch is not None and os.environ.get("MXDET_TUNE_OPT_STREAM", "branch") == "branch") \
-                else torch.cuda.Stream()
-            self._cap_opt = (self.lr_dev,) + hyper
+            self.opt_stream = self.branch if self.branch is not None else torch.cuda.Stream()
+            update_hyper = (self.lr_dev,) + hyper
             for lo_hi in sorted(self._seen_buckets):
                 self._transpose_table(*lo_hi)
-        use_front = self.front_pipeline and self.backbone.frozen_front() > 0 and warmup > 0
+        # exactly one frozen stage: with more, forward_rest has no C2 to hand to the FPN under front_override
+        use_front = self.front_pipeline and self.backbone.frozen_front() == 1 and warmup > 0
         if use_front:
-            from ...utils.hipgraph import GraphEvent
             # the second output buffer of the front end and every plan keyed by it (grouped launches of the consumers)
             # must exist before a capture: one more eager step on parity 1
-            snap = (self.arena.w.clone(), self.arena.m.clone())
-            self.backbone.eager_parity = 1
-            self.train_step(*self.static_in, step=0, image_offset=image_offset, lr=lr, gt_masks=self.static_masks,
-                            momentum=hyper[0], wd=hyper[1])
-            self.backbone.eager_parity = 0
-            torch.cuda.synchronize()
-            self.arena.w.copy_(snap[0])
-            self.arena.m.copy_(snap[1])
-            self.arena.refresh_bf16()
-            self.refresh_transposed()
-            del snap
-            torch.cuda.synchronize()
-            self._tail_event = GraphEvent()
-            fstream = self.branch if self.branch is not None else torch.cuda.Stream()
-            if (self.dist is not None and getattr(self.reducer, "comm", None) is not None
-                    and os.environ.get("MXDET_TUNE_FRONT_PROBE", "1") == "1"):
-                fstream = self._stream_clear_of_the_exchange(fstream)
-            self._front = {"graphs": [], "segments": [], "losses": [], "stream": fstream, "count": 0,
-                           "ready": [torch.cuda.Event(), torch.cuda.Event()], "pool": torch.cuda.graph_pool_handle()}
+            with self._weights_restored():
+                self.backbone.eager_parity = 1
+                eager_step(0)
+                self.backbone.eager_parity = 0
+            cap.tail_event = GraphEvent()
+            cap.front_stream = self.branch if self.branch is not None else torch.cuda.Stream()
+            if self.dist is not None and getattr(self.reducer, "comm", None) is not None and self.front_probe:
+                cap.front_stream = self._stream_clear_of_the_exchange(cap.front_stream)
+        cur = torch.cuda.current_stream()
         side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
+        side.wait_stream(cur)
         for parity in ((0, 1) if use_front else (0,)):
+            front = None
             if use_front:
                 # the front end of this parity: its own graph, captured on the front stream
-                fs = self._front["stream"]
-                fs.wait_stream(torch.cuda.current_stream())
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.stream(fs):
-                    g.capture_begin(pool=self._front["pool"], capture_error_mode="thread_local")
+                cap.front_stream.wait_stream(cur)
+                front = torch.cuda.CUDAGraph()
+                with torch.cuda.stream(cap.front_stream):
+                    begin_capture(front, cap.pool_front)
                     c2 = self.backbone.forward_front(self.static_in[0], parity)
-                    g.capture_end()
-                torch.cuda.current_stream().wait_stream(fs)
-                self._front["graphs"].append(g)
+                    front.capture_end()
+                cur.wait_stream(cap.front_stream)
                 self.backbone.front_override = c2
-                self.segments = []
-                self._buckets = []
-                self._final_join_opt = False
             with torch.cuda.stream(side):
-                self._cap = True
-                self._seg_begin()
+                self._rec = ScheduleRecorder(self, cap, update_hyper)
+                self._rec.seg_begin()
                 self._upd, self._upd_done = (((self.lr_dev,) + hyper) if self.dist is None else None), []
                 losses = self.forward_backward(*self.static_in, step=0, image_offset=image_offset, step_dev=self.step_dev,
                                                gt_masks=self.static_masks)
                 self._upd = None
                 self.optimizer_step(self.lr_dev, hyper[0], hyper[1])
-                self._seg_end()
-                if self._final_join_opt:
-                    self.segments.append(("join_opt",))
-                self._cap = False
-                self._capture_deferred()
-            if use_front:
-                self._front["segments"].append(self.segments)
-                self._front["losses"].append(losses)
+                self._rec.finish(front, losses)        # detaches itself
         self.backbone.front_override = None
-        torch.cuda.current_stream().wait_stream(side)
+        cur.wait_stream(side)
         torch.cuda.synchronize()
         if use_front:
-            self._tail_event.record()            # the first replayed step has no predecessor to wait for
+            cap.tail_event.record()            # the first replayed step has no predecessor to wait for
             torch.cuda.synchronize()
-        self.static_losses = losses
+        self.captured = cap
 
-    def _capture_deferred(self):
-        """The per-bucket weight-gradient and update graphs of the exchange schedule, captured after the main capture (their
-        places in the schedule are the event nodes / markers _reduce left in it)."""
-        todo, self._deferred = self._deferred, []
-        for d in todo:
-            if d[0] == "wgrad":
-                _, marker, pre, items_pre, items = d
-                g = torch.cuda.CUDAGraph()
-                side, self.ws.side = self.ws.side, None
-                with torch.cuda.stream(side):
-                    g.capture_begin(pool=self._pool_w, capture_error_mode="thread_local")
-                    if pre is not None:
-                        pre.side = None
-                        pre.pending = items_pre
-                        pre.flush()
-                    self.ws.pending = items
-                    self.ws.flush()
-                    g.capture_end()
-                self.ws.side = side
-                marker[1] = g
-            else:
-                _, marker, lo, hi = d
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.stream(self.opt_stream):
-                    g.capture_begin(pool=self._pool_opt, capture_error_mode="thread_local")
-                    self._apply_update(lo, hi, self._cap_opt, 1.0 / self.world)
-                    g.capture_end()
-                marker[1] = g
-
-    def _stream_clear_of_the_exchange(self, preferred, tries=4):
+    def _stream_clear_of_the_exchange(self, preferred):
         """A stream on which work is NOT held up while an all-reduce waits for its bucket's weight gradients.
 
         HIP multiplexes streams onto a few hardware queues (four), in order of first use, and a stream that waits for an
@@ -579,7 +349,7 @@ class DetectorBase:
         import time
         comm = self.reducer.comm
         dev = self.arena.g.device
-        tries = int(os.environ.get("MXDET_TUNE_FRONT_PROBE_TRIES", tries))
+        tries = self.front_probe_tries
         while len(_PROBE_STREAMS) < tries:             # one set per process: every model's probe tries the same streams
             _PROBE_STREAMS.append(torch.cuda.Stream())
         cands = [preferred] + _PROBE_STREAMS[:tries]
@@ -624,80 +394,43 @@ class DetectorBase:
         """Called by forward_backward where the data-gradient chain has ended and only the last bucket's weight gradients,
         fold and update remain: under capture with the front-end pipeline, an event-record node the NEXT step's front end
         waits for (it then runs beside that tail: HBM-bound frozen convolutions next to MFMA-bound weight gradients)."""
-        if self._cap and self._front is not None and self._tail_event is not None:
-            self._tail_event.record_node()
+        if self._rec is not None and self._rec.cap.tail_event is not None:
+            self._rec.cap.tail_event.record_node()
 
     def replay(self, image, gt_boxes, im_info, step, gt_masks=None, lr=None):
         """One training step from the captured graphs; lr (if given) replaces the captured learning rate from here on."""
         si = self.static_in
+        cap = self.captured
         if lr is not None and lr != self._lr_host:
             self.lr_dev.fill_(float(lr))
             self._lr_host = lr
-        segments, losses = self.segments, self.static_losses
-        if self._front is not None:
+        if cap.front_stream is not None:
             # front end of THIS batch on the front stream, behind the previous step's tail mark (not behind its end)
-            fr = self._front
-            par = fr["count"] & 1
-            fr["count"] += 1
-            fs = fr["stream"]
-            if os.environ.get("MXDET_TUNE_FRONT_PIPE", "1") != "2":      # "2": no tail gate (as early as the stream allows)
-                self._tail_event.wait(fs)
-            with torch.cuda.stream(fs):
+            par = cap.count & 1
+            cap.count += 1
+            cap.tail_event.wait(cap.front_stream)
+            with torch.cuda.stream(cap.front_stream):
                 if image is not si[0]:
                     si[0].copy_(image, non_blocking=True)
                 if "front" not in _ABL:
-                    fr["graphs"][par].replay()
-                fr["ready"][par].record()
-            torch.cuda.current_stream().wait_event(fr["ready"][par])
-            segments, losses = fr["segments"][par], fr["losses"][par]
-        elif image is not si[0]:
-            si[0].copy_(image, non_blocking=True)
+                    cap.parities[par].front.replay()
+                cap.ready[par].record()
+            torch.cuda.current_stream().wait_event(cap.ready[par])
+            captured = cap.parities[par]
+        else:
+            captured = cap.parities[0]
+            if image is not si[0]:
+                si[0].copy_(image, non_blocking=True)
         if image is not si[0]:
             si[1].copy_(gt_boxes, non_blocking=True)
             si[2].copy_(im_info, non_blocking=True)
             if gt_masks is not None:
                 self.static_masks.copy_(gt_masks, non_blocking=True)
         self.step_dev.fill_(step)
-        fork_ev = None
-        handles = {}
-        for seg in segments:
-            if isinstance(seg, (tuple, list)):
-                if seg[0] == "wgrad":
-                    seg[2].wait(self.ws.side)                 # the event node behind the producers of the bucket's dy / x
-                    with torch.cuda.stream(self.ws.side):
-                        seg[1].replay()
-                elif seg[0] == "reduce":
-                    if len(seg) > 4 and seg[4]:               # ordered behind the side stream's weight gradients
-                        with torch.cuda.stream(self.ws.side):
-                            h = self.reducer.reduce(seg[1], seg[2])
-                    else:
-                        h = self.reducer.reduce(seg[1], seg[2])
-                    if len(seg) > 3:
-                        handles[seg[3]] = h
-                elif seg[0] == "update":
-                    with torch.cuda.stream(self.opt_stream):
-                        for h in handles.get(seg[2], ()):
-                            h.wait()                       # orders the optimizer stream after the bucket's sums
-                        seg[1].replay()
-                elif seg[0] == "join_opt":
-                    torch.cuda.current_stream().wait_stream(self.opt_stream)
-                    if self.ws.side is not None:
-                        torch.cuda.current_stream().wait_stream(self.ws.side)
-                    self.reducer.pending, self.reducer.log = [], []
-                elif seg[0] == "fork":
-                    fork_ev = torch.cuda.Event()
-                    fork_ev.record()
-                elif seg[0] == "branch":
-                    self.branch.wait_event(fork_ev)
-                    with torch.cuda.stream(self.branch):
-                        seg[1].replay()
-                elif seg[0] == "join":
-                    torch.cuda.current_stream().wait_stream(self.branch)
-                else:
-                    self.reducer.wait()
-            else:
-                seg.replay()
-        return losses
+        scratch = ReplayScratch()
+        for entry in captured.schedule:
+            entry.run(self, scratch)
+        return captured.losses
 
     def optimizer_step(self, lr, momentum=0.9, wd=1e-4):
         self.ws.flush()
@@ -705,44 +438,24 @@ class DetectorBase:
         done, self._upd_done = self._upd_done, []
         if done:
             # buckets were updated as they finished; update whatever the bucket marks did not cover
-            covered = sorted(done)
-            gaps, pos = [], 0
-            for lo, hi in covered:
-                if lo > pos:
-                    gaps.append((pos, lo))
-                pos = max(pos, hi)
-            if pos < self.arena.size:
-                gaps.append((pos, self.arena.size))
             self._upd = (lr, momentum, wd)
-            for lo, hi in gaps:
+            for lo, hi in uncovered_ranges(done, self.arena.size):
                 self._update_range(lo, hi)
             self._upd = None
             self.ws.join()
             return
-        if self._cap and self.dist is not None and self._cap_opt is not None:
-            pos = 0
-            for lo, hi in sorted(self._buckets):
-                assert lo <= pos, "parameter range [%d, %d) belongs to no gradient bucket" % (pos, lo)
-                pos = max(pos, hi)
-            assert pos >= self.arena.size, "parameter range [%d, %d) belongs to no gradient bucket" % (pos, self.arena.size)
-            self._final_join_opt = True      # every bucket has its own update graph; capture() appends the join
-            return
-        if self._cap:
-            if self.dist is not None:
-                self._seg_end()
-                self.segments.append(("wait",))
-                self._seg_begin()
-        else:
+        if self._rec is None:
             self.reducer.wait()
-        rescale = 1.0 / self.world
-        self.arena.sgd_step(lr, momentum, wd, rescale)
+        elif self.dist is not None and self._rec.end_exchange():
+            return                               # every bucket has its own update graph
+        self.arena.sgd_step(lr, momentum, wd, 1.0 / self.world)
         self.refresh_transposed()
 
     def train_step(self, image, gt_boxes, im_info, step=0, image_offset=0, lr=0.0025, gt_masks=None,
                    momentum=0.9, wd=1e-4):
         self._upd, self._upd_done = ((lr, momentum, wd) if self.dist is None else None), []
         from ...ops import dense
-        trace = not getattr(self, "_pf_wired", False) and os.environ.get("MXDET_TUNE_PREFETCH", "1") != "0"
+        trace = not getattr(self, "_pf_wired", False) and self.prefetch != "0"
         if trace:
             dense.PF_TRACE = []
         try:
@@ -769,7 +482,7 @@ class DetectorBase:
                 layer.pf_fwd = nxt
             elif kind == "b":
                 layer.pf_bwd = nxt
-            elif key is not None and os.environ.get("MXDET_TUNE_PREFETCH", "1") != "2":
+            elif key is not None and self.prefetch != "2":
                 dense.GROUP_HINTS[key] = nxt     # grouped launch: its table is rebuilt with the hint at the next eager call
                 dense._group_plans.pop(key, None)
         self._pf_wired = True

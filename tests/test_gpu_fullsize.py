@@ -260,7 +260,7 @@ def test_full_size_exchange_schedule_over_rccl_world1(hip):
         m.capture(img, gt, info, lr=lr)
         losses = torch.cat(m.replay(img, gt, info, 0)).clone()
         torch.cuda.synchronize()
-        nb = len(m._buckets)
+        nb = len(m.captured.buckets)
         if parallel:
             m.comm.close()
         return w0, m.arena.w.clone(), losses, nb

@@ -164,7 +164,7 @@ def test_front_end_pipeline_follows_the_batches(hip):
     m.ws.join()
     torch.cuda.synchronize()
     m.capture(*batches[0], lr=0.0, image_offset=0, warmup=1)
-    assert m._front is not None and len(m._front["graphs"]) == 2          # the pipeline is on: two parities were captured
+    assert [p.front is not None for p in m.captured.parities] == [True, True]   # the pipeline is on: two parities were captured
     for it, k in enumerate((1, 2, 0, 0, 2, 1, 1)):
         got = torch.cat(m.replay(*batches[k], 7)).clone()
         torch.cuda.synchronize()
@@ -178,10 +178,12 @@ def test_front_end_pipeline_follows_the_batches(hip):
         assert torch.allclose(ref[k], got, rtol=1e-4, atol=1e-5), (k, ref[k], got)
 
 
-def test_gradient_exchange_path_matches_single_gpu_step(hip):
+@pytest.mark.parametrize("wgrad_stream", [True, False], ids=["side_stream", "cut_form"])
+def test_gradient_exchange_path_matches_single_gpu_step(hip, wgrad_stream):
     """The N > 1 schedule (graph cut at every bucket's all-reduce, per-bucket update graphs on the optimizer stream)
     run at world size 1 over RCCL must take the same step as the single-GPU schedule: same losses, parameters equal up
-    to the fp32-atomic ordering of RoIAlign-backward (1e-5 of the largest update)."""
+    to the fp32-atomic ordering of RoIAlign-backward (1e-5 of the largest update). cut_form: both models without the
+    weight-gradient stream, so every bucket's all-reduce cuts the main graph instead of riding on the side stream."""
     import socket
     import torch
     import torch.distributed as dist
@@ -192,7 +194,8 @@ def test_gradient_exchange_path_matches_single_gpu_step(hip):
 
     def one_step(parallel):
         m = FasterRCNN("cuda", seed=7, pre_nms_top_n=1000, post_nms_top_n=1000)
-        m.enable_wgrad_stream()
+        if wgrad_stream:
+            m.enable_wgrad_stream()
         m.enable_branch_stream()
         m.enable_grouped_wgrad()
         if parallel:
@@ -225,6 +228,63 @@ def test_gradient_exchange_path_matches_single_gpu_step(hip):
     assert torch.allclose(l_single[2:], l_par[2:], rtol=5e-2, atol=1e-2), (l_single, l_par)
     assert (w_single - w_par).abs().max().item() <= 1e-2 * moved
     assert (wb_single - wb_par).abs().max().item() <= 2e-2 * wb_single.abs().max().item()
+
+
+# The captured schedule per configuration, as recorded from the tuple / list protocol of the commit before the typed schedule
+# (profiles/r05_typed_schedule.txt). Both parities of the front-end pipeline carry the same list.
+_SCHED_HEAD = ["Fork", "Branch", "MainGraph",               # anchor targets on the branch stream | backbone, FPN, RPN head
+               "Fork", "Branch", "MainGraph",               # RPN losses + backward on the branch stream | proposals .. box head
+               "Join", "MainGraph"]                         # dP complete | RoI backward .. end of backward
+SCHEDULES = {
+    "single": _SCHED_HEAD,
+    "rccl": _SCHED_HEAD + ["BucketWgrad", "BucketReduce", "BucketUpdate",
+                           "BucketWgrad", "BucketReduce", "BucketUpdate",
+                           "BucketWgrad", "BucketReduce", "BucketUpdate",
+                           "BucketWgrad", "BucketReduce", "BucketUpdate",
+                           "BucketWgrad", "BucketReduce", "BucketUpdate", "JoinUpdates"],
+    "rccl_cut": _SCHED_HEAD + ["BucketReduce", "BucketUpdate", "MainGraph",
+                               "BucketReduce", "BucketUpdate", "MainGraph",
+                               "BucketReduce", "BucketUpdate", "MainGraph",
+                               "BucketReduce", "BucketUpdate", "MainGraph",
+                               "BucketReduce", "BucketUpdate", "JoinUpdates"],
+}
+
+
+@pytest.mark.parametrize("config", ["single", "rccl", "rccl_cut"])
+def test_captured_schedule_shape(hip, config):
+    """capture() records, per parity, exactly the entries the step's streams need: the two forks to the branch stream and
+    their join; with a gradient exchange, five buckets -- as side-stream graphs behind event nodes of the one main graph
+    (rccl), or, without the weight-gradient stream, as cuts of the main graph (rccl_cut) -- and the join of their updates."""
+    import socket
+    import torch
+    import torch.distributed as dist
+    from mxdetection_amd.models import FasterRCNN
+    image, gt, im_info = _inputs(2, 256, 320, seed=3)
+    if config != "single":
+        s = socket.socket()
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+        s.close()
+        dist.init_process_group("nccl", init_method="tcp://127.0.0.1:%d" % port, rank=0, world_size=1)
+    try:
+        m = FasterRCNN("cuda", seed=7, pre_nms_top_n=1000, post_nms_top_n=1000)
+        if config != "rccl_cut":
+            m.enable_wgrad_stream()
+        m.enable_branch_stream()
+        m.enable_grouped_wgrad()
+        if config != "single":
+            m.enable_data_parallel(1)
+        m.capture(image, gt, im_info, lr=0.001, image_offset=0, warmup=1)
+        torch.cuda.synchronize()
+    finally:
+        if config != "single":
+            dist.destroy_process_group()
+    assert len(m.captured.parities) == 2
+    for p in m.captured.parities:
+        assert [type(e).__name__ for e in p.schedule] == SCHEDULES[config]
+        assert [e.on_side for e in p.schedule if type(e).__name__ == "BucketReduce"] == \
+            ([] if config == "single" else [config == "rccl"] * 5)
+    assert len(m.captured.buckets) == (0 if config == "single" else 5)
 
 
 def test_checkpoint_round_trip(hip, tmp_path):
