@@ -607,13 +607,37 @@ int mxdet_filter_transpose_batched(const void* descs_dev, int32_t ndesc, int32_t
  *          order, 32 per MFMA step; needs DT's outputs.
  *   DGRAD  the 3x3 / stride 1 / pad 1 data gradient (wt_conv [C,3,3,C] transposed filter) of dts scattered to its cells,
  *          written to (accumulate[l]: added to) the pixels of dP[l] that have an active cell in their 3x3 neighbourhood,
- *          each once, with the bits mxdet_conv2d_dgrad gives them; other pixels are not touched. */
+ *          each once, with the bits mxdet_conv2d_dgrad gives them; other pixels are not touched.
+ *   WGRAD_ORDERED  the four weight / bias gradients of WGRAD (f32, overwritten) with the BITS of the dense grouped weight
+ *          gradient (mxdet_conv2d_wgrad_grouped) on gh / the DTMAP maps: only the 32-pixel MFMA half-steps that hold an
+ *          active cell are issued, in the dense order, every active pixel at its dense reduction position, a fresh
+ *          accumulator per dense split-K slab and the slab sums added in the dense fold order. Needs DT's outputs,
+ *          `ordered` = the schedule mxdet_rpn_ordered_schedule wrote for this pyramid (host memory, 2 * num_levels
+ *          records: rpn.out's levels, then rpn.conv's) and `ordered_work` (device, 16-byte aligned, at least
+ *          MXDET_RPN_ORDERED_WORK_INTS(smax) i32). One prepass launch re-keys the list into the dense order, one launch
+ *          does the rest; an Inf / NaN of P or t beside a zero gradient row is NOT propagated (the dense kernels give NaN). */
 #define MXDET_RPN_SPARSE_MAX_LEVELS 8
 #define MXDET_RPN_SPARSE_ZERO 1
 #define MXDET_RPN_SPARSE_DT 2
 #define MXDET_RPN_SPARSE_WGRAD 4
 #define MXDET_RPN_SPARSE_DGRAD 8
 #define MXDET_RPN_SPARSE_DTMAP 16
+#define MXDET_RPN_SPARSE_WGRAD_ORDERED 32
+#define MXDET_RPN_ORDERED_WORK_INTS(smax) (10 * (smax) + 32)
+/* The dense split-K order of one item (one level of one filter) of a grouped weight-gradient plan. The kernels read kind,
+ * H, W, halves_per_slab and bias_pixels and add the slabs in ITEM order; slab0, fold_ksplit and bias_splits record where the
+ * plan put the item's slabs in its filter's run: the launch only checks that they follow the item order (slab0 ascending
+ * from 0, below fold_ksplit), which mxdet_rpn_ordered_schedule guarantees for the plans it accepts. */
+typedef struct {
+  int32_t kind;          /* 0: one-tap tile, reduction over the real pixels (n*H + h)*W + w; 1: three-tap tile, over
+                            the virtual pixels (n*H + h)*(W + 1) + w */
+  int32_t H, W;
+  int32_t halves_per_slab;   /* 32-pixel MFMA half-steps per split (slab) */
+  int32_t slab0;         /* the item's first slab in its filter's run of slabs */
+  int32_t fold_ksplit;   /* slabs in the run (the fold adds them in index order) */
+  int32_t bias_pixels;   /* real pixels per split of the bias sums; split ks is slab slab0 + ks of the bias run */
+  int32_t bias_splits;
+} mxdet_rpn_ordered_item_t;
 typedef struct {
   int32_t num_levels, N, A, C, Ch, smax;
   int32_t H[MXDET_RPN_SPARSE_MAX_LEVELS], W[MXDET_RPN_SPARSE_MAX_LEVELS];
@@ -624,6 +648,8 @@ typedef struct {
   const void* gh[MXDET_RPN_SPARSE_MAX_LEVELS];     /* bf16 [N,H,W,Ch]: d(loss)/d(head output) */
   void* dP[MXDET_RPN_SPARSE_MAX_LEVELS];           /* bf16 [N,H,W,C] */
   void* dt[MXDET_RPN_SPARSE_MAX_LEVELS];           /* bf16 [N,H,W,C] or NULL (DTMAP) */
+  const mxdet_rpn_ordered_item_t* ordered;         /* host, [2 * num_levels] or NULL (WGRAD_ORDERED) */
+  void* ordered_work;                              /* device i32 scratch or NULL (WGRAD_ORDERED) */
 } mxdet_rpn_sparse_t;
 int mxdet_rpn_sparse_list(const mxdet_rpn_sparse_t* d, const int32_t* labels, int32_t* list, int32_t* state,
                           int32_t* map, mxdet_stream_t stream);
@@ -631,6 +657,11 @@ int mxdet_rpn_sparse_backward(const mxdet_rpn_sparse_t* d, const int32_t* list, 
                               const int32_t* map, const uint16_t* wt_out, const uint16_t* wt_conv, uint16_t* dts,
                               uint16_t* ghs, float* dw_out, float* db_out, float* dw_conv, float* db_conv,
                               int32_t parts, mxdet_stream_t stream);
+/* The schedule of WGRAD_ORDERED from the HOST table mxdet_conv2d_wgrad_grouped_plan wrote for the head's 2 * num_levels
+ * items (rpn.out on (t[l], gh[l]) for every level, then rpn.conv on (P[l], dt[l]); no accumulate): the split parameters
+ * are read off that plan, never derived a second time. MXDET_EINVAL when the items are not two filters of num_levels
+ * levels each whose slabs follow the item order. */
+int mxdet_rpn_ordered_schedule(const void* table_host, int32_t n, int32_t num_levels, mxdet_rpn_ordered_item_t* items);
 
 /* Deformable convolution (DCN v1 / v2), MXNet role contrib.DeformableConvolution (Deformable-ConvNets'
  * deformable_im2col semantics; dilation 1, 3x3 kernels only: anything else is MXDET_ESHAPE).

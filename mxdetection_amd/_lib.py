@@ -82,11 +82,18 @@ class GnDescT(C.Structure):
                 ("accumulate", c_i32)]
 
 
+class RpnOrderedItemT(C.Structure):
+    """mxdet_rpn_ordered_item_t (include/mxdet.h)."""
+    _fields_ = [("kind", c_i32), ("H", c_i32), ("W", c_i32), ("halves_per_slab", c_i32), ("slab0", c_i32),
+                ("fold_ksplit", c_i32), ("bias_pixels", c_i32), ("bias_splits", c_i32)]
+
+
 class RpnSparseT(C.Structure):
     """mxdet_rpn_sparse_t (include/mxdet.h)."""
     _fields_ = [("num_levels", c_i32), ("N", c_i32), ("A", c_i32), ("C", c_i32), ("Ch", c_i32), ("smax", c_i32),
                 ("H", c_i32 * 8), ("W", c_i32 * 8), ("accumulate", c_i32 * 8),
-                ("P", c_vp * 8), ("t", c_vp * 8), ("tbits", c_vp * 8), ("gh", c_vp * 8), ("dP", c_vp * 8), ("dt", c_vp * 8)]
+                ("P", c_vp * 8), ("t", c_vp * 8), ("tbits", c_vp * 8), ("gh", c_vp * 8), ("dP", c_vp * 8), ("dt", c_vp * 8),
+                ("ordered", C.POINTER(RpnOrderedItemT)), ("ordered_work", c_vp)]
 
 
 WgradItemT._fields_ = [("desc", ConvDescT), ("x", c_vp), ("dy", c_vp), ("dw", c_vp), ("db", c_vp)]
@@ -193,6 +200,7 @@ SIGNATURES = {
     "mxdet_rpn_sparse_list": (c_i32, [P(RpnSparseT), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mxdet_rpn_sparse_backward": (c_i32, [P(RpnSparseT), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                           c_i32, c_vp]),
+    "mxdet_rpn_ordered_schedule": (c_i32, [c_vp, c_i32, c_i32, P(RpnOrderedItemT)]),
     "mxdet_filter_transpose": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mxdet_filter_transpose_batched": (c_i32, [c_vp, c_i32, c_i32, c_vp]),
     "mxdet_deform_im2col": (c_i32, [P(DeformDescT), c_vp, c_vp, c_vp, c_vp]),

@@ -22,9 +22,13 @@ HEAD_CPAD = 64   # fused cls+reg output channels padded so that dgrad's reductio
 
 RELU_BITS = os.environ.get("MXDET_TUNE_RELU_BITS", "1") == "1"
 # backward over the sampled anchors' cells only (ops/rpn_sparse.py). 0: the dense kernels; 1: sparse
-# data gradients, the dense weight-gradient kernels on a scattered dt map (every result bit-identical to 0); 2: the weight
+# data gradients, weight gradients with the dense bits (RPN_ORDERED below, or the dense kernels on a scattered dt map): every
+# result bit-identical to 0; 2: the weight
 # gradients over the slots as well (faster; they differ from 0 in fp32 summation order)
 RPN_SPARSE = int(os.environ.get("MXDET_TUNE_RPN_SPARSE", "1"))
+# mode 1 with grouped weight gradients: 1 = the weight gradients from the active cells too, in the dense split-K summation
+# order (bit-identical, no dt map); 0 = the dense kernels on the scattered dt map
+RPN_ORDERED = int(os.environ.get("MXDET_TUNE_RPN_ORDERED", "1"))
 
 
 class RPNHead:
@@ -161,8 +165,9 @@ class RPNHead:
         """The same gradients from the active cells alone (assign_targets listed them): dP is cleared where it holds
         nothing yet, then compact rpn.out data-gradient rows and the rpn.conv data gradient of the touched pixels.
         Weight gradients: the dense kernels as in backward(), rpn.conv's on a dt map that holds the listed rows and zeros
-        (same operands bit for bit, so same results); or (sparse_wgrad) sums over the slots straight into the arena,
-        nothing recorded in the workspace."""
+        (same operands bit for bit, so same results); with a grouping workspace (RPN_ORDERED) sums over the active cells in
+        the grouped plan's split-K order instead (same bits again), straight into the arena, nothing recorded in the
+        workspace and no dt map; or (sparse_wgrad) sums over the slots in slot order, also straight into the arena."""
         g = self.out.arena
         grads = (g.view(self.out.wi, "g"), g.view(self.out.bi, "g"), g.view(self.conv.wi, "g"), g.view(self.conv.bi, "g"))
         if self.sparse_wgrad:
@@ -170,6 +175,16 @@ class RPNHead:
             return
         L = len(self.h)
         grouped = self.out.ws.grouping
+        if grouped and RPN_ORDERED and self.out.train_bias and self.conv.train_bias:
+            if self.sparse.ordered is None and not torch.cuda.is_current_stream_capturing():
+                # the ten items flush() would plan, in the order they are recorded below
+                self.sparse.plan_ordered(
+                    [(self.t[l], self.gh[l], 1, 1, 1, 0, grads[0], grads[1], False) for l in range(L)] +
+                    [(self.P[l], self.dt_map[l], 3, 3, 1, 1, grads[2], grads[3], False) for l in range(L)])
+            if self.sparse.ordered is not None:     # (first seen under capture: the dense kernels below)
+                self.sparse.backward(self.P, self.t, self.tbits, self.gh, dP, dP_has_grad, self.out.wt, self.conv.wt, *grads,
+                                     parts=RS.ZERO | RS.DT | RS.DGRAD | RS.WGRAD_ORDERED)
+                return
         for l in range(L):
             self.out.backward_weight(self.t[l], self.gh[l], accumulate=(l > 0) and not grouped)
         self.sparse.backward(self.P, self.t, self.tbits, self.gh, dP, dP_has_grad, self.out.wt, self.conv.wt, *grads,
