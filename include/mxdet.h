@@ -426,6 +426,43 @@ int mxdet_retina_loss_level_iou(const uint16_t* cls, const uint16_t* reg, int32_
                                 float std_w, float std_h, float reg_weight, const int32_t* num_fg, float loss_scale,
                                 uint16_t* grad_cls, uint16_t* grad_reg, float* partial, mxdet_stream_t stream);
 
+/* Quality-aware class losses for the RetinaNet head: QFL (Li et al., NeurIPS 2020) and the IoU-weighted
+ * Varifocal loss (Zhang et al., CVPR 2021). They train the matched class column against the IoU of the predicted box with
+ * its ground truth, so that the test-time score sigmoid(cls) ranks detections by localisation quality.
+ * Per anchor: lab = cls_labels[n, anchor], m = matched_gt[n, anchor], q = the anchor's quality. For lab > 0 and
+ * 0 <= m < G_max, q = inter / union of the decoded prediction against gt_boxes[n, m]: exactly the inter, union of the
+ * IoU-family box losses above (corner-relative decode, "+1" convention, dw / dh clamp, stds by value). Otherwise q = 0.
+ * q is a constant of the class loss: no gradient flows from the class term into the deltas.
+ * Per element (anchor, class c): x the logit, s = sigmoid(x), y = q if lab == c + 1, else 0. With lab < 0 (ignore) every
+ * element contributes 0 and its gradient is 0. BCE(s, y) = -y log s - (1 - y) log(1 - s), in the log forms of the focal loss.
+ *   MXDET_CLS_LOSS_QFL, parameter beta passed in `gamma` (alpha is ignored):
+ *     L = |y - s|^beta * BCE(s, y);  dL/dx = beta |e|^(beta-1) sign(e) s (1 - s) BCE + |e|^beta e, with e = s - y.
+ *     beta = 2 takes the product form, any other beta > 0 mxdet_expf(beta * mxdet_logf(max(|e|, 1e-30f))).
+ *   MXDET_CLS_LOSS_VFL, parameters alpha and gamma:
+ *     y > 0:  L = y * BCE(s, y) and dL/dx = y (s - y);
+ *     else:   L = -alpha s^gamma log(1 - s) and dL/dx = alpha (gamma s^gamma (1 - s) (-log(1 - s)) + s^gamma s).
+ *     A matched anchor whose prediction does not overlap its ground truth (q == 0) is a negative in its own class column.
+ * Both terms are normalised by max(1, *num_fg) and scaled by loss_scale / grad_scale as in the entries above. */
+#define MXDET_CLS_LOSS_QFL 1
+#define MXDET_CLS_LOSS_VFL 2
+/* The unfused primitive, with the contract of mxdet_focal_loss (workspace mxdet_loss_workspace_bytes(n), fixed reduction
+ * order, gradient in the logits dtype, normaliser = max(1, #labels > 0) counted on the device): logits [n,C] (f32 | bf16),
+ * labels[n], quality[n] f32 = the y of row r's column labels[r] - 1. n == 0 writes loss_out[0] = 0 and returns MXDET_OK. */
+int mxdet_quality_focal_loss(const void* logits, int32_t dtype, const int32_t* labels, const float* quality, int64_t n,
+                             int32_t C, int32_t cls_kind, float alpha, float gamma, float grad_scale, float* loss_out,
+                             void* grad_logits, void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
+/* mxdet_retina_loss_level_iou with the class term replaced by cls_kind: the box term (kind, stds, reg_weight), grid,
+ * partial layout and vector / scalar split are that entry's; grad_reg and partial[2i+1] are bit-identical to it. The box
+ * part of a workgroup runs first and hands the 256 qualities to the class walk through LDS: no atomics, no host
+ * synchronisation, capturable; a replay follows new gt_boxes. gamma must be positive. */
+int mxdet_retina_loss_level_quality(const uint16_t* cls, const uint16_t* reg, int32_t N, int32_t H, int32_t W, int32_t A,
+                                    int32_t C, int32_t ld_cls, int32_t ld_reg, const int32_t* cls_labels,
+                                    const float* anchors, const int32_t* matched_gt, const float* gt_boxes, int32_t G_max,
+                                    int64_t A_total, int64_t level_offset, int32_t cls_kind, float alpha, float gamma,
+                                    int32_t kind, float std_x, float std_y, float std_w, float std_h, float reg_weight,
+                                    const int32_t* num_fg, float loss_scale, uint16_t* grad_cls, uint16_t* grad_reg,
+                                    float* partial, mxdet_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * core/mask + mask_heads (README.md:18, :30) -- Mask R-CNN.
  * mask targets: for roi r (batch, box) with matched GT g = matched_gt[r] and class labels[r] > 0, resample the

@@ -147,3 +147,66 @@ def retina_loss_level_iou(cls, reg, A, C, cls_labels, anchors, matched_gt, gt_bo
                                           cls_labels.shape[1], level_offset, alpha, gamma, IOU_LOSS_KINDS[kind], stds[0],
                                           stds[1], stds[2], stds[3], reg_weight, ptr(num_fg), loss_scale, ptr(grad_cls),
                                           ptr(grad_reg), ptr(partial), stream_ptr()), "retina_loss_level_iou")
+
+
+# ---- quality-aware class losses of the RetinaNet head: QFL / Varifocal (include/mxdet.h) ----
+CLS_LOSS_KINDS = _lib.CLS_LOSS_KINDS
+CLS_LOSSES = ("focal",) + tuple(CLS_LOSS_KINDS)
+CLS_LOSS_DEFAULTS = {"qfl": (0.0, 2.0), "vfl": (0.75, 2.0)}        # (alpha, gamma) as published; QFL: beta in gamma, no alpha
+
+
+def check_cls_loss(cls_loss, reg_loss, alpha=None, gamma=None):
+    """The class-loss options of the RetinaNet head, checked before anything is allocated. alpha / gamma None = the kind's
+    published default (focal: the head's own alpha / gamma). Returns (alpha, gamma) for a quality loss, None for focal."""
+    if cls_loss not in CLS_LOSSES:
+        raise ValueError("cls_loss must be one of %s (got %r)" % (", ".join(CLS_LOSSES), cls_loss))
+    for name, v in (("cls_loss_alpha", alpha), ("cls_loss_gamma", gamma)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float))):
+            raise ValueError("%s must be a number or None (got %r)" % (name, v))
+    if gamma is not None and not gamma > 0:
+        raise ValueError("cls_loss_gamma must be positive (got %r)" % (gamma,))
+    if alpha is not None and not 0 <= alpha <= 1:
+        raise ValueError("cls_loss_alpha must lie in [0, 1] (got %r)" % (alpha,))
+    if cls_loss == "focal":
+        return None
+    if reg_loss not in IOU_LOSS_KINDS:
+        raise ValueError("cls_loss = %r needs an IoU-family reg_loss (%s): the quality is the decoded box's IoU, "
+                         "reg_loss = %r decodes none" % (cls_loss, ", ".join(IOU_LOSS_KINDS), reg_loss))
+    a0, g0 = CLS_LOSS_DEFAULTS[cls_loss]
+    return float(a0 if alpha is None else alpha), float(g0 if gamma is None else gamma)
+
+
+def quality_focal_loss(logits, labels, quality, cls_loss="qfl", alpha=None, gamma=None, grad_scale=1.0, workspace=None):
+    """QFL / Varifocal loss fwd+bwd on given qualities. logits [n,C] (f32|bf16), labels [n] i32, quality [n] f32 (the
+    target of row r's column labels[r] - 1). Returns (loss[1] f32, grad like logits)."""
+    lib = _lib.load()
+    if cls_loss not in CLS_LOSS_KINDS:
+        raise ValueError("cls_loss must be one of %s (got %r)" % (", ".join(CLS_LOSS_KINDS), cls_loss))
+    a0, g0 = CLS_LOSS_DEFAULTS[cls_loss]
+    alpha, gamma = (a0 if alpha is None else alpha), (g0 if gamma is None else gamma)
+    n, Cc = logits.shape
+    if workspace is None:
+        workspace = loss_workspace(n, logits.device)
+    loss = torch.empty((1,), dtype=torch.float32, device=logits.device)
+    grad = torch.empty_like(logits)
+    check(lib.mxdet_quality_focal_loss(ptr(logits), _DT[logits.dtype], ptr(labels), ptr(quality), n, Cc,
+                                       CLS_LOSS_KINDS[cls_loss], alpha, gamma, grad_scale, ptr(loss), ptr(grad), ptr(workspace),
+                                       workspace.numel(), stream_ptr()), "quality_focal_loss")
+    return loss, grad
+
+
+def retina_loss_level_quality(cls, reg, A, C, cls_labels, anchors, matched_gt, gt_boxes, level_offset, cls_loss, alpha, gamma,
+                              kind, stds, reg_weight, num_fg, loss_scale, grad_cls, grad_reg, partial):
+    """retina_loss_level_iou with the class term 'qfl' (beta in gamma) or 'vfl' on the decoded box's IoU."""
+    lib = _lib.load()
+    if cls_loss not in CLS_LOSS_KINDS:
+        raise ValueError("cls_loss must be one of %s (got %r)" % (", ".join(CLS_LOSS_KINDS), cls_loss))
+    if kind not in IOU_LOSS_KINDS:
+        raise ValueError("cls_loss = %r needs an IoU-family reg_loss (got %r)" % (cls_loss, kind))
+    N, H, W, ld_cls = cls.shape
+    check(lib.mxdet_retina_loss_level_quality(ptr(cls), ptr(reg), N, H, W, A, C, ld_cls, reg.shape[3], ptr(cls_labels),
+                                              ptr(anchors), ptr(matched_gt), ptr(gt_boxes), gt_boxes.shape[1],
+                                              cls_labels.shape[1], level_offset, CLS_LOSS_KINDS[cls_loss], alpha, gamma,
+                                              IOU_LOSS_KINDS[kind], stds[0], stds[1], stds[2], stds[3], reg_weight, ptr(num_fg),
+                                              loss_scale, ptr(grad_cls), ptr(grad_reg), ptr(partial), stream_ptr()),
+          "retina_loss_level_quality")

@@ -265,8 +265,10 @@ __device__ __forceinline__ float4 load_f4_a4(const float* p) {
 }
 
 // b: roi / anchor, g: ground truth (absolute corners), d: raw deltas. Returns L, gd[4] = dL / d(raw delta).
+// iou (optional): inter / union of the decoded box -- the quality of the quality-aware class losses; 1 - L
+// is not it, GIoU and DIoU add terms. Callers that pass none compile to what they were.
 __device__ __forceinline__ float box_iou_loss_elem(const float4 b, const float4 g, const float* d, const BoxStds sd,
-                                                   const int kind, float* gd) {
+                                                   const int kind, float* gd, float* iou = nullptr) {
   const float b1[2] = {b.x, b.y}, b2[2] = {b.z, b.w}, ga[2] = {g.x, g.y}, gb[2] = {g.z, g.w};
   const float sc[2] = {sd.x, sd.y}, ss[2] = {sd.w, sd.h};
   float len[2], pc[2], pl[2], g1[2], g2[2], gl[2], il[2], cl[2], a1[2], a2[2], st[2], ck[2];
@@ -297,6 +299,7 @@ __device__ __forceinline__ float box_iou_loss_elem(const float4 b, const float4 
   const float inter = il[0] * il[1];
   const float uni = pl[0] * pl[1] + gl[0] * gl[1] - inter;
   float L = 1.0f - inter / uni;
+  if (iou) *iou = inter / uni;
   const float iu2 = 1.0f / (uni * uni);
   float dI = -(uni + inter) * iu2, dA = inter * iu2;   // dL / d inter, dL / d (pl0 * pl1)
   float gc[2] = {0.0f, 0.0f}, gp[2] = {0.0f, 0.0f};    // dL / d cl[k], and the part of dL / d pc[k] not through a corner
@@ -390,6 +393,70 @@ rcnn_loss_iou_kernel(const void* __restrict__ cls, const void* __restrict__ reg,
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Quality-aware class losses: the matched class column is trained against y = the IoU of the predicted box
+// with its ground truth (a constant of the class loss), every other element against y = 0.
+//   QFL (Li et al. 2020):   L = |y - s|^beta * BCE(s, y), beta in `gamma`; alpha unused
+//   VFL (Zhang et al. 2021): y > 0: L = y * BCE(s, y);  y == 0: L = -alpha * s^gamma * log(1 - s)
+// One element: logit x, target y in [0, 1]. Returns L, g = dL / dx. The logs are those of the focal code.
+__device__ __forceinline__ float quality_cls_elem(const float x, const float y, const int cls_kind, const float alpha,
+                                                  const float gamma, float& g) {
+  float p, q, sp;
+  sigmoid_softplus(x, p, q, sp);
+  const float logp = -((x < 0.0f ? -x : 0.0f) + sp);
+  const float log1mp = -((x > 0.0f ? x : 0.0f) + sp);
+  if (cls_kind == MXDET_CLS_LOSS_QFL) {
+    const float e = p - y;
+    const float bce = -y * logp - (1.0f - y) * log1mp;
+    float mod, dmod;                                       // |e|^beta and beta * |e|^(beta - 1) * sign(e)
+    if (gamma == 2.0f) {
+      mod = e * e;
+      dmod = 2.0f * e;
+    } else {
+      const float ae = e < 0.0f ? -e : e, aec = ae > 1e-30f ? ae : 1e-30f;
+      mod = mxdet_expf(gamma * mxdet_logf(aec));
+      dmod = gamma * (mod / aec);
+      if (e < 0.0f) dmod = -dmod;
+    }
+    g = dmod * (p * q) * bce + mod * e;
+    return mod * bce;
+  }
+  // both sides and two selects: a branch on y would split nearly every wave that holds a foreground anchor
+  const float bce = -y * logp - (1.0f - y) * log1mp;
+  const float mod = (gamma == 2.0f) ? p * p : mxdet_expf(gamma * mxdet_logf(p > 1e-30f ? p : 1e-30f));
+  const float gneg = alpha * (gamma * mod * q * (-log1mp) + mod * p);
+  const float lneg = -alpha * mod * log1mp;
+  g = y > 0.0f ? y * (p - y) : gneg;
+  return y > 0.0f ? y * bce : lneg;
+}
+
+// the unfused primitive: focal_kernel with a per-row quality as the target of the row's own class column
+__global__ void __launch_bounds__(256)
+quality_focal_loss_kernel(const void* __restrict__ logits, int dtype, const int32_t* __restrict__ labels,
+                          const float* __restrict__ quality, long long n, int C, int cls_kind, float alpha, float gamma,
+                          float grad_scale, const int* __restrict__ num_fg, void* __restrict__ grad,
+                          float* __restrict__ partial) {
+  __shared__ float red[8];
+  const long long total = n * C;
+  int nf = *num_fg;
+  float inv_norm = 1.0f / (float)(nf > 1 ? nf : 1);
+  float acc = 0.0f;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    long long r = i / C;
+    int c = (int)(i - r * C);
+    int lab = labels[r];
+    float g = 0.0f;
+    if (lab >= 0) {
+      const float y = (lab == c + 1) ? quality[r] : 0.0f;
+      acc += quality_cls_elem(load_as_f32(logits, i, dtype), y, cls_kind, alpha, gamma, g);
+    }
+    store_from_f32(grad, i, dtype, g * inv_norm * grad_scale);
+  }
+  float s = block_sum_fixed(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s * inv_norm;
+}
+
 }  // namespace mxdet
 
 using namespace mxdet;
@@ -447,6 +514,40 @@ extern "C" int mxdet_focal_loss(const void* logits, int32_t dtype, const int32_t
                      C, alpha, gamma, grad_scale, cnt, grad_logits, partial);
   hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, partial, blocks, 1, loss_out);
   return check_launch("focal_loss");
+}
+
+static bool cls_kind_ok(int32_t k) { return k == MXDET_CLS_LOSS_QFL || k == MXDET_CLS_LOSS_VFL; }
+
+extern "C" int mxdet_quality_focal_loss(const void* logits, int32_t dtype, const int32_t* labels, const float* quality,
+                                        int64_t n, int32_t C, int32_t cls_kind, float alpha, float gamma, float grad_scale,
+                                        float* loss_out, void* grad_logits, void* workspace, size_t workspace_bytes,
+                                        mxdet_stream_t stream) {
+  clear_error();
+  MXDET_REQUIRE(n >= 0 && C > 0, MXDET_ESHAPE, "quality_focal_loss: bad shape");
+  MXDET_REQUIRE(dtype == MXDET_DTYPE_F32 || dtype == MXDET_DTYPE_BF16, MXDET_EINVAL, "quality_focal_loss: dtype");
+  MXDET_REQUIRE(cls_kind_ok(cls_kind), MXDET_EINVAL, "quality_focal_loss: cls_kind must be MXDET_CLS_LOSS_QFL or _VFL");
+  MXDET_REQUIRE(gamma > 0.0f, MXDET_EINVAL, "quality_focal_loss: gamma must be positive");
+  MXDET_REQUIRE(loss_out, MXDET_EINVAL, "quality_focal_loss: null pointer");
+  hipStream_t s = as_stream(stream);
+  if (n == 0) {                                             // nothing to read or write but the loss word
+    hipError_t e0 = zero_async(loss_out, sizeof(float), s);
+    MXDET_REQUIRE(e0 == hipSuccess, MXDET_EHIP, "quality_focal_loss: memset failed");
+    return MXDET_OK;
+  }
+  MXDET_REQUIRE(logits && labels && quality && grad_logits, MXDET_EINVAL, "quality_focal_loss: null pointer");
+  MXDET_REQUIRE(workspace && workspace_bytes >= mxdet_loss_workspace_bytes(n), MXDET_EWORKSPACE,
+                "quality_focal_loss: workspace too small");
+  int* cnt = (int*)workspace;
+  float* partial = (float*)((char*)workspace + 256);
+  hipError_t e = zero_async(cnt, 256, s);
+  MXDET_REQUIRE(e == hipSuccess, MXDET_EHIP, "quality_focal_loss: memset failed");
+  hipLaunchKernelGGL(count_fg_kernel, dim3((unsigned)ceil_div<int64_t>(n, 256)), dim3(256), 0, s, labels, (long long)n, cnt);
+  long long total = (long long)n * C;
+  int blocks = (int)(ceil_div<long long>(total, 256) < 2048 ? ceil_div<long long>(total, 256) : 2048);
+  hipLaunchKernelGGL(quality_focal_loss_kernel, dim3(blocks), dim3(256), 0, s, logits, dtype, labels, quality, (long long)n, C,
+                     cls_kind, alpha, gamma, grad_scale, cnt, grad_logits, partial);
+  hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, partial, blocks, 1, loss_out);
+  return check_launch("quality_focal_loss");
 }
 
 extern "C" int32_t mxdet_rpn_loss_num_partials(int32_t N, int32_t H, int32_t W) {
@@ -834,6 +935,137 @@ retina_loss_iou_kernel(const uint16_t* __restrict__ cls, const uint16_t* __restr
   }
 }
 
+// Class walk of the 16-byte form with a quality target: the lane mapping of retina_focal_vec; qs[al] is the quality of the
+// workgroup's anchor al (0 unless it is foreground with a match inside gt_boxes), written by the box part.
+__device__ __forceinline__ float retina_quality_vec(const uint16_t* __restrict__ cls, int HW, int A, int C, int ld_cls,
+                                                    const int32_t* __restrict__ cls_labels, long long A_total,
+                                                    long long level_offset, int cls_kind, float alpha, float gamma, float inv,
+                                                    float loss_scale, long long a_first, long long total,
+                                                    const float* __restrict__ qs, uint16_t* __restrict__ gcls) {
+  const int CH = C >> 3;
+  float lc = 0.0f;
+  for (int it = threadIdx.x; it < 256 * CH; it += 256) {
+    const int al = it / CH, ck = it - al * CH;
+    const long long idx = a_first + al;
+    if (idx >= total) continue;
+    const int a = (int)(idx % A);
+    const long long cell = idx / A;
+    const int n = (int)(cell / HW);
+    const long long local = cell - (long long)n * HW;
+    const int lab = cls_labels[(long long)n * A_total + level_offset + local * A + a];
+    const long long off = cell * ld_cls + (long long)a * C + ck * 8;
+    uint4 o = make_uint4(0u, 0u, 0u, 0u);
+    if (lab >= 0) {
+      const float qa = qs[al];
+      const uint4 zv = *(const uint4*)(cls + off);
+      const unsigned zw[4] = {zv.x, zv.y, zv.z, zv.w};
+      unsigned ow[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        unsigned packed = 0u;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int c = ck * 8 + 2 * k + h;
+          const float x = h ? __uint_as_float(zw[k] & 0xffff0000u) : __uint_as_float(zw[k] << 16);
+          float g;
+          lc += quality_cls_elem(x, lab == c + 1 ? qa : 0.0f, cls_kind, alpha, gamma, g);
+          packed |= (unsigned)f32_to_bf16_bits(g * inv * loss_scale) << (16 * h);
+        }
+        ow[k] = packed;
+      }
+      o = make_uint4(ow[0], ow[1], ow[2], ow[3]);
+    }
+    *(uint4*)(gcls + off) = o;
+  }
+  return lc;
+}
+
+// class walk of the scalar form: the C logits of one anchor, its quality in a register
+__device__ __forceinline__ float retina_quality_anchor(const uint16_t* __restrict__ z, int C, int lab, float qa, int cls_kind,
+                                                       float alpha, float gamma, float inv, float loss_scale,
+                                                       uint16_t* __restrict__ gz) {
+  float lc = 0.0f;
+  for (int c = 0; c < C; ++c) {
+    float g = 0.0f;
+    if (lab >= 0) lc += quality_cls_elem(bf16_bits_to_f32(z[c]), lab == c + 1 ? qa : 0.0f, cls_kind, alpha, gamma, g);
+    gz[c] = f32_to_bf16_bits(g * inv * loss_scale);
+  }
+  return lc;
+}
+
+// The level loss with a quality-aware class term: grid, partial sums, vector / scalar split and the box part
+// are those of retina_loss_iou_kernel<VEC>. The box part runs FIRST -- lane t on anchor a_first + t -- and leaves the
+// anchor's quality inter / union; the 16-byte class walk visits the workgroup's anchors with another lane mapping, so the
+// 256 qualities cross through LDS behind one barrier that every lane reaches. The scalar form keeps it in a register.
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+retina_loss_quality_kernel(const uint16_t* __restrict__ cls, const uint16_t* __restrict__ reg, int N, int HW, int A, int C,
+                           int ld_cls, int ld_reg, const int32_t* __restrict__ cls_labels,
+                           const float4* __restrict__ anchors, const int32_t* __restrict__ matched,
+                           const float* __restrict__ gt, int G_max, long long A_total, long long level_offset, int cls_kind,
+                           float alpha, float gamma, int kind, BoxStds sd, float reg_weight, const int* __restrict__ num_fg,
+                           float loss_scale, uint16_t* __restrict__ gcls, uint16_t* __restrict__ greg,
+                           float* __restrict__ partial) {
+  __shared__ float red[8];
+  __shared__ float qs[256];
+  const long long total = (long long)N * HW * A;
+  const long long a_first = (long long)blockIdx.x * 256;
+  const long long idx = a_first + threadIdx.x;
+  const int nf = *num_fg;
+  const float inv = 1.0f / (float)(nf > 1 ? nf : 1);
+  float lc = 0.0f, lr = 0.0f, qa = 0.0f;
+  int lab = -1;
+  long long coff = 0;                                     // this lane's anchor: first class logit
+  if (idx < total) {
+    const int a = (int)(idx % A);
+    const long long cell = idx / A;
+    const int n = (int)(cell / HW);
+    const long long local = cell - (long long)n * HW;
+    const long long ai = level_offset + local * A + a;
+    const long long gi = (long long)n * A_total + ai;
+    lab = cls_labels[gi];
+    coff = cell * ld_cls + (long long)a * C;
+    const uint16_t* d = reg + cell * ld_reg + a * 4;
+    uint16_t* gd = greg + cell * ld_reg + a * 4;
+    unsigned short gb[4] = {0, 0, 0, 0};
+    const int m = lab > 0 ? matched[gi] : -1;
+    if (m >= 0 && m < G_max) {                            // a match outside gt_boxes: regresses nothing, quality 0
+      float dd[4], g4[4];
+      if (VEC) {
+        unpack4_bf16(*(const uint2*)d, dd);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) dd[k] = bf16_bits_to_f32(d[k]);
+      }
+      const float4 g = load_f4_a4(gt + ((long long)n * G_max + m) * 5);
+      lr = reg_weight * box_iou_loss_elem(anchors[ai], g, dd, sd, kind, g4, &qa);
+      const float gs = reg_weight * inv * loss_scale;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) gb[k] = f32_to_bf16_bits(g4[k] * gs);
+    }
+    if (VEC) {
+      *(uint2*)gd = make_uint2((unsigned)gb[0] | ((unsigned)gb[1] << 16), (unsigned)gb[2] | ((unsigned)gb[3] << 16));
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) gd[k] = gb[k];
+    }
+  }
+  if (VEC) {
+    qs[threadIdx.x] = qa;
+    __syncthreads();
+    lc = retina_quality_vec(cls, HW, A, C, ld_cls, cls_labels, A_total, level_offset, cls_kind, alpha, gamma, inv, loss_scale,
+                            a_first, total, qs, gcls);
+  } else if (idx < total) {
+    lc = retina_quality_anchor(cls + coff, C, lab, qa, cls_kind, alpha, gamma, inv, loss_scale, gcls + coff);
+  }
+  float s0 = block_sum_fixed(lc, red);
+  float s1 = block_sum_fixed(lr, red);
+  if (threadIdx.x == 0) {
+    partial[2 * blockIdx.x + 0] = s0 * inv;
+    partial[2 * blockIdx.x + 1] = s1 * inv;
+  }
+}
+
 }  // namespace mxdet
 
 extern "C" int mxdet_anchor_class_labels(const int32_t* labels, const int32_t* matched_gt, const float* gt_boxes,
@@ -927,4 +1159,48 @@ extern "C" int mxdet_retina_loss_level_iou(const uint16_t* cls, const uint16_t* 
                        (long long)level_offset, alpha, gamma, kind, sd, reg_weight, (const int*)num_fg, loss_scale, grad_cls,
                        grad_reg, partial);
   return check_launch("retina_loss_level_iou");
+}
+
+extern "C" int mxdet_retina_loss_level_quality(const uint16_t* cls, const uint16_t* reg, int32_t N, int32_t H, int32_t W,
+                                               int32_t A, int32_t C, int32_t ld_cls, int32_t ld_reg,
+                                               const int32_t* cls_labels, const float* anchors, const int32_t* matched_gt,
+                                               const float* gt_boxes, int32_t G_max, int64_t A_total, int64_t level_offset,
+                                               int32_t cls_kind, float alpha, float gamma, int32_t kind, float std_x,
+                                               float std_y, float std_w, float std_h, float reg_weight, const int32_t* num_fg,
+                                               float loss_scale, uint16_t* grad_cls, uint16_t* grad_reg, float* partial,
+                                               mxdet_stream_t stream) {
+  clear_error();
+  MXDET_REQUIRE(N > 0 && H > 0 && W > 0 && A > 0 && C > 0 && ld_cls >= A * C && ld_reg >= 4 * A && G_max > 0, MXDET_ESHAPE,
+                "retina_loss_level_quality: bad shape");
+  MXDET_REQUIRE(cls_kind_ok(cls_kind), MXDET_EINVAL, "retina_loss_level_quality: cls_kind must be MXDET_CLS_LOSS_QFL or _VFL");
+  MXDET_REQUIRE(gamma > 0.0f, MXDET_EINVAL, "retina_loss_level_quality: gamma must be positive");
+  MXDET_REQUIRE(iou_kind_ok(kind), MXDET_EINVAL, "retina_loss_level_quality: kind must be MXDET_IOU_LOSS_IOU, _GIOU or _DIOU");
+  MXDET_REQUIRE(stds_ok(std_x, std_y, std_w, std_h) && reg_weight > 0.0f, MXDET_EINVAL,
+                "retina_loss_level_quality: stds and reg_weight must be positive");
+  MXDET_REQUIRE(cls && reg && cls_labels && anchors && matched_gt && gt_boxes && num_fg && grad_cls && grad_reg && partial,
+                MXDET_EINVAL, "retina_loss_level_quality: null pointer");
+  MXDET_REQUIRE((uintptr_t)anchors % 16 == 0, MXDET_EINVAL, "retina_loss_level_quality: anchors must be 16-byte aligned");
+  MXDET_REQUIRE(level_offset >= 0 && level_offset + (int64_t)H * W * A <= A_total, MXDET_ESHAPE,
+                "retina_loss_level_quality: level outside the anchor range");
+  int blocks = mxdet_retina_loss_num_partials(N, H, W, A);
+  // the vec condition of mxdet_retina_loss_level
+  const bool vec = (C % 8 == 0) && (ld_cls % 8 == 0) && (ld_reg % 4 == 0) && (((uintptr_t)cls | (uintptr_t)grad_cls) % 16 == 0) &&
+                   (((uintptr_t)reg | (uintptr_t)grad_reg) % 8 == 0);
+  if (route_probe_on()) {
+    const int32_t rec[kRouteWords] = {MXDET_ROUTE_RETINA_LOSS_QUALITY, vec ? 1 : 0, blocks};
+    route_record(rec);
+    return MXDET_OK;
+  }
+  const BoxStds sd = {std_x, std_y, std_w, std_h};
+  if (vec)
+    hipLaunchKernelGGL(retina_loss_quality_kernel<true>, dim3(blocks), dim3(256), 0, as_stream(stream), cls, reg, N, H * W, A,
+                       C, ld_cls, ld_reg, cls_labels, (const float4*)anchors, matched_gt, gt_boxes, G_max, (long long)A_total,
+                       (long long)level_offset, cls_kind, alpha, gamma, kind, sd, reg_weight, (const int*)num_fg, loss_scale,
+                       grad_cls, grad_reg, partial);
+  else
+    hipLaunchKernelGGL(retina_loss_quality_kernel<false>, dim3(blocks), dim3(256), 0, as_stream(stream), cls, reg, N, H * W, A,
+                       C, ld_cls, ld_reg, cls_labels, (const float4*)anchors, matched_gt, gt_boxes, G_max, (long long)A_total,
+                       (long long)level_offset, cls_kind, alpha, gamma, kind, sd, reg_weight, (const int*)num_fg, loss_scale,
+                       grad_cls, grad_reg, partial);
+  return check_launch("retina_loss_level_quality");
 }

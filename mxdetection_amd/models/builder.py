@@ -8,6 +8,9 @@ def build_detector(cfg, device="cuda"):
     dcn = dict(dcn_stages=tuple(net.dcn_stages), dcn_modulated=bool(net.dcn_modulated), dcn_groups=int(net.dcn_groups))
     reg = dict(reg_loss=str(net.reg_loss), reg_loss_weight=net.reg_loss_weight)
     if net.type in ("faster_rcnn", "mask_rcnn"):
+        if net.cls_loss != "focal":
+            raise ValueError("network.cls_loss = %r: %s keeps softmax cross-entropy (qfl / vfl are retinanet options)"
+                             % (net.cls_loss, net.type))
         if net.assigner != "max_iou":
             raise ValueError("network.assigner = %r: %s keeps the RPN's sampler (atss is a retinanet option)"
                              % (net.assigner, net.type))
@@ -25,7 +28,8 @@ def build_detector(cfg, device="cuda"):
             raise ValueError("network.bbox_head / network.head_norm: retinanet has no RoI heads")
         model = RetinaNet(device, depth=net.backbone_depth, num_classes=net.num_classes - 1, seed=net.seed, **dcn, **reg,
                           assigner=str(net.assigner), atss_topk=net.atss_topk, anchor_ratios=tuple(net.anchor_ratios),
-                          anchor_scales_per_octave=net.anchor_scales_per_octave, anchor_scale=float(net.anchor_scale))
+                          anchor_scales_per_octave=net.anchor_scales_per_octave, anchor_scale=float(net.anchor_scale),
+                          cls_loss=str(net.cls_loss), cls_loss_alpha=net.cls_loss_alpha, cls_loss_gamma=net.cls_loss_gamma)
     else:
         raise ValueError("unknown network.type %r" % (net.type,))
     if net.pretrained:

@@ -2,7 +2,7 @@
 on hand-written HIP kernels, same arena / graph / data-parallel machinery as Faster R-CNN."""
 import torch
 
-from ..core.loss import check_reg_loss
+from ..core.loss import check_cls_loss, check_reg_loss
 from .backbones import ResNet
 from .necks.fpn import RetinaFPN
 from .rpn_heads.retina_head import RetinaHead, check_assigner
@@ -25,14 +25,17 @@ def check_anchor_setting(anchor_ratios, anchor_scales_per_octave, anchor_scale):
 class RetinaNet(DetectorBase):
     def __init__(self, device="cuda", depth=101, num_classes=80, seed=7, dcn_stages=(), dcn_modulated=True, dcn_groups=1,
                  reg_loss="smooth_l1", reg_loss_weight=1.0, assigner="max_iou", atss_topk=9, anchor_ratios=(0.5, 1.0, 2.0),
-                 anchor_scales_per_octave=3, anchor_scale=4.0):
+                 anchor_scales_per_octave=3, anchor_scale=4.0, cls_loss="focal", cls_loss_alpha=None, cls_loss_gamma=None):
         """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
         reg_loss / reg_loss_weight: the head's box loss -- 'smooth_l1', or 'iou' / 'giou' / 'diou' on the decoded box times
         reg_loss_weight (rpn_heads.RetinaHead).
         assigner / atss_topk: 'max_iou' (thresholds 0.5 / 0.4) or 'atss' (core.anchor.atss_assign).
         anchor_ratios / anchor_scales_per_octave / anchor_scale: the head's anchors per cell -- every ratio at the sizes
-        anchor_scale * 2^(i / scales_per_octave) * stride, i < scales_per_octave (ATSS as published: (1.0,), 1, 8.0)."""
+        anchor_scale * 2^(i / scales_per_octave) * stride, i < scales_per_octave (ATSS as published: (1.0,), 1, 8.0).
+        cls_loss / cls_loss_alpha / cls_loss_gamma: the head's class loss -- 'focal', or 'qfl' / 'vfl' against the IoU of the
+        decoded box (rpn_heads.RetinaHead; needs an IoU-family reg_loss). The parameter layout does not depend on it."""
         check_reg_loss(reg_loss, reg_loss_weight)
+        check_cls_loss(cls_loss, reg_loss, cls_loss_alpha, cls_loss_gamma)
         check_assigner(assigner, atss_topk)
         ratios, octave_scales = check_anchor_setting(anchor_ratios, anchor_scales_per_octave, anchor_scale)
         gen = torch.Generator().manual_seed(seed)
@@ -40,7 +43,8 @@ class RetinaNet(DetectorBase):
         self.strides = [8, 16, 32, 64, 128]
         self.head = RetinaHead(256, self.strides, self.arena, self.ws, device, gen, num_classes=num_classes,
                                ratios=ratios, octave_scales=octave_scales, anchor_scale=float(anchor_scale),
-                               reg_loss=reg_loss, reg_loss_weight=reg_loss_weight, assigner=assigner, atss_topk=atss_topk)
+                               reg_loss=reg_loss, reg_loss_weight=reg_loss_weight, assigner=assigner, atss_topk=atss_topk,
+                               cls_loss=cls_loss, cls_loss_alpha=cls_loss_alpha, cls_loss_gamma=cls_loss_gamma)
         self.mark_head = self.arena.size
         self.neck = RetinaFPN([512, 1024, 2048], 256, self.arena, self.ws, device, gen)
         self.mark_fpn = self.arena.size

@@ -30,12 +30,23 @@ class RetinaHead:
     def __init__(self, channels, strides, arena, ws, device, gen, num_classes=80, num_convs=4, ratios=(0.5, 1.0, 2.0),
                  octave_scales=(1.0, 2.0 ** (1.0 / 3.0), 2.0 ** (2.0 / 3.0)), anchor_scale=4.0, fg_thresh=0.5,
                  bg_thresh=0.4, alpha=0.25, gamma=2.0, sigma=3.0, prior=0.01, reg_loss="smooth_l1", reg_loss_weight=1.0,
-                 assigner="max_iou", atss_topk=9):
+                 assigner="max_iou", atss_topk=9, cls_loss="focal", cls_loss_alpha=None, cls_loss_gamma=None):
         """assigner: 'max_iou' (fg_thresh / bg_thresh) or 'atss' (the atss_topk nearest anchors per level and GT).
         reg_loss: 'smooth_l1' on the encoded deltas (core.loss.retina_loss_level), or 'iou' / 'giou' / 'diou' on the
-        decoded box times reg_loss_weight (core.loss.retina_loss_level_iou; stds 1, as the inference decode)."""
+        decoded box times reg_loss_weight (core.loss.retina_loss_level_iou; stds 1, as the inference decode).
+        cls_loss: 'focal' (alpha / gamma above, today's calls), or 'qfl' / 'vfl': the matched class column is trained
+        against the IoU of the decoded box with its ground truth (core.loss.retina_loss_level_quality; needs an IoU-family
+        reg_loss). cls_loss_alpha / cls_loss_gamma: None = the kind's published setting (QFL beta = 2 in gamma; VFL
+        alpha = 0.75, gamma = 2); with 'focal' they replace alpha / gamma when given."""
         L_.check_reg_loss(reg_loss, reg_loss_weight)
         check_assigner(assigner, atss_topk)
+        quality = L_.check_cls_loss(cls_loss, reg_loss, cls_loss_alpha, cls_loss_gamma)
+        self.cls_loss = cls_loss
+        if quality is not None:
+            self.cls_alpha, self.cls_gamma = quality
+        else:
+            alpha = alpha if cls_loss_alpha is None else float(cls_loss_alpha)
+            gamma = gamma if cls_loss_gamma is None else float(cls_loss_gamma)
         self.assigner, self.atss_topk = assigner, int(atss_topk)
         self.reg_loss, self.reg_loss_weight = reg_loss, float(reg_loss_weight)
         kw = dict(arena=arena, ws=ws, device=device, gen=gen)
@@ -130,6 +141,11 @@ class RetinaHead:
             if self.reg_loss == "smooth_l1":
                 L_.retina_loss_level(self.co[l], self.bo[l], self.A, self.Cn, self.cls_labels, targets, self.level_offsets[l],
                                      self.alpha, self.gamma, self.sigma, self.num_fg, loss_scale, gc, gb, self.partial[2 * off:])
+            elif self.cls_loss != "focal":
+                L_.retina_loss_level_quality(self.co[l], self.bo[l], self.A, self.Cn, self.cls_labels, self.anchors, matched,
+                                             gt_boxes, self.level_offsets[l], self.cls_loss, self.cls_alpha, self.cls_gamma,
+                                             self.reg_loss, (1.0, 1.0, 1.0, 1.0), self.reg_loss_weight, self.num_fg, loss_scale,
+                                             gc, gb, self.partial[2 * off:])
             else:
                 L_.retina_loss_level_iou(self.co[l], self.bo[l], self.A, self.Cn, self.cls_labels, self.anchors, matched, gt_boxes,
                                          self.level_offsets[l], self.alpha, self.gamma, self.reg_loss, (1.0, 1.0, 1.0, 1.0),

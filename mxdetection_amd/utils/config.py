@@ -49,6 +49,9 @@ DEFAULTS = {
         "gn_groups": 32,                  # GroupNorm groups (256 / gn_groups must be a multiple of 8)
         "reg_loss": "smooth_l1",          # box regression loss of the box head / the RetinaNet head: smooth_l1 | iou | giou | diou
         "reg_loss_weight": 1.0,           # weight of an IoU-family reg_loss (on the decoded box); smooth_l1 takes none. The RPN keeps smooth-L1
+        "cls_loss": "focal",              # retinanet class loss: focal | qfl (Li et al. 2020) | vfl (Zhang et al. 2021); qfl / vfl need an IoU-family reg_loss
+        "cls_loss_alpha": None,           # null = the kind's published setting (focal 0.25, vfl 0.75; qfl takes none)
+        "cls_loss_gamma": None,           # null = the kind's published setting (focal 2, qfl beta = 2, vfl 2)
         "assigner": "max_iou",            # retinanet targets: max_iou (thresholds 0.5 / 0.4) | atss (Zhang et al. 2020). The RPN keeps its sampler
         "atss_topk": 9,                   # ATSS: candidates per ground-truth box and pyramid level (1..16)
         "anchor_ratios": [0.5, 1.0, 2.0],  # retinanet anchors per cell: these h/w ratios ...
