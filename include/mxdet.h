@@ -463,6 +463,50 @@ int mxdet_retina_loss_level_quality(const uint16_t* cls, const uint16_t* reg, in
                                     const int32_t* num_fg, float loss_scale, uint16_t* grad_cls, uint16_t* grad_reg,
                                     float* partial, mxdet_stream_t stream);
 
+/* Distribution box regression for the RetinaNet head: the box half of Generalized Focal Loss (Li et al.,
+ * NeurIPS 2020). R = reg_max in 1..MXDET_REG_MAX_LIMIT, s = the level's stride, b the anchor box, cx = 0.5 (b.x1 + b.x2),
+ * cy = 0.5 (b.y1 + b.y2), g the matched ground truth.
+ * Layout: 4 (R + 1) logits per anchor, the logit of bin k of side `side` (0..3 = l, t, r, b) of anchor a at channel
+ *   a * 4 (R + 1) + side * (R + 1) + k: the published layout, so converted weights keep their order.
+ * Integral decode, float32, no FMA contraction, in this order per side: m = max_k x_k; e_k = mxdet_expf(x_k - m);
+ *   Z = sum_k e_k and S = sum_k (float)k * e_k, both from 0 with k ascending; E = S / Z; p_k = e_k / Z.
+ *   Box (cx - s E_l, cy - s E_t, cx + s E_r, cy + s E_b); the losses work relative to (cx, cy): p1 = (-(s E_l), -(s E_t)),
+ *   p2 = (s E_r, s E_b), g1 = (g.x1 - cx, g.y1 - cy), g2 = (g.x2 - cx, g.y2 - cy), length p2 - p1 + 1, centre 0.5 (p1 + p2).
+ * Box term: reg_weight * L, L the IoU / GIoU / DIoU loss above on that box ("+1" convention, the same inter / union and tie
+ *   rule); the gradient reaches the logits through dE / dx_k = p_k (k - E).
+ * Quality (cls_kind QFL / VFL): q = inter / union of that box, a constant of the class loss: no gradient flows from the
+ *   class term into the distribution. q = 0 for background, ignored anchors and matches outside gt_boxes.
+ * DFL: per side dist = (cx - g.x1, cy - g.y1, g.x2 - cx, g.y2 - cy), y = clamp(dist / s, 0, (float)R - 0.1f) (0.1: the
+ *   published epsilon), yl = floor(y), CE(x, j) = (m + mxdet_logf(Z)) - x_j:
+ *   DFL = (yl + 1 - y) CE(x, yl) + (y - yl) CE(x, yl + 1); y is a constant. The anchor's term is dfl_weight * (1/4) * the sum
+ *   of its four sides, added in the order l, t, r, b.
+ * Only cls_labels > 0 with 0 <= matched < G_max regresses. The level entry normalises all three terms by max(1, *num_fg)
+ * and scales by loss_scale. Not part of this: weighting the box and DFL terms by the detached class score. */
+#define MXDET_CLS_LOSS_FOCAL 0
+#define MXDET_REG_MAX_LIMIT 31
+/* The unfused primitive (what a CustomOp binding calls), four lanes per row: boxes[n,4], gt[n,4] (16-byte aligned), logits
+ * rows of ld >= 4 (R + 1) elements (f32 | bf16). Per row: loss_box = reg_weight * L, loss_dfl, quality (may be NULL), and
+ * grad_logits (logits dtype and ld) = grad_scale * d(loss_box + loss_dfl) / dx. Columns past 4 (R + 1) are untouched.
+ * n == 0 returns MXDET_OK. */
+int mxdet_box_dist_loss(const float* boxes, const float* gt, const void* logits, int32_t dtype, int32_t ld, int64_t n,
+                        int32_t reg_max, float stride, int32_t kind, float reg_weight, float dfl_weight, float grad_scale,
+                        float* loss_box, float* loss_dfl, float* quality, void* grad_logits, mxdet_stream_t stream);
+/* The fused level entry: the arguments of mxdet_retina_loss_level_quality without the stds, with reg_max, stride and
+ * dfl_weight; cls_kind also accepts MXDET_CLS_LOSS_FOCAL (alpha, gamma: the focal loss's). reg / grad_reg rows hold
+ * ld_reg >= 4 (R + 1) A elements. Grid: mxdet_retina_loss_num_partials workgroups of 256 anchors; partial holds THREE words
+ * per workgroup (class, box, DFL): finalize with ncomp = 3. grad_reg: every real channel of every anchor of the level is
+ * written (zeros where nothing regresses), padding channels are untouched. For equal logits, labels and quality, grad_cls
+ * and the class partial are bit-identical to the _quality (focal: _iou) entry. Vector / scalar split: the condition of
+ * mxdet_retina_loss_level. No atomics, no host synchronisation, nothing allocated, capturable; a replay follows new
+ * gt_boxes. */
+int mxdet_retina_loss_level_dfl(const uint16_t* cls, const uint16_t* reg, int32_t N, int32_t H, int32_t W, int32_t A,
+                                int32_t C, int32_t ld_cls, int32_t ld_reg, const int32_t* cls_labels, const float* anchors,
+                                const int32_t* matched_gt, const float* gt_boxes, int32_t G_max, int64_t A_total,
+                                int64_t level_offset, int32_t cls_kind, float alpha, float gamma, int32_t kind,
+                                int32_t reg_max, float stride, float reg_weight, float dfl_weight, const int32_t* num_fg,
+                                float loss_scale, uint16_t* grad_cls, uint16_t* grad_reg, float* partial,
+                                mxdet_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * core/mask + mask_heads (README.md:18, :30) -- Mask R-CNN.
  * mask targets: for roi r (batch, box) with matched GT g = matched_gt[r] and class labels[r] > 0, resample the
@@ -808,6 +852,17 @@ int mxdet_retina_detect_soft(const mxdet_pyramid_t* p, int32_t N, const float* i
                              float score_thresh, float nms_thresh, int32_t max_per_image, float* dets,
                              int32_t* num_dets, void* workspace, size_t workspace_bytes, int32_t method, float sigma,
                              mxdet_stream_t stream);
+/* Test-time detection of the distribution head: mxdet_retina_detect_soft with method = -1 for greedy NMS and
+ * reg_max in 1..MXDET_REG_MAX_LIMIT. p->reg[l] holds 4 (reg_max + 1) logits per anchor in the layout of mxdet_box_dist_loss,
+ * addressed with the same reg_s* strides (channel index times reg_sc). Selection, merge, NMS and ordering are exactly those
+ * of mxdet_retina_detect(_soft); only the box of each selected candidate differs: the integral decode at the candidate's
+ * global index (level, cell, anchor) with the anchor centre 0.5 (x1 + x2), 0.5 (y1 + y2) of base_anchors + cell * stride,
+ * clipped as mxdet_decode_clip clips. Only the at most pre_nms_top_n candidates per level and image are decoded. Same
+ * workspace as mxdet_retina_detect. */
+int mxdet_retina_detect_dfl(const mxdet_pyramid_t* p, int32_t N, const float* im_info, int32_t pre_nms_top_n,
+                            float score_thresh, float nms_thresh, int32_t max_per_image, float* dets, int32_t* num_dets,
+                            void* workspace, size_t workspace_bytes, int32_t method, float sigma, int32_t reg_max,
+                            mxdet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * process_data (README.md:23) -- the step in front of the path.

@@ -53,7 +53,7 @@ int64_t mxdet_debug_get_tuning(int32_t which);
 /* Route probe (per calling thread): which kernel instantiation a dense convolution / weight-gradient call, or which
  * form of the RetinaNet level loss, runs.
  * While the probe is on, mxdet_conv2d_fwd / _fwd_splitk / _fwd_chain / _dgrad / _grouped, mxdet_conv2d_wgrad,
- * mxdet_conv2d_wgrad_grouped(_parts) and mxdet_retina_loss_level(_iou / _quality) validate their arguments as usual, record the launch(es) they WOULD make and return
+ * mxdet_conv2d_wgrad_grouped(_parts) and mxdet_retina_loss_level(_iou / _quality / _dfl) validate their arguments as usual, record the launch(es) they WOULD make and return
  * MXDET_OK without launching, without dereferencing any pointer and without touching the device (so it also works on a
  * machine without a GPU, with dummy non-null pointers). Switching it on clears the records. A record is 16 int32 words,
  * word 0 = kind:
@@ -70,7 +70,8 @@ int64_t mxdet_debug_get_tuning(int32_t which);
  *                             a multiple of 8 / 8 / 4, or cls / grad_cls not 16-byte or reg / grad_reg not 8-byte aligned),
  *                             grid (= mxdet_retina_loss_num_partials)
  *   MXDET_ROUTE_RETINA_LOSS_IOU  the same two words for mxdet_retina_loss_level_iou (retina_loss_iou_kernel<vec>)
- *   MXDET_ROUTE_RETINA_LOSS_QUALITY  the same two words for mxdet_retina_loss_level_quality (retina_loss_quality_kernel<vec>) */
+ *   MXDET_ROUTE_RETINA_LOSS_QUALITY  the same two words for mxdet_retina_loss_level_quality (retina_loss_quality_kernel<vec>)
+ *   MXDET_ROUTE_RETINA_LOSS_DFL  the same two words for mxdet_retina_loss_level_dfl (retina_loss_dfl_kernel<vec, focal>) */
 #define MXDET_ROUTE_CONV 1
 #define MXDET_ROUTE_WGRAD 2
 #define MXDET_ROUTE_CONV_GROUPED 3
@@ -78,6 +79,7 @@ int64_t mxdet_debug_get_tuning(int32_t which);
 #define MXDET_ROUTE_RETINA_LOSS 5
 #define MXDET_ROUTE_RETINA_LOSS_IOU 6
 #define MXDET_ROUTE_RETINA_LOSS_QUALITY 7
+#define MXDET_ROUTE_RETINA_LOSS_DFL 8
 #define MXDET_ROUTE_WORDS 16
 #define MXDET_ROUTE_MAX 4
 int mxdet_debug_route_probe(int32_t on);

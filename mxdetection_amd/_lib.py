@@ -120,6 +120,8 @@ SIGNATURES = {
     "mxdet_retina_detect": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mxdet_retina_detect_soft": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp, c_sz, c_i32, c_f32,
                                          c_vp]),
+    "mxdet_retina_detect_dfl": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp, c_sz, c_i32, c_f32,
+                                        c_i32, c_vp]),
     "mxdet_debug_preprocess_direct": (c_i32, [c_i32]),
     "mxdet_image_preprocess": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "mxdet_polygon_masks": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
@@ -181,6 +183,11 @@ SIGNATURES = {
     "mxdet_retina_loss_level_quality": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
                                                 c_vp, c_i32, c_i64, c_i64, c_i32, c_f32, c_f32, c_i32, c_f32, c_f32, c_f32, c_f32,
                                                 c_f32, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    "mxdet_box_dist_loss": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_f32, c_i32, c_f32, c_f32, c_f32, c_vp, c_vp,
+                                    c_vp, c_vp, c_vp]),
+    "mxdet_retina_loss_level_dfl": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                            c_i32, c_i64, c_i64, c_i32, c_f32, c_f32, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp,
+                                            c_f32, c_vp, c_vp, c_vp, c_vp]),
     "mxdet_mask_target": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mxdet_pixel_shuffle2": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mxdet_mask_loss_workspace_bytes": (c_sz, [c_i64, c_i32]),
@@ -256,12 +263,15 @@ TUNING_KEYS = {"T64": 0, "T128": 1, "PAR64": 2, "WG_TARGET": 3, "WG_MINSTEPS": 4
                "T128W": 15, "T3_MIX": 16, "SPLITK_TILE": 17, "T3_PER_ITEM": 18}
 # word 0 of a route-probe record (MXDET_ROUTE_* in include/mxdet_debug.h)
 ROUTE_KINDS = {"CONV": 1, "WGRAD": 2, "CONV_GROUPED": 3, "WGRAD_GROUPED": 4, "RETINA_LOSS": 5, "RETINA_LOSS_IOU": 6,
-               "RETINA_LOSS_QUALITY": 7}
+               "RETINA_LOSS_QUALITY": 7, "RETINA_LOSS_DFL": 8}
 
 # `kind` of the IoU-family box losses (MXDET_IOU_LOSS_* in include/mxdet.h)
 IOU_LOSS_KINDS = {"iou": 0, "giou": 1, "diou": 2}
 # `cls_kind` of the quality-aware class losses (MXDET_CLS_LOSS_* in include/mxdet.h)
 CLS_LOSS_KINDS = {"qfl": 1, "vfl": 2}
+# `cls_kind` of mxdet_retina_loss_level_dfl: the above and MXDET_CLS_LOSS_FOCAL; reg_max's bound (MXDET_REG_MAX_LIMIT)
+CLS_LOSS_KINDS_DFL = {"focal": 0, "qfl": 1, "vfl": 2}
+REG_MAX_LIMIT = 31
 
 _lib = None
 

@@ -293,10 +293,15 @@ def detections_to_coco(dets, num_dets, image_ids, scales, class_to_cat=None):
 class RetinaDetect:
     """One-stage test-time detection on the device (mxdet_retina_detect): per-level top-k over (anchor, class) logits,
     decode, merge, sigmoid, per-class NMS, max_per_image. cls[l] bf16/f32 [N,H,W,>=A*C] (channel a*C + c), reg[l]
-    [N,H,W,>=4A] (channel a*4 + k), base[l] device f32 [A,4]. nms_method / soft_sigma as in DetectionPostprocess."""
+    [N,H,W,>=4A] (channel a*4 + k), base[l] device f32 [A,4]. nms_method / soft_sigma as in DetectionPostprocess.
+    reg_max > 0: the distribution head (mxdet_retina_detect_dfl) -- reg[l] [N,H,W,>=4*(reg_max+1)*A], channel
+    a*4*(reg_max+1) + side*(reg_max+1) + k; the selected candidates' boxes are the integral decode."""
 
     def __init__(self, num_classes, strides, base_anchors, pre_nms_top_n=1000, score_thresh=0.05, nms_thresh=0.5,
-                 max_per_image=100, nms_method="hard", soft_sigma=0.5):
+                 max_per_image=100, nms_method="hard", soft_sigma=0.5, reg_max=0):
+        if isinstance(reg_max, bool) or not isinstance(reg_max, int) or not 0 <= reg_max <= _lib.REG_MAX_LIMIT:
+            raise ValueError("reg_max must be an integer in 0..%d (got %r)" % (_lib.REG_MAX_LIMIT, reg_max))
+        self.reg_max = reg_max
         self.C, self.strides, self.base = num_classes, list(strides), base_anchors
         self.method, self.soft_sigma = soft_nms_method(nms_method), soft_sigma
         self.pre_n, self.score_thresh, self.nms_thresh, self.max_det = pre_nms_top_n, score_thresh, nms_thresh, max_per_image
@@ -323,7 +328,10 @@ class RetinaDetect:
         num = torch.empty((N,), dtype=torch.int32, device=cls[0].device)
         args = (C.byref(d), N, ptr(im_info), self.pre_n, self.score_thresh, self.nms_thresh, self.max_det, ptr(dets), ptr(num),
                 ptr(self._ws), self._ws.numel())
-        if self.method == 0:
+        if self.reg_max > 0:
+            check(lib.mxdet_retina_detect_dfl(*args, self.method if self.method else -1, self.soft_sigma, self.reg_max,
+                                              stream_ptr()), "retina_detect_dfl")
+        elif self.method == 0:
             check(lib.mxdet_retina_detect(*args, stream_ptr()), "retina_detect")
         else:
             check(lib.mxdet_retina_detect_soft(*args, self.method, self.soft_sigma, stream_ptr()), "retina_detect_soft")

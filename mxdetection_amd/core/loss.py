@@ -210,3 +210,68 @@ def retina_loss_level_quality(cls, reg, A, C, cls_labels, anchors, matched_gt, g
                                               IOU_LOSS_KINDS[kind], stds[0], stds[1], stds[2], stds[3], reg_weight, ptr(num_fg),
                                               loss_scale, ptr(grad_cls), ptr(grad_reg), ptr(partial), stream_ptr()),
           "retina_loss_level_quality")
+
+
+# ---- distribution box regression of the RetinaNet head: integral decode + DFL (include/mxdet.h) ----
+CLS_LOSS_KINDS_DFL = _lib.CLS_LOSS_KINDS_DFL
+REG_MAX_LIMIT = _lib.REG_MAX_LIMIT
+
+
+def check_reg_max(reg_max, reg_loss, dfl_weight=0.25):
+    """The distribution-head options, checked before anything is allocated: reg_max = 0 (plain deltas) or the last bin
+    1..REG_MAX_LIMIT (each side a distribution over 0..reg_max strides; needs an IoU-family reg_loss, which acts on the
+    integral-decoded box); dfl_weight > 0."""
+    if isinstance(reg_max, bool) or not isinstance(reg_max, int) or not 0 <= reg_max <= REG_MAX_LIMIT:
+        raise ValueError("reg_max must be an integer in 0..%d (got %r)" % (REG_MAX_LIMIT, reg_max))
+    w = dfl_weight
+    if isinstance(w, bool) or not isinstance(w, (int, float)) or not w > 0:
+        raise ValueError("dfl_weight must be a positive number (got %r)" % (w,))
+    if reg_max > 0 and reg_loss not in IOU_LOSS_KINDS:
+        raise ValueError("reg_max = %r needs an IoU-family reg_loss (%s): the box loss acts on the integral-decoded box, "
+                         "reg_loss = %r decodes none" % (reg_max, ", ".join(IOU_LOSS_KINDS), reg_loss))
+
+
+def box_dist_loss(boxes, gt, logits, reg_max, stride, kind="giou", reg_weight=1.0, dfl_weight=0.25, grad_scale=1.0,
+                  grad_logits=None, want_quality=True):
+    """Unfused distribution box loss fwd+bwd: boxes / gt [n,4] f32, logits [n,ld>=4*(reg_max+1)] (f32|bf16; may be a column
+    view of a wider buffer). Returns (loss_box [n], loss_dfl [n], quality [n] or None, grad_logits like logits; only the
+    first 4*(reg_max+1) columns are written)."""
+    lib = _lib.load()
+    if kind not in IOU_LOSS_KINDS:
+        raise ValueError("kind must be one of %s (got %r)" % (", ".join(IOU_LOSS_KINDS), kind))
+    check_reg_max(reg_max, kind, dfl_weight)
+    n = boxes.shape[0]
+    dev = boxes.device
+    loss_box = torch.empty((n,), dtype=torch.float32, device=dev)
+    loss_dfl = torch.empty((n,), dtype=torch.float32, device=dev)
+    quality = torch.empty((n,), dtype=torch.float32, device=dev) if want_quality else None
+    ld = logits.stride(0) if n > 1 else logits.shape[1]
+    if grad_logits is None:     # same leading dimension as logits
+        grad_logits = torch.zeros((n, ld), dtype=logits.dtype, device=logits.device)[:, :logits.shape[1]]
+    for name, t in (("logits", logits), ("grad_logits", grad_logits)):      # one leading dimension serves both
+        if t.dtype != logits.dtype or t.shape[1] < 4 * (reg_max + 1) or (n > 0 and t.stride(1) != 1) or (n > 1 and t.stride(0) != ld):
+            raise ValueError("box_dist_loss: %s must hold rows of >= %d contiguous %s elements with the row stride of logits "
+                             "(%d); got shape %s, strides %s, %s" % (name, 4 * (reg_max + 1), logits.dtype, ld, tuple(t.shape),
+                                                                       tuple(t.stride()), t.dtype))
+    check(lib.mxdet_box_dist_loss(ptr(boxes), ptr(gt), ptr(logits), _DT[logits.dtype], ld, n, reg_max, stride,
+                                  IOU_LOSS_KINDS[kind], reg_weight, dfl_weight, grad_scale, ptr(loss_box), ptr(loss_dfl),
+                                  ptr(quality), ptr(grad_logits), stream_ptr()), "box_dist_loss")
+    return loss_box, loss_dfl, quality, grad_logits
+
+
+def retina_loss_level_dfl(cls, reg, A, C, cls_labels, anchors, matched_gt, gt_boxes, level_offset, cls_loss, alpha, gamma,
+                          kind, reg_max, stride, reg_weight, dfl_weight, num_fg, loss_scale, grad_cls, grad_reg, partial):
+    """The level loss of the distribution head: class term 'focal' / 'qfl' / 'vfl', box term `kind` on the integral-decoded
+    box, DFL. reg / grad_reg [N,H,W,ld_reg >= 4*(reg_max+1)*A]; partial: THREE f32 words per workgroup."""
+    lib = _lib.load()
+    if cls_loss not in CLS_LOSS_KINDS_DFL:
+        raise ValueError("cls_loss must be one of %s (got %r)" % (", ".join(CLS_LOSS_KINDS_DFL), cls_loss))
+    if kind not in IOU_LOSS_KINDS:
+        raise ValueError("reg_max = %r needs an IoU-family reg_loss (got %r)" % (reg_max, kind))
+    N, H, W, ld_cls = cls.shape
+    check(lib.mxdet_retina_loss_level_dfl(ptr(cls), ptr(reg), N, H, W, A, C, ld_cls, reg.shape[3], ptr(cls_labels),
+                                          ptr(anchors), ptr(matched_gt), ptr(gt_boxes), gt_boxes.shape[1],
+                                          cls_labels.shape[1], level_offset, CLS_LOSS_KINDS_DFL[cls_loss], alpha, gamma,
+                                          IOU_LOSS_KINDS[kind], reg_max, stride, reg_weight, dfl_weight, ptr(num_fg),
+                                          loss_scale, ptr(grad_cls), ptr(grad_reg), ptr(partial), stream_ptr()),
+          "retina_loss_level_dfl")

@@ -6,6 +6,7 @@
 // per bf16 logit). Scalar losses are reduced in a fixed order (per-block tree, then an index-ordered
 // single-workgroup pass), so repeated runs give identical bits.
 #include "common.h"
+#include "dist_box.h"
 
 namespace mxdet {
 
@@ -264,37 +265,25 @@ __device__ __forceinline__ float4 load_f4_a4(const float* p) {
   return make_float4(v.x, v.y, v.z, v.w);
 }
 
-// b: roi / anchor, g: ground truth (absolute corners), d: raw deltas. Returns L, gd[4] = dL / d(raw delta).
-// iou (optional): inter / union of the decoded box -- the quality of the quality-aware class losses; 1 - L
-// is not it, GIoU and DIoU add terms. Callers that pass none compile to what they were.
-__device__ __forceinline__ float box_iou_loss_elem(const float4 b, const float4 g, const float* d, const BoxStds sd,
-                                                   const int kind, float* gd, float* iou = nullptr) {
-  const float b1[2] = {b.x, b.y}, b2[2] = {b.z, b.w}, ga[2] = {g.x, g.y}, gb[2] = {g.z, g.w};
-  const float sc[2] = {sd.x, sd.y}, ss[2] = {sd.w, sd.h};
-  float len[2], pc[2], pl[2], g1[2], g2[2], gl[2], il[2], cl[2], a1[2], a2[2], st[2], ck[2];
+// The IoU core, shared by the delta decode below and the integral decode of the distribution head. Per
+// axis k, in any common origin: predicted corners p1 / p2, centre pc and "+1" length pl; ground-truth corners g1 / g2.
+// Returns L. Outputs per axis: d1 / d2 = dL / d p1, p2 through the min / max corners only, gp = dL / d pc through the DIoU
+// centre term only, da = dL / d pl through the area only. iou (optional): inter / union -- the quality of the quality-aware
+// class losses; 1 - L is not it, GIoU and DIoU add terms.
+__device__ __forceinline__ float box_iou_core(const float* p1, const float* p2, const float* pc, const float* pl,
+                                              const float* g1, const float* g2, const int kind, float* d1, float* d2,
+                                              float* gp, float* da, float* iou) {
+  float gl[2], il[2], cl[2], a1[2], a2[2], st[2];
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
-    g1[k] = ga[k] - b1[k];
-    g2[k] = gb[k] - b1[k];
-    len[k] = b2[k] - b1[k] + 1.0f;
-    const float c0 = 0.5f * (len[k] - 1.0f);
-    float t = d[2 + k] * ss[k];
-    ck[k] = tie_step(MXDET_BBOX_XFORM_CLIP, t);
-    if (t > MXDET_BBOX_XFORM_CLIP) t = MXDET_BBOX_XFORM_CLIP;
-    float c = d[k] * sc[k];
-    c = c * len[k];
-    pc[k] = c + c0;
-    pl[k] = mxdet_expf(t) * len[k];
-    const float hl = 0.5f * (pl[k] - 1.0f);
-    const float p1 = pc[k] - hl, p2 = pc[k] + hl;
     gl[k] = g2[k] - g1[k] + 1.0f;
-    a1[k] = tie_step(p1, g1[k]);                      // share of p1 in max(p1, g1)
-    a2[k] = tie_step(g2[k], p2);                      // share of p2 in min(p2, g2)
-    const float lo = p1 > g1[k] ? p1 : g1[k], hi = p2 < g2[k] ? p2 : g2[k];
+    a1[k] = tie_step(p1[k], g1[k]);                   // share of p1 in max(p1, g1)
+    a2[k] = tie_step(g2[k], p2[k]);                   // share of p2 in min(p2, g2)
+    const float lo = p1[k] > g1[k] ? p1[k] : g1[k], hi = p2[k] < g2[k] ? p2[k] : g2[k];
     const float r = hi - lo + 1.0f;
     st[k] = tie_step(r, 0.0f);
     il[k] = r > 0.0f ? r : 0.0f;
-    cl[k] = (p2 > g2[k] ? p2 : g2[k]) - (p1 < g1[k] ? p1 : g1[k]) + 1.0f;
+    cl[k] = (p2[k] > g2[k] ? p2[k] : g2[k]) - (p1[k] < g1[k] ? p1[k] : g1[k]) + 1.0f;
   }
   const float inter = il[0] * il[1];
   const float uni = pl[0] * pl[1] + gl[0] * gl[1] - inter;
@@ -302,7 +291,9 @@ __device__ __forceinline__ float box_iou_loss_elem(const float4 b, const float4 
   if (iou) *iou = inter / uni;
   const float iu2 = 1.0f / (uni * uni);
   float dI = -(uni + inter) * iu2, dA = inter * iu2;   // dL / d inter, dL / d (pl0 * pl1)
-  float gc[2] = {0.0f, 0.0f}, gp[2] = {0.0f, 0.0f};    // dL / d cl[k], and the part of dL / d pc[k] not through a corner
+  float gc[2] = {0.0f, 0.0f};                          // dL / d cl[k]
+  gp[0] = 0.0f;
+  gp[1] = 0.0f;
   if (kind == MXDET_IOU_LOSS_GIOU) {
     const float C = cl[0] * cl[1], ic = 1.0f / C;
     L += (C - uni) * ic;
@@ -324,10 +315,43 @@ __device__ __forceinline__ float box_iou_loss_elem(const float4 b, const float4 
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const float gi = dI * il[1 - k] * st[k];
-    const float d2 = gi * a2[k] + gc[k] * (1.0f - a2[k]);          // dL / d p2
-    const float d1 = -(gi * a1[k] + gc[k] * (1.0f - a1[k]));       // dL / d p1
-    const float dpl = dA * pl[1 - k] + 0.5f * (d2 - d1);
-    gd[k] = (d1 + d2 + gp[k]) * (sc[k] * len[k]);
+    d2[k] = gi * a2[k] + gc[k] * (1.0f - a2[k]);
+    d1[k] = -(gi * a1[k] + gc[k] * (1.0f - a1[k]));
+    da[k] = dA * pl[1 - k];
+  }
+  return L;
+}
+
+// b: roi / anchor, g: ground truth (absolute corners), d: raw deltas. Returns L, gd[4] = dL / d(raw delta).
+// iou (optional): see box_iou_core. Callers that pass none compile to what they were.
+__device__ __forceinline__ float box_iou_loss_elem(const float4 b, const float4 g, const float* d, const BoxStds sd,
+                                                   const int kind, float* gd, float* iou = nullptr) {
+  const float b1[2] = {b.x, b.y}, b2[2] = {b.z, b.w}, ga[2] = {g.x, g.y}, gb[2] = {g.z, g.w};
+  const float sc[2] = {sd.x, sd.y}, ss[2] = {sd.w, sd.h};
+  float len[2], pc[2], pl[2], p1[2], p2[2], g1[2], g2[2], ck[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    g1[k] = ga[k] - b1[k];
+    g2[k] = gb[k] - b1[k];
+    len[k] = b2[k] - b1[k] + 1.0f;
+    const float c0 = 0.5f * (len[k] - 1.0f);
+    float t = d[2 + k] * ss[k];
+    ck[k] = tie_step(MXDET_BBOX_XFORM_CLIP, t);
+    if (t > MXDET_BBOX_XFORM_CLIP) t = MXDET_BBOX_XFORM_CLIP;
+    float c = d[k] * sc[k];
+    c = c * len[k];
+    pc[k] = c + c0;
+    pl[k] = mxdet_expf(t) * len[k];
+    const float hl = 0.5f * (pl[k] - 1.0f);
+    p1[k] = pc[k] - hl;
+    p2[k] = pc[k] + hl;
+  }
+  float d1[2], d2[2], gp[2], da[2];
+  const float L = box_iou_core(p1, p2, pc, pl, g1, g2, kind, d1, d2, gp, da, iou);
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const float dpl = da[k] + 0.5f * (d2[k] - d1[k]);
+    gd[k] = (d1[k] + d2[k] + gp[k]) * (sc[k] * len[k]);
     gd[2 + k] = dpl * (pl[k] * ss[k]) * ck[k];
   }
   return L;
@@ -1066,6 +1090,182 @@ retina_loss_quality_kernel(const uint16_t* __restrict__ cls, const uint16_t* __r
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Distribution box regression (definition in include/mxdet.h): four lanes per box, lane `side` (l, t, r, b)
+// on the R + 1 logits at x[off ..]. All four lanes of a quad call this together: the expectations cross by lane reads
+// inside the quad, then every lane evaluates the (cheap) IoU core on the whole box and keeps its own side's dL / dE.
+// Writes the side's R + 1 gradients: (reg_weight * dL/dE * p_k (k - E) + dfl_weight / 4 * (p_k - target_k)) * gscale.
+// Returns L (unweighted, equal on the four lanes); dfl = this side's DFL, q = inter / union.
+__device__ __forceinline__ float dist_box_quad(const void* x, long long off, int dtype, int R, int side, const float4 b,
+                                               const float4 g, float s, int kind, float reg_weight, float dfl_weight,
+                                               float gscale, void* gx, float& dfl, float& q) {
+  float xv[kDistBins], m, Z;                              // the logits, then e_k = exp(x_k - m)
+  dist_load(x, off, 1, dtype, R, xv);
+  const float E = dist_expect(xv, R, m, Z);
+  const int q0 = lane_id() & ~3;
+  const float El = __shfl(E, q0 + 0), Et = __shfl(E, q0 + 1), Er = __shfl(E, q0 + 2), Eb = __shfl(E, q0 + 3);
+  const float cx = 0.5f * (b.x + b.z), cy = 0.5f * (b.y + b.w);
+  const float g1[2] = {g.x - cx, g.y - cy}, g2[2] = {g.z - cx, g.w - cy};
+  const float p1[2] = {-(s * El), -(s * Et)}, p2[2] = {s * Er, s * Eb};
+  float pl[2], pc[2], d1[2], d2[2], gp[2], da[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    pl[k] = p2[k] - p1[k] + 1.0f;
+    pc[k] = 0.5f * (p1[k] + p2[k]);
+  }
+  const float L = box_iou_core(p1, p2, pc, pl, g1, g2, kind, d1, d2, gp, da, &q);
+  const int ax = side & 1;
+  // pc = (p1 + p2) / 2 and pl = p2 - p1 + 1: dL / d p1 = d1 + gp / 2 - da, dL / d p2 = d2 + gp / 2 + da
+  const float dp = side < 2 ? d1[ax] + 0.5f * gp[ax] - da[ax] : d2[ax] + 0.5f * gp[ax] + da[ax];
+  const float dE = side < 2 ? -(s * dp) : s * dp;
+  const float dist = side < 2 ? -g1[ax] : g2[ax];
+  const float ymax = (float)R - 0.1f;
+  float y = dist / s;
+  y = y < 0.0f ? 0.0f : y;
+  y = y > ymax ? ymax : y;
+  const int yl = (int)y;                                  // y >= 0: truncation is floor
+  const float wl = (float)yl + 1.0f - y, wr = y - (float)yl;
+  const float lse = m + mxdet_logf(Z);
+  dfl = wl * (lse - load_as_f32(x, off + yl, dtype)) + wr * (lse - load_as_f32(x, off + yl + 1, dtype));
+  const float gb = reg_weight * dE, gd = dfl_weight * 0.25f;
+#pragma unroll
+  for (int k = 0; k < kDistBins; ++k)
+    if (k <= R) {
+      const float p = xv[k] / Z;
+      const float t = (k == yl ? wl : 0.0f) + (k == yl + 1 ? wr : 0.0f);
+      store_from_f32(gx, off + k, dtype, (gb * (p * ((float)k - E)) + gd * (p - t)) * gscale);
+    }
+  return L;
+}
+
+// the unfused primitive: four lanes per row
+__global__ void __launch_bounds__(256)
+box_dist_loss_kernel(const float4* __restrict__ boxes, const float4* __restrict__ gt, const void* __restrict__ logits,
+                     int dtype, int ld, long long n, int R, float stride, int kind, float reg_weight, float dfl_weight,
+                     float grad_scale, float* __restrict__ loss_box, float* __restrict__ loss_dfl,
+                     float* __restrict__ quality, void* __restrict__ grad) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long i = t >> 2;
+  const int side = (int)(t & 3);
+  if (i >= n) return;                                     // whole quads leave together
+  float dfl, q;
+  const float L = dist_box_quad(logits, i * ld + side * (R + 1), dtype, R, side, boxes[i], gt[i], stride, kind, reg_weight,
+                                dfl_weight, grad_scale, grad, dfl, q);
+  const int q0 = lane_id() & ~3;
+  const float dsum = ((__shfl(dfl, q0 + 0) + __shfl(dfl, q0 + 1)) + __shfl(dfl, q0 + 2)) + __shfl(dfl, q0 + 3);
+  if (side == 0) {
+    loss_box[i] = reg_weight * L;
+    loss_dfl[i] = dfl_weight * 0.25f * dsum;
+    if (quality) quality[i] = q;
+  }
+}
+
+// The level loss of the distribution head: the grid of the other level kernels (256 anchors per workgroup),
+// three partial sums per workgroup (class, box, DFL). Phases, each behind a barrier that every lane reaches:
+//   1  lane t on anchor a_first + t: label and match -> ms[t] (>= 0: the anchor regresses against that row of gt_boxes)
+//   2  zeros into the 4 (R + 1) gradient channels of every anchor that does not regress: 8-byte stores on consecutive
+//      addresses (VEC) or 2-byte ones; an anchor's channels start a multiple of 8 bytes into its 8-byte aligned row
+//   3  four lanes per regressing anchor, 64 anchors per pass over the workgroup's COMPACTED list of them (dist_box_quad);
+//      side 0 keeps the sums and leaves the quality in qs[]. A workgroup holds a handful of positives: one pass, where
+//      a fixed anchor-to-quad map needs four, each as long as its slowest quad.
+//   4  the class walk of retina_loss_iou_kernel (FOCAL) or retina_loss_quality_kernel: same code, same bits.
+template <bool VEC, bool FOCAL>
+__global__ void __launch_bounds__(256)
+retina_loss_dfl_kernel(const uint16_t* __restrict__ cls, const uint16_t* __restrict__ reg, int N, int HW, int A, int C,
+                       int ld_cls, int ld_reg, const int32_t* __restrict__ cls_labels, const float4* __restrict__ anchors,
+                       const int32_t* __restrict__ matched, const float* __restrict__ gt, int G_max, long long A_total,
+                       long long level_offset, int cls_kind, float alpha, float gamma, int kind, int R, float stride,
+                       float reg_weight, float dfl_weight, const int* __restrict__ num_fg, float loss_scale,
+                       uint16_t* __restrict__ gcls, uint16_t* __restrict__ greg, float* __restrict__ partial) {
+  __shared__ float red[8];
+  __shared__ float qs[256];
+  __shared__ int ms[256];
+  __shared__ long long roff[256];                         // first gradient channel of the workgroup's anchors
+  __shared__ int plist[256], cnt[5];                      // the regressing anchors, in anchor order
+  const long long total = (long long)N * HW * A;
+  const long long a_first = (long long)blockIdx.x * 256;
+  const long long idx = a_first + threadIdx.x;
+  const int nf = *num_fg;
+  const float inv = 1.0f / (float)(nf > 1 ? nf : 1);
+  const int nb = R + 1;
+  float lc = 0.0f, lr = 0.0f, ldf = 0.0f;
+  int lab = -1, mt = -2;                                  // mt -2: no such anchor
+  long long coff = 0, goff = 0;
+  if (idx < total) {
+    const int a = (int)(idx % A);
+    const long long cell = idx / A;
+    const int n = (int)(cell / HW);
+    const long long local = cell - (long long)n * HW;
+    const long long gi = (long long)n * A_total + level_offset + local * A + a;
+    lab = cls_labels[gi];
+    coff = cell * ld_cls + (long long)a * C;
+    goff = cell * ld_reg + (long long)a * (4 * nb);
+    const int m = lab > 0 ? matched[gi] : -1;
+    mt = (m >= 0 && m < G_max) ? m : -1;                  // a match outside gt_boxes: regresses nothing, quality 0
+  }
+  ms[threadIdx.x] = mt;
+  roff[threadIdx.x] = goff;
+  qs[threadIdx.x] = 0.0f;
+  int npos;
+  const int rank = block_excl_count(mt >= 0, cnt, &npos);
+  if (mt >= 0) plist[rank] = threadIdx.x;
+  __syncthreads();
+  const int per = VEC ? nb : 4 * nb;                      // stores per anchor (<= 128: it < 2^15, fast_divmod is exact)
+  const float rper = 1.0f / (float)per;
+  for (int it = threadIdx.x; it < 256 * per; it += 256) {
+    int ck;
+    const int al = fast_divmod(it, per, rper, &ck);
+    if (ms[al] != -1) continue;
+    const long long off = roff[al];
+    if (VEC)
+      *(uint2*)(greg + off + 4 * ck) = make_uint2(0u, 0u);
+    else
+      greg[off + ck] = 0;
+  }
+  for (int j = threadIdx.x >> 2; j < npos; j += 64) {     // the four lanes of a quad share j
+    const int al = plist[j], side = threadIdx.x & 3;
+    const int m = ms[al];
+    const long long ix = a_first + al;
+    const int a = (int)(ix % A);
+    const long long cell = ix / A;
+    const int n = (int)(cell / HW);
+    const long long ai = level_offset + (cell - (long long)n * HW) * A + a;
+    const float4 g = load_f4_a4(gt + ((long long)n * G_max + m) * 5);
+    float dfl, q;
+    const float L = dist_box_quad(reg, roff[al] + side * nb, MXDET_DTYPE_BF16, R, side,
+                                  anchors[ai], g, stride, kind, reg_weight, dfl_weight, inv * loss_scale, greg, dfl, q);
+    const int q0 = lane_id() & ~3;
+    const float dsum = ((__shfl(dfl, q0 + 0) + __shfl(dfl, q0 + 1)) + __shfl(dfl, q0 + 2)) + __shfl(dfl, q0 + 3);
+    if (side == 0) {
+      lr += reg_weight * L;
+      ldf += dfl_weight * 0.25f * dsum;
+      qs[al] = q;
+    }
+  }
+  __syncthreads();
+  if (VEC) {
+    if (FOCAL)
+      lc = retina_focal_vec(cls, HW, A, C, ld_cls, cls_labels, A_total, level_offset, alpha, gamma, inv, loss_scale, a_first,
+                            total, gcls);
+    else
+      lc = retina_quality_vec(cls, HW, A, C, ld_cls, cls_labels, A_total, level_offset, cls_kind, alpha, gamma, inv,
+                              loss_scale, a_first, total, qs, gcls);
+  } else if (idx < total) {
+    if (FOCAL)
+      lc = retina_focal_anchor(cls + coff, C, lab, alpha, gamma, inv, loss_scale, gcls + coff);
+    else
+      lc = retina_quality_anchor(cls + coff, C, lab, qs[threadIdx.x], cls_kind, alpha, gamma, inv, loss_scale, gcls + coff);
+  }
+  float s0 = block_sum_fixed(lc, red);
+  float s1 = block_sum_fixed(lr, red);
+  float s2 = block_sum_fixed(ldf, red);
+  if (threadIdx.x == 0) {
+    partial[3 * blockIdx.x + 0] = s0 * inv;
+    partial[3 * blockIdx.x + 1] = s1 * inv;
+    partial[3 * blockIdx.x + 2] = s2 * inv;
+  }
+}
+
 }  // namespace mxdet
 
 extern "C" int mxdet_anchor_class_labels(const int32_t* labels, const int32_t* matched_gt, const float* gt_boxes,
@@ -1203,4 +1403,75 @@ extern "C" int mxdet_retina_loss_level_quality(const uint16_t* cls, const uint16
                        (long long)level_offset, cls_kind, alpha, gamma, kind, sd, reg_weight, (const int*)num_fg, loss_scale,
                        grad_cls, grad_reg, partial);
   return check_launch("retina_loss_level_quality");
+}
+
+static bool cls_kind_dfl_ok(int32_t k) { return k == MXDET_CLS_LOSS_FOCAL || cls_kind_ok(k); }
+
+extern "C" int mxdet_box_dist_loss(const float* boxes, const float* gt, const void* logits, int32_t dtype, int32_t ld,
+                                   int64_t n, int32_t reg_max, float stride, int32_t kind, float reg_weight,
+                                   float dfl_weight, float grad_scale, float* loss_box, float* loss_dfl, float* quality,
+                                   void* grad_logits, mxdet_stream_t stream) {
+  clear_error();
+  MXDET_REQUIRE(reg_max >= 1 && reg_max <= MXDET_REG_MAX_LIMIT, MXDET_EINVAL, "box_dist_loss: reg_max %d not in 1..%d", reg_max,
+                MXDET_REG_MAX_LIMIT);
+  MXDET_REQUIRE(n >= 0 && n <= (int64_t)1 << 28 && ld >= 4 * (reg_max + 1), MXDET_ESHAPE,
+                "box_dist_loss: bad shape (ld must be >= 4 * (reg_max + 1))");
+  MXDET_REQUIRE(dtype == MXDET_DTYPE_F32 || dtype == MXDET_DTYPE_BF16, MXDET_EINVAL, "box_dist_loss: dtype");
+  MXDET_REQUIRE(iou_kind_ok(kind), MXDET_EINVAL, "box_dist_loss: kind must be MXDET_IOU_LOSS_IOU, _GIOU or _DIOU");
+  MXDET_REQUIRE(stride > 0.0f && reg_weight > 0.0f && dfl_weight > 0.0f, MXDET_EINVAL,
+                "box_dist_loss: stride, reg_weight and dfl_weight must be positive");
+  if (n == 0) return MXDET_OK;
+  MXDET_REQUIRE(boxes && gt && logits && loss_box && loss_dfl && grad_logits, MXDET_EINVAL, "box_dist_loss: null pointer");
+  MXDET_REQUIRE((((uintptr_t)boxes | (uintptr_t)gt) % 16) == 0, MXDET_EINVAL,
+                "box_dist_loss: boxes and gt must be 16-byte aligned");
+  hipLaunchKernelGGL(box_dist_loss_kernel, dim3((unsigned)ceil_div<int64_t>(4 * n, 256)), dim3(256), 0, as_stream(stream),
+                     (const float4*)boxes, (const float4*)gt, logits, dtype, ld, (long long)n, reg_max, stride, kind,
+                     reg_weight, dfl_weight, grad_scale, loss_box, loss_dfl, quality, grad_logits);
+  return check_launch("box_dist_loss");
+}
+
+extern "C" int mxdet_retina_loss_level_dfl(const uint16_t* cls, const uint16_t* reg, int32_t N, int32_t H, int32_t W, int32_t A,
+                                           int32_t C, int32_t ld_cls, int32_t ld_reg, const int32_t* cls_labels,
+                                           const float* anchors, const int32_t* matched_gt, const float* gt_boxes,
+                                           int32_t G_max, int64_t A_total, int64_t level_offset, int32_t cls_kind, float alpha,
+                                           float gamma, int32_t kind, int32_t reg_max, float stride, float reg_weight,
+                                           float dfl_weight, const int32_t* num_fg, float loss_scale, uint16_t* grad_cls,
+                                           uint16_t* grad_reg, float* partial, mxdet_stream_t stream) {
+  clear_error();
+  MXDET_REQUIRE(reg_max >= 1 && reg_max <= MXDET_REG_MAX_LIMIT, MXDET_EINVAL, "retina_loss_level_dfl: reg_max %d not in 1..%d",
+                reg_max, MXDET_REG_MAX_LIMIT);
+  MXDET_REQUIRE(N > 0 && H > 0 && W > 0 && A > 0 && C > 0 && ld_cls >= A * C && ld_reg >= 4 * (reg_max + 1) * A && G_max > 0,
+                MXDET_ESHAPE, "retina_loss_level_dfl: bad shape");
+  MXDET_REQUIRE(cls_kind_dfl_ok(cls_kind), MXDET_EINVAL,
+                "retina_loss_level_dfl: cls_kind must be MXDET_CLS_LOSS_FOCAL, _QFL or _VFL");
+  MXDET_REQUIRE(gamma > 0.0f, MXDET_EINVAL, "retina_loss_level_dfl: gamma must be positive");
+  MXDET_REQUIRE(iou_kind_ok(kind), MXDET_EINVAL, "retina_loss_level_dfl: kind must be MXDET_IOU_LOSS_IOU, _GIOU or _DIOU");
+  MXDET_REQUIRE(stride > 0.0f && reg_weight > 0.0f && dfl_weight > 0.0f, MXDET_EINVAL,
+                "retina_loss_level_dfl: stride, reg_weight and dfl_weight must be positive");
+  MXDET_REQUIRE(cls && reg && cls_labels && anchors && matched_gt && gt_boxes && num_fg && grad_cls && grad_reg && partial,
+                MXDET_EINVAL, "retina_loss_level_dfl: null pointer");
+  MXDET_REQUIRE((uintptr_t)anchors % 16 == 0, MXDET_EINVAL, "retina_loss_level_dfl: anchors must be 16-byte aligned");
+  MXDET_REQUIRE(level_offset >= 0 && level_offset + (int64_t)H * W * A <= A_total, MXDET_ESHAPE,
+                "retina_loss_level_dfl: level outside the anchor range");
+  int blocks = mxdet_retina_loss_num_partials(N, H, W, A);
+  // the vec condition of mxdet_retina_loss_level
+  const bool vec = (C % 8 == 0) && (ld_cls % 8 == 0) && (ld_reg % 4 == 0) && (((uintptr_t)cls | (uintptr_t)grad_cls) % 16 == 0) &&
+                   (((uintptr_t)reg | (uintptr_t)grad_reg) % 8 == 0);
+  if (route_probe_on()) {
+    const int32_t rec[kRouteWords] = {MXDET_ROUTE_RETINA_LOSS_DFL, vec ? 1 : 0, blocks};
+    route_record(rec);
+    return MXDET_OK;
+  }
+  const bool focal = cls_kind == MXDET_CLS_LOSS_FOCAL;
+#define MXDET_DFL_LAUNCH(V, F)                                                                                              \
+  hipLaunchKernelGGL((retina_loss_dfl_kernel<V, F>), dim3(blocks), dim3(256), 0, as_stream(stream), cls, reg, N, H * W, A, C, \
+                     ld_cls, ld_reg, cls_labels, (const float4*)anchors, matched_gt, gt_boxes, G_max, (long long)A_total,     \
+                     (long long)level_offset, cls_kind, alpha, gamma, kind, reg_max, stride, reg_weight, dfl_weight,          \
+                     (const int*)num_fg, loss_scale, grad_cls, grad_reg, partial)
+  if (vec && focal) MXDET_DFL_LAUNCH(true, true);
+  else if (vec) MXDET_DFL_LAUNCH(true, false);
+  else if (focal) MXDET_DFL_LAUNCH(false, true);
+  else MXDET_DFL_LAUNCH(false, false);
+#undef MXDET_DFL_LAUNCH
+  return check_launch("retina_loss_level_dfl");
 }

@@ -15,6 +15,7 @@
 // merges on those keys. A list's selections come out in descending key order, which is what the rank-merge needs.
 // Integer-exact (kept indices, classes) and bit-exact (scores, boxes) against oracle/mxdet_oracle.c.
 #include "common.h"
+#include "dist_box.h"
 #include "select.h"
 #include "soft_nms.h"
 
@@ -206,6 +207,52 @@ __global__ void retina_candidates_kernel(const float* __restrict__ rois, const f
   boxes[i] = make_float4(r[1], r[2], r[3], r[4]);
 }
 
+// The distribution head: the boxes of the merged candidates again, by the integral decode at the candidate's
+// global index (level, cell, anchor). One lane per candidate and side would save nothing: there are at most 4096 per image.
+struct DistPyr {
+  int num_levels, A, C, dtype, R;
+  int H[8], W[8], stride[8];
+  const void* reg[8];
+  long long reg_sn[8], reg_sy[8], reg_sx[8], reg_sc[8];
+  const float* base[8];
+  long long level_offset[9];                              // in (anchor, class) pairs, as gidx counts them
+};
+
+__global__ void retina_dist_boxes_kernel(DistPyr p, const int32_t* __restrict__ gidx, const int32_t* __restrict__ num, int N,
+                                         int Rc, const float* __restrict__ im_info, float4* __restrict__ boxes) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N * Rc) return;
+  const int n = i / Rc, j = i - n * Rc;
+  if (j >= num[n]) return;                                // retina_candidates_kernel left zeros
+  const long long gi = gidx[i];
+  int l = 0;
+  while (l + 1 < p.num_levels && gi >= p.level_offset[l + 1]) ++l;
+  const int local = (int)(gi - p.level_offset[l]);
+  const int AC = p.A * p.C;
+  const int a = (local % AC) / p.C, cell = local / AC;
+  const int x = cell % p.W[l], y = cell / p.W[l];
+  const float* base = p.base[l] + a * 4;
+  const float sx = (float)(x * p.stride[l]), sy = (float)(y * p.stride[l]);
+  const float ax1 = base[0] + sx, ay1 = base[1] + sy, ax2 = base[2] + sx, ay2 = base[3] + sy;
+  const float cx = 0.5f * (ax1 + ax2), cy = 0.5f * (ay1 + ay2), s = (float)p.stride[l];
+  const long long off = n * p.reg_sn[l] + y * p.reg_sy[l] + x * p.reg_sx[l];
+  const int nb = p.R + 1;
+  float E[4];
+#pragma unroll
+  for (int sd = 0; sd < 4; ++sd) {
+    float xv[kDistBins], m, Z;
+    dist_load(p.reg[l], off + (long long)(a * 4 * nb + sd * nb) * p.reg_sc[l], p.reg_sc[l], p.dtype, p.R, xv);
+    E[sd] = dist_expect(xv, p.R, m, Z);
+  }
+  float ox1 = cx - s * E[0], oy1 = cy - s * E[1], ox2 = cx + s * E[2], oy2 = cy + s * E[3];
+  const float mx = im_info[n * 3 + 1] - 1.0f, my = im_info[n * 3 + 0] - 1.0f;      // the clip of mxdet_decode_clip
+  ox1 = ox1 < 0.0f ? 0.0f : (ox1 > mx ? mx : ox1);
+  oy1 = oy1 < 0.0f ? 0.0f : (oy1 > my ? my : oy1);
+  ox2 = ox2 < 0.0f ? 0.0f : (ox2 > mx ? mx : ox2);
+  oy2 = oy2 < 0.0f ? 0.0f : (oy2 > my ? my : oy2);
+  boxes[i] = make_float4(ox1, oy1, ox2, oy2);
+}
+
 struct RetinaWs {
   float* rois; float* logit; int32_t* gidx; int32_t* num; float* score; int32_t* cls; float4* boxes;
   float4* sboxes; unsigned long long* skeys; int32_t* counts; int32_t* keep_idx; int32_t* num_keep;
@@ -342,7 +389,7 @@ extern "C" size_t mxdet_retina_detect_workspace_bytes(const mxdet_pyramid_t* p, 
 static int retina_detect_impl(const mxdet_pyramid_t* p, int32_t N, const float* im_info, int32_t pre_nms_top_n,
                               float score_thresh, float nms_thresh, int32_t max_per_image, float* dets,
                               int32_t* num_dets, void* workspace, size_t workspace_bytes, int method, float sigma,
-                              mxdet_stream_t stream) {
+                              mxdet_stream_t stream, int reg_max = 0) {
   MXDET_REQUIRE(p && im_info && dets && num_dets, MXDET_EINVAL, "retina_detect: null pointer");
   MXDET_REQUIRE(N > 0 && p->num_levels > 0 && p->classes >= 1 && pre_nms_top_n > 0, MXDET_ESHAPE, "retina_detect: bad sizes");
   const int C = p->classes, R = retina_candidates_cap(p, pre_nms_top_n), B = N * C;
@@ -359,6 +406,23 @@ static int retina_detect_impl(const mxdet_pyramid_t* p, int32_t N, const float* 
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(retina_candidates_kernel, dim3(ceil_div(N * R, 256)), dim3(256), 0, s, (const float*)w.rois,
                      (const float*)w.logit, (const int32_t*)w.gidx, (const int32_t*)w.num, N, R, C, w.score, w.cls, w.boxes);
+  if (reg_max > 0) {                                        // the distribution head: the candidates' boxes again
+    DistPyr d;
+    d.num_levels = p->num_levels; d.A = p->A / C; d.C = C; d.dtype = p->dtype; d.R = reg_max;
+    long long lo = 0;
+    for (int l = 0; l < 8; ++l) {
+      const bool on = l < p->num_levels;
+      d.H[l] = on ? p->H[l] : 0; d.W[l] = on ? p->W[l] : 0; d.stride[l] = on ? p->stride[l] : 0;
+      d.reg[l] = on ? p->reg[l] : nullptr; d.base[l] = on ? p->base_anchors[l] : nullptr;
+      d.reg_sn[l] = on ? p->reg_sn[l] : 0; d.reg_sy[l] = on ? p->reg_sy[l] : 0;
+      d.reg_sx[l] = on ? p->reg_sx[l] : 0; d.reg_sc[l] = on ? p->reg_sc[l] : 0;
+      d.level_offset[l] = lo;
+      if (on) lo += (long long)p->H[l] * p->W[l] * p->A;
+    }
+    d.level_offset[8] = lo;
+    hipLaunchKernelGGL(retina_dist_boxes_kernel, dim3(ceil_div(N * R, 256)), dim3(256), 0, s, d, (const int32_t*)w.gidx,
+                       (const int32_t*)w.num, N, R, im_info, w.boxes);
+  }
   int Kpad = 1;
   while (Kpad < R) Kpad <<= 1;
   hipLaunchKernelGGL(det_class_sort_kernel, dim3(C, N), dim3(1024), 0, s, (const float*)w.score, (const float4*)w.boxes,
@@ -397,4 +461,19 @@ extern "C" int mxdet_retina_detect_soft(const mxdet_pyramid_t* p, int32_t N, con
   MXDET_REQUIRE(method != 2 || sigma > 0.0f, MXDET_EINVAL, "retina_detect_soft: sigma must be positive for method 2");
   return retina_detect_impl(p, N, im_info, pre_nms_top_n, score_thresh, nms_thresh, max_per_image, dets, num_dets,
                             workspace, workspace_bytes, method, sigma, stream);
+}
+
+extern "C" int mxdet_retina_detect_dfl(const mxdet_pyramid_t* p, int32_t N, const float* im_info, int32_t pre_nms_top_n,
+                                       float score_thresh, float nms_thresh, int32_t max_per_image, float* dets,
+                                       int32_t* num_dets, void* workspace, size_t workspace_bytes, int32_t method, float sigma,
+                                       int32_t reg_max, mxdet_stream_t stream) {
+  clear_error();
+  MXDET_REQUIRE(method >= -1 && method <= 2, MXDET_EINVAL, "retina_detect_dfl: method %d not in -1..2", method);
+  MXDET_REQUIRE(method != 2 || sigma > 0.0f, MXDET_EINVAL, "retina_detect_dfl: sigma must be positive for method 2");
+  MXDET_REQUIRE(reg_max >= 1 && reg_max <= MXDET_REG_MAX_LIMIT, MXDET_EINVAL, "retina_detect_dfl: reg_max %d not in 1..%d",
+                reg_max, MXDET_REG_MAX_LIMIT);
+  MXDET_REQUIRE(!p || (p->classes >= 1 && p->A > 0 && p->A % p->classes == 0), MXDET_ESHAPE,
+                "retina_detect_dfl: A must be a multiple of classes");
+  return retina_detect_impl(p, N, im_info, pre_nms_top_n, score_thresh, nms_thresh, max_per_image, dets, num_dets,
+                            workspace, workspace_bytes, method, sigma, stream, reg_max);
 }

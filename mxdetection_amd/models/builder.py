@@ -11,6 +11,9 @@ def build_detector(cfg, device="cuda"):
         if net.cls_loss != "focal":
             raise ValueError("network.cls_loss = %r: %s keeps softmax cross-entropy (qfl / vfl are retinanet options)"
                              % (net.cls_loss, net.type))
+        if net.reg_max != 0:
+            raise ValueError("network.reg_max = %r: %s regresses plain deltas (the distribution box head is a retinanet "
+                             "option)" % (net.reg_max, net.type))
         if net.assigner != "max_iou":
             raise ValueError("network.assigner = %r: %s keeps the RPN's sampler (atss is a retinanet option)"
                              % (net.assigner, net.type))
@@ -29,7 +32,8 @@ def build_detector(cfg, device="cuda"):
         model = RetinaNet(device, depth=net.backbone_depth, num_classes=net.num_classes - 1, seed=net.seed, **dcn, **reg,
                           assigner=str(net.assigner), atss_topk=net.atss_topk, anchor_ratios=tuple(net.anchor_ratios),
                           anchor_scales_per_octave=net.anchor_scales_per_octave, anchor_scale=float(net.anchor_scale),
-                          cls_loss=str(net.cls_loss), cls_loss_alpha=net.cls_loss_alpha, cls_loss_gamma=net.cls_loss_gamma)
+                          cls_loss=str(net.cls_loss), cls_loss_alpha=net.cls_loss_alpha, cls_loss_gamma=net.cls_loss_gamma,
+                          reg_max=net.reg_max, dfl_weight=net.dfl_weight)
     else:
         raise ValueError("unknown network.type %r" % (net.type,))
     if net.pretrained:

@@ -2,7 +2,7 @@
 on hand-written HIP kernels, same arena / graph / data-parallel machinery as Faster R-CNN."""
 import torch
 
-from ..core.loss import check_cls_loss, check_reg_loss
+from ..core.loss import check_cls_loss, check_reg_loss, check_reg_max
 from .backbones import ResNet
 from .necks.fpn import RetinaFPN
 from .rpn_heads.retina_head import RetinaHead, check_assigner
@@ -25,7 +25,8 @@ def check_anchor_setting(anchor_ratios, anchor_scales_per_octave, anchor_scale):
 class RetinaNet(DetectorBase):
     def __init__(self, device="cuda", depth=101, num_classes=80, seed=7, dcn_stages=(), dcn_modulated=True, dcn_groups=1,
                  reg_loss="smooth_l1", reg_loss_weight=1.0, assigner="max_iou", atss_topk=9, anchor_ratios=(0.5, 1.0, 2.0),
-                 anchor_scales_per_octave=3, anchor_scale=4.0, cls_loss="focal", cls_loss_alpha=None, cls_loss_gamma=None):
+                 anchor_scales_per_octave=3, anchor_scale=4.0, cls_loss="focal", cls_loss_alpha=None, cls_loss_gamma=None,
+                 reg_max=0, dfl_weight=0.25):
         """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
         reg_loss / reg_loss_weight: the head's box loss -- 'smooth_l1', or 'iou' / 'giou' / 'diou' on the decoded box times
         reg_loss_weight (rpn_heads.RetinaHead).
@@ -33,8 +34,13 @@ class RetinaNet(DetectorBase):
         anchor_ratios / anchor_scales_per_octave / anchor_scale: the head's anchors per cell -- every ratio at the sizes
         anchor_scale * 2^(i / scales_per_octave) * stride, i < scales_per_octave (ATSS as published: (1.0,), 1, 8.0).
         cls_loss / cls_loss_alpha / cls_loss_gamma: the head's class loss -- 'focal', or 'qfl' / 'vfl' against the IoU of the
-        decoded box (rpn_heads.RetinaHead; needs an IoU-family reg_loss). The parameter layout does not depend on it."""
+        decoded box (rpn_heads.RetinaHead; needs an IoU-family reg_loss). The parameter layout does not depend on it.
+        reg_max / dfl_weight: reg_max > 0 = the distribution box head of Generalized Focal Loss -- retina.box_out emits
+        4 * (reg_max + 1) logits per anchor, the box is their integral decode (training and predict), the loss gains a third
+        component dfl_weight * DFL (rpn_heads.RetinaHead; needs an IoU-family reg_loss). As published: 16, 0.25 with ATSS,
+        qfl and reg_loss_weight 2. The layout of retina.box_out depends on it; load_checkpoint refuses the other layout."""
         check_reg_loss(reg_loss, reg_loss_weight)
+        check_reg_max(reg_max, reg_loss, dfl_weight)
         check_cls_loss(cls_loss, reg_loss, cls_loss_alpha, cls_loss_gamma)
         check_assigner(assigner, atss_topk)
         ratios, octave_scales = check_anchor_setting(anchor_ratios, anchor_scales_per_octave, anchor_scale)
@@ -44,7 +50,8 @@ class RetinaNet(DetectorBase):
         self.head = RetinaHead(256, self.strides, self.arena, self.ws, device, gen, num_classes=num_classes,
                                ratios=ratios, octave_scales=octave_scales, anchor_scale=float(anchor_scale),
                                reg_loss=reg_loss, reg_loss_weight=reg_loss_weight, assigner=assigner, atss_topk=atss_topk,
-                               cls_loss=cls_loss, cls_loss_alpha=cls_loss_alpha, cls_loss_gamma=cls_loss_gamma)
+                               cls_loss=cls_loss, cls_loss_alpha=cls_loss_alpha, cls_loss_gamma=cls_loss_gamma,
+                               reg_max=reg_max, dfl_weight=dfl_weight)
         self.mark_head = self.arena.size
         self.neck = RetinaFPN([512, 1024, 2048], 256, self.arena, self.ws, device, gen)
         self.mark_fpn = self.arena.size
@@ -80,9 +87,33 @@ class RetinaNet(DetectorBase):
         key = (score_thresh, nms_thresh, max_per_image, pre_nms_top_n, nms_method, soft_sigma)
         if getattr(self, "_det_key", None) != key:
             self._det = RetinaDetect(self.head.Cn, self.strides, self.head.base, pre_nms_top_n, score_thresh, nms_thresh,
-                                     max_per_image, nms_method=nms_method, soft_sigma=soft_sigma)
+                                     max_per_image, nms_method=nms_method, soft_sigma=soft_sigma, reg_max=self.head.reg_max)
             self._det_key = key
         return self._det(co, bo, im_info)
+
+    def load_checkpoint(self, path, strict=True):
+        """DetectorBase.load_checkpoint, after checking that the file's output layers have this head's layout: a plain-delta
+        file (4 rows per anchor) would otherwise load into the first rows of a distribution head, and the reverse fail
+        half way. The anchors per cell come from retina.cls_out (rows / classes), so 9 plain anchors (36 box rows) are not
+        taken for one anchor with reg_max = 8. Raises ValueError before any tensor is changed. The file is parsed once."""
+        from ..utils import load_params
+        blob = load_params(path)
+        h = self.head
+        box, cls = blob.get("arg:retina.box_out.weight"), blob.get("arg:retina.cls_out.weight")
+        fa = cls.shape[0] // h.Cn if cls is not None and cls.shape[0] % h.Cn == 0 else None    # the file's anchors per cell
+        bad_cls = cls is not None and cls.shape[0] != h.A * h.Cn
+        if (box is not None and box.shape[0] != h.reg_ch) or bad_cls:
+            rows = box.shape[0] if box is not None else None
+            a = fa if fa else h.A
+            if rows is not None and rows % (4 * a) == 0:
+                theirs = "%d anchors per cell x %d rows per anchor (reg_max = %d)" % (a, rows // a, rows // (4 * a) - 1)
+            else:
+                theirs = "no layout of %d anchors per cell" % a
+            raise ValueError("checkpoint retina.box_out has %s rows: %s; retina.cls_out has %s rows. The model's box_out has %d "
+                             "rows: %d anchors per cell x 4 x (reg_max + 1 = %d), its cls_out %d -- the layouts differ, build the "
+                             "model with the file's anchors and reg_max"
+                             % (rows, theirs, None if cls is None else cls.shape[0], h.reg_ch, h.A, h.reg_max + 1, h.A * h.Cn))
+        return super().load_checkpoint(path, strict, blob=blob)
 
     def forward_backward(self, image, gt_boxes, im_info, step=0, image_offset=0, step_dev=None, gt_masks=None):
         N, _, H, W = image.shape

@@ -30,16 +30,23 @@ class RetinaHead:
     def __init__(self, channels, strides, arena, ws, device, gen, num_classes=80, num_convs=4, ratios=(0.5, 1.0, 2.0),
                  octave_scales=(1.0, 2.0 ** (1.0 / 3.0), 2.0 ** (2.0 / 3.0)), anchor_scale=4.0, fg_thresh=0.5,
                  bg_thresh=0.4, alpha=0.25, gamma=2.0, sigma=3.0, prior=0.01, reg_loss="smooth_l1", reg_loss_weight=1.0,
-                 assigner="max_iou", atss_topk=9, cls_loss="focal", cls_loss_alpha=None, cls_loss_gamma=None):
+                 assigner="max_iou", atss_topk=9, cls_loss="focal", cls_loss_alpha=None, cls_loss_gamma=None, reg_max=0,
+                 dfl_weight=0.25):
         """assigner: 'max_iou' (fg_thresh / bg_thresh) or 'atss' (the atss_topk nearest anchors per level and GT).
         reg_loss: 'smooth_l1' on the encoded deltas (core.loss.retina_loss_level), or 'iou' / 'giou' / 'diou' on the
         decoded box times reg_loss_weight (core.loss.retina_loss_level_iou; stds 1, as the inference decode).
         cls_loss: 'focal' (alpha / gamma above, today's calls), or 'qfl' / 'vfl': the matched class column is trained
         against the IoU of the decoded box with its ground truth (core.loss.retina_loss_level_quality; needs an IoU-family
         reg_loss). cls_loss_alpha / cls_loss_gamma: None = the kind's published setting (QFL beta = 2 in gamma; VFL
-        alpha = 0.75, gamma = 2); with 'focal' they replace alpha / gamma when given."""
+        alpha = 0.75, gamma = 2); with 'focal' they replace alpha / gamma when given.
+        reg_max / dfl_weight: reg_max > 0 makes the box branch a distribution head (GFL, Li et al. 2020): 4 * (reg_max + 1)
+        logits per anchor, the box their integral decode, reg_loss on that box plus dfl_weight * DFL, any cls_loss
+        (core.loss.retina_loss_level_dfl; needs an IoU-family reg_loss). reg_max = 0: the plain deltas, today's calls."""
         L_.check_reg_loss(reg_loss, reg_loss_weight)
         check_assigner(assigner, atss_topk)
+        L_.check_reg_max(reg_max, reg_loss, dfl_weight)
+        self.reg_max, self.dfl_weight = int(reg_max), float(dfl_weight)
+        self.ncomp = 3 if self.reg_max > 0 else 2             # loss components: class, box (, DFL)
         quality = L_.check_cls_loss(cls_loss, reg_loss, cls_loss_alpha, cls_loss_gamma)
         self.cls_loss = cls_loss
         if quality is not None:
@@ -52,10 +59,11 @@ class RetinaHead:
         kw = dict(arena=arena, ws=ws, device=device, gen=gen)
         self.A, self.Cn = len(ratios) * len(octave_scales), num_classes
         self.ld_cls = (self.A * num_classes + 63) // 64 * 64
-        self.ld_reg = (self.A * 4 + 63) // 64 * 64
+        self.reg_ch = self.A * 4 * (self.reg_max + 1)       # real box channels: 4 deltas, or 4 sides of reg_max + 1 bins
+        self.ld_reg = (self.reg_ch + 63) // 64 * 64
         # registration = backward completion order
         self.cls_out = ConvLayer("retina.cls_out", channels, self.ld_cls, 3, init_std=0.01, cout_real=self.A * num_classes, **kw)
-        self.box_out = ConvLayer("retina.box_out", channels, self.ld_reg, 3, init_std=0.01, cout_real=self.A * 4, **kw)
+        self.box_out = ConvLayer("retina.box_out", channels, self.ld_reg, 3, init_std=0.01, cout_real=self.reg_ch, **kw)
         self.cls_convs = [ConvLayer("retina.cls%d" % i, channels, channels, 3, init_std=0.01, **kw)
                           for i in reversed(range(num_convs))][::-1]
         self.box_convs = [ConvLayer("retina.box%d" % i, channels, channels, 3, init_std=0.01, **kw)
@@ -98,8 +106,8 @@ class RetinaHead:
         self.cls_labels = torch.empty((N, At), dtype=torch.int32, device=dev)
         self.num_fg = torch.zeros((1,), dtype=torch.int32, device=dev)
         self.nparts = [L_.retina_loss_num_partials(N, H, W, self.A) for (H, W) in self.level_shapes]
-        self.partial = torch.zeros((2 * sum(self.nparts),), dtype=torch.float32, device=dev)
-        self.loss = torch.zeros((2,), dtype=torch.float32, device=dev)
+        self.partial = torch.zeros((self.ncomp * sum(self.nparts),), dtype=torch.float32, device=dev)
+        self.loss = torch.zeros((self.ncomp,), dtype=torch.float32, device=dev)
 
     def forward(self, P):
         """Layer i of BOTH towers on ALL levels is one grouped launch (10 independent convolutions): 5 launches for the
@@ -138,7 +146,13 @@ class RetinaHead:
         for l in range(len(self.co)):
             gc = self._buf("gco%d" % l, self.co[l].shape, zero=True)     # padding channels stay zero
             gb = self._buf("gbo%d" % l, self.bo[l].shape, zero=True)
-            if self.reg_loss == "smooth_l1":
+            if self.reg_max > 0:
+                alpha, gamma = (self.alpha, self.gamma) if self.cls_loss == "focal" else (self.cls_alpha, self.cls_gamma)
+                L_.retina_loss_level_dfl(self.co[l], self.bo[l], self.A, self.Cn, self.cls_labels, self.anchors, matched, gt_boxes,
+                                         self.level_offsets[l], self.cls_loss, alpha, gamma, self.reg_loss, self.reg_max,
+                                         float(self.strides[l]), self.reg_loss_weight, self.dfl_weight, self.num_fg, loss_scale,
+                                         gc, gb, self.partial[3 * off:])
+            elif self.reg_loss == "smooth_l1":
                 L_.retina_loss_level(self.co[l], self.bo[l], self.A, self.Cn, self.cls_labels, targets, self.level_offsets[l],
                                      self.alpha, self.gamma, self.sigma, self.num_fg, loss_scale, gc, gb, self.partial[2 * off:])
             elif self.cls_loss != "focal":
@@ -153,7 +167,7 @@ class RetinaHead:
             off += self.nparts[l]
             self.gco.append(gc)
             self.gbo.append(gb)
-        L_.loss_finalize(self.partial, off, 2, self.loss)
+        L_.loss_finalize(self.partial, off, self.ncomp, self.loss)
         return self.loss
 
     def backward(self, dP):

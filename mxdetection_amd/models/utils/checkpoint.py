@@ -102,10 +102,12 @@ class CheckpointMixin:
             blob["aux:momentum:" + e[0]] = self._to_mx(self.arena.view(i, "m"), by_name.get(e[0]))
         save_params(path, blob)
 
-    def load_checkpoint(self, path, strict=True):
-        """Inverse of save_checkpoint; refreshes the bf16 / transposed working copies. Returns the names not found."""
+    def load_checkpoint(self, path, strict=True, blob=None):
+        """Inverse of save_checkpoint; refreshes the bf16 / transposed working copies. Returns the names not found.
+        blob: the file's contents when the caller has parsed it already (utils.load_params(path))."""
         from ...utils import load_params
-        blob = load_params(path)
+        if blob is None:
+            blob = load_params(path)
         missing = []
         by_name = {}
         for name, kind, t, layer in self._named_tensors():

@@ -52,6 +52,8 @@ DEFAULTS = {
         "cls_loss": "focal",              # retinanet class loss: focal | qfl (Li et al. 2020) | vfl (Zhang et al. 2021); qfl / vfl need an IoU-family reg_loss
         "cls_loss_alpha": None,           # null = the kind's published setting (focal 0.25, vfl 0.75; qfl takes none)
         "cls_loss_gamma": None,           # null = the kind's published setting (focal 2, qfl beta = 2, vfl 2)
+        "reg_max": 0,                     # retinanet box branch: 0 = deltas (dx, dy, dw, dh); R > 0 = each side a distribution over 0..R strides, integral decode + DFL (Li et al. 2020; published 16; needs an IoU-family reg_loss)
+        "dfl_weight": 0.25,               # weight of the Distribution Focal Loss (reg_max > 0)
         "assigner": "max_iou",            # retinanet targets: max_iou (thresholds 0.5 / 0.4) | atss (Zhang et al. 2020). The RPN keeps its sampler
         "atss_topk": 9,                   # ATSS: candidates per ground-truth box and pyramid level (1..16)
         "anchor_ratios": [0.5, 1.0, 2.0],  # retinanet anchors per cell: these h/w ratios ...
