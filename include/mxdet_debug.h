@@ -66,11 +66,11 @@ int64_t mxdet_debug_get_tuning(int32_t which);
  *   MXDET_ROUTE_CONV_GROUPED  BM, BN, WM, WN, NS, DGRAD, 0, TAPS, 0, 0, 0, 0, 0, grid, items
  *   MXDET_ROUTE_WGRAD_GROUPED mixed grid (0 / 1 / 2 = MXDET_TUNE_T3_MIX in effect), ring depth three-tap tiles, ring depth
  *                             one-tap tiles (0 = none launched), grid_big, grid_wgrad, grid_reduce (after `parts`), parts
- *   MXDET_ROUTE_RETINA_LOSS   vec (1 = the 16-byte form retina_loss_vec_kernel, 0 = the scalar form: C, ld_cls or ld_reg not
+ *   MXDET_ROUTE_RETINA_LOSS   vec (1 = the 16-byte form retina_loss_kernel<true>, 0 = the scalar form: C, ld_cls or ld_reg not
  *                             a multiple of 8 / 8 / 4, or cls / grad_cls not 16-byte or reg / grad_reg not 8-byte aligned),
  *                             grid (= mxdet_retina_loss_num_partials)
- *   MXDET_ROUTE_RETINA_LOSS_IOU  the same two words for mxdet_retina_loss_level_iou (retina_loss_iou_kernel<vec>)
- *   MXDET_ROUTE_RETINA_LOSS_QUALITY  the same two words for mxdet_retina_loss_level_quality (retina_loss_quality_kernel<vec>)
+ *   MXDET_ROUTE_RETINA_LOSS_IOU  the same two words for mxdet_retina_loss_level_iou (retina_loss_iou_kernel<vec, false>)
+ *   MXDET_ROUTE_RETINA_LOSS_QUALITY  the same two words for mxdet_retina_loss_level_quality (retina_loss_iou_kernel<vec, true>)
  *   MXDET_ROUTE_RETINA_LOSS_DFL  the same two words for mxdet_retina_loss_level_dfl (retina_loss_dfl_kernel<vec, focal>) */
 #define MXDET_ROUTE_CONV 1
 #define MXDET_ROUTE_WGRAD 2

@@ -6,48 +6,9 @@
 // per bf16 logit). Scalar losses are reduced in a fixed order (per-block tree, then an index-ordered
 // single-workgroup pass), so repeated runs give identical bits.
 #include "common.h"
-#include "dist_box.h"
+#include "loss_elem.h"
 
 namespace mxdet {
-
-// deterministic block sum: fixed shuffle tree inside each wave, then wave partials added in order
-__device__ inline float block_sum_fixed(float v, float* smem /* >= blockDim/64 floats */) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-  int wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane_id() == 0) smem[wid] = v;
-  __syncthreads();
-  float s = 0.0f;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < nw; ++i) s += smem[i];
-  return s;  // valid on thread 0
-}
-
-__device__ __forceinline__ float softplus_neg_abs(float z) {
-  // log(1 + exp(-|z|))
-  float az = z < 0.0f ? -z : z;
-  return mxdet_logf(1.0f + mxdet_expf(-az));
-}
-// p = sigmoid(z), q = 1 - p and sp = log(1 + exp(-|z|)) from ONE exp(-|z|), each with its full relative accuracy at large |z|:
-// q is the other quotient of the same division, not 1.0f - p (which cancels once p is near 1), and sp keeps the part of t that
-// 1 + t rounds away (log1p: log(d) * t / (d - 1); d - 1 is exact, and sp = t once d rounds to 1). The focal terms
-// (1-p)^gamma * log p and p^gamma * log(1-p) of a well-classified element are products of exactly these small numbers.
-__device__ __forceinline__ void sigmoid_softplus(float z, float& p, float& q, float& sp) {
-  const float az = z < 0.0f ? -z : z;
-  const float t = mxdet_expf(-az);
-  const float d = 1.0f + t;
-  const float dm1 = d - 1.0f;
-  sp = dm1 == 0.0f ? t : mxdet_logf(d) * (t / dm1);
-  const float big = 1.0f / d, small = t / d;
-  p = z >= 0.0f ? big : small;
-  q = z >= 0.0f ? small : big;
-}
-__device__ __forceinline__ float sigmoidf_det(float z) {
-  // 1/(1+exp(-z)) evaluated on the stable side
-  if (z >= 0.0f) return 1.0f / (1.0f + mxdet_expf(-z));
-  float e = mxdet_expf(z);
-  return e / (1.0f + e);
-}
 
 // ---------------------------------------------------------------------------------------------
 __global__ void smooth_l1_fwd_kernel(const float* __restrict__ p, const float* __restrict__ t,
@@ -80,10 +41,13 @@ __global__ void count_fg_kernel(const int32_t* __restrict__ labels, long long n,
   if (lane_id() == 0 && m) atomicAdd(cnt, __popcll(m));
 }
 
+// The unfused class loss over [n, C] logits: sigmoid focal (FocalElem; quality is not read) or QFL / VFL (QualityElem) with a
+// per-row quality as the target of the row's own class column. Grid-stride, gradient in the logits' dtype.
+template <class Elem>
 __global__ void __launch_bounds__(256)
-focal_kernel(const void* __restrict__ logits, int dtype, const int32_t* __restrict__ labels,
-             long long n, int C, float alpha, float gamma, float grad_scale,
-             const int* __restrict__ num_fg, void* __restrict__ grad, float* __restrict__ partial) {
+cls_loss_kernel(const void* __restrict__ logits, int dtype, const int32_t* __restrict__ labels,
+                const float* __restrict__ quality, long long n, int C, const Elem elem, float grad_scale,
+                const int* __restrict__ num_fg, void* __restrict__ grad, float* __restrict__ partial) {
   __shared__ float red[8];
   const long long total = n * C;
   int nf = *num_fg;
@@ -94,28 +58,14 @@ focal_kernel(const void* __restrict__ logits, int dtype, const int32_t* __restri
     long long r = i / C;
     int c = (int)(i - r * C);
     int lab = labels[r];
-    float z = load_as_f32(logits, i, dtype);
     float g = 0.0f;
     if (lab >= 0) {
-      float p, q, sp;
-      sigmoid_softplus(z, p, q, sp);
-      // log(p) = -(max(-z,0) + sp); log(1-p) = -(max(z,0) + sp)
-      float logp = -((z < 0.0f ? -z : 0.0f) + sp);
-      float log1mp = -((z > 0.0f ? z : 0.0f) + sp);
-      if (lab == c + 1) {
-        float mod = (gamma == 2.0f) ? q * q : mxdet_expf(gamma * mxdet_logf(q > 1e-30f ? q : 1e-30f));
-        acc += -alpha * mod * logp;
-        g = -alpha * mod * (q - gamma * p * logp);
-      } else {
-        float mod = (gamma == 2.0f) ? p * p : mxdet_expf(gamma * mxdet_logf(p > 1e-30f ? p : 1e-30f));
-        acc += -(1.0f - alpha) * mod * log1mp;
-        g = (1.0f - alpha) * mod * (p - gamma * q * log1mp);
-      }
+      const bool positive = lab == c + 1;
+      acc += elem(load_as_f32(logits, i, dtype), positive, (Elem::kQuality && positive) ? quality[r] : 0.0f, g);
     }
     store_from_f32(grad, i, dtype, g * inv_norm * grad_scale);
   }
-  float s = block_sum_fixed(acc, red);
-  if (threadIdx.x == 0) partial[blockIdx.x] = s * inv_norm;
+  store_block_partials<1>({acc}, inv_norm, red, partial);
 }
 
 // out[j] = sum_i partial[i*ncomp + j], index-ordered, one workgroup
@@ -175,12 +125,7 @@ rpn_loss_kernel(const uint16_t* __restrict__ head, int N, int H, int W, int A, i
       }
     }
   }
-  float s0 = block_sum_fixed(lc, red);
-  float s1 = block_sum_fixed(lr, red);
-  if (threadIdx.x == 0) {
-    partial[2 * blockIdx.x + 0] = s0 * norm;
-    partial[2 * blockIdx.x + 1] = s1 * norm;
-  }
+  store_block_partials<2>({lc, lr}, norm, red, partial);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -250,118 +195,6 @@ rcnn_loss_kernel(const void* __restrict__ cls, const void* __restrict__ reg, int
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// IoU / GIoU / DIoU loss on the decoded box. Everything is evaluated relative to the box's own corner
-// (x1, y1): in absolute image coordinates the corners cancel at ulp(1300) = 1.2e-4 px against boxes a few pixels wide.
-struct BoxStds { float x, y, w, h; };
-
-// d max(a, b) / da: 1, 0 or -- at an exact tie -- the mean of the two one-sided derivatives
-__device__ __forceinline__ float tie_step(float a, float b) { return a > b ? 1.0f : (a == b ? 0.5f : 0.0f); }
-
-// 16 bytes at a 4-byte aligned address (rows of gt_boxes [.,5] are 20 bytes apart)
-__device__ __forceinline__ float4 load_f4_a4(const float* p) {
-  typedef float f4a4_t __attribute__((ext_vector_type(4), aligned(4)));
-  const f4a4_t v = *(const f4a4_t*)p;
-  return make_float4(v.x, v.y, v.z, v.w);
-}
-
-// The IoU core, shared by the delta decode below and the integral decode of the distribution head. Per
-// axis k, in any common origin: predicted corners p1 / p2, centre pc and "+1" length pl; ground-truth corners g1 / g2.
-// Returns L. Outputs per axis: d1 / d2 = dL / d p1, p2 through the min / max corners only, gp = dL / d pc through the DIoU
-// centre term only, da = dL / d pl through the area only. iou (optional): inter / union -- the quality of the quality-aware
-// class losses; 1 - L is not it, GIoU and DIoU add terms.
-__device__ __forceinline__ float box_iou_core(const float* p1, const float* p2, const float* pc, const float* pl,
-                                              const float* g1, const float* g2, const int kind, float* d1, float* d2,
-                                              float* gp, float* da, float* iou) {
-  float gl[2], il[2], cl[2], a1[2], a2[2], st[2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    gl[k] = g2[k] - g1[k] + 1.0f;
-    a1[k] = tie_step(p1[k], g1[k]);                   // share of p1 in max(p1, g1)
-    a2[k] = tie_step(g2[k], p2[k]);                   // share of p2 in min(p2, g2)
-    const float lo = p1[k] > g1[k] ? p1[k] : g1[k], hi = p2[k] < g2[k] ? p2[k] : g2[k];
-    const float r = hi - lo + 1.0f;
-    st[k] = tie_step(r, 0.0f);
-    il[k] = r > 0.0f ? r : 0.0f;
-    cl[k] = (p2[k] > g2[k] ? p2[k] : g2[k]) - (p1[k] < g1[k] ? p1[k] : g1[k]) + 1.0f;
-  }
-  const float inter = il[0] * il[1];
-  const float uni = pl[0] * pl[1] + gl[0] * gl[1] - inter;
-  float L = 1.0f - inter / uni;
-  if (iou) *iou = inter / uni;
-  const float iu2 = 1.0f / (uni * uni);
-  float dI = -(uni + inter) * iu2, dA = inter * iu2;   // dL / d inter, dL / d (pl0 * pl1)
-  float gc[2] = {0.0f, 0.0f};                          // dL / d cl[k]
-  gp[0] = 0.0f;
-  gp[1] = 0.0f;
-  if (kind == MXDET_IOU_LOSS_GIOU) {
-    const float C = cl[0] * cl[1], ic = 1.0f / C;
-    L += (C - uni) * ic;
-    dI += ic;
-    dA -= ic;
-    const float dC = uni * ic * ic;
-    gc[0] = dC * cl[1];
-    gc[1] = dC * cl[0];
-  } else if (kind == MXDET_IOU_LOSS_DIOU) {
-    const float e0 = pc[0] - 0.5f * (g1[0] + g2[0]), e1 = pc[1] - 0.5f * (g1[1] + g2[1]);
-    const float rho = e0 * e0 + e1 * e1, iD = 1.0f / (cl[0] * cl[0] + cl[1] * cl[1]);
-    L += rho * iD;
-    const float q = -2.0f * rho * iD * iD;
-    gc[0] = q * cl[0];
-    gc[1] = q * cl[1];
-    gp[0] = 2.0f * e0 * iD;
-    gp[1] = 2.0f * e1 * iD;
-  }
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const float gi = dI * il[1 - k] * st[k];
-    d2[k] = gi * a2[k] + gc[k] * (1.0f - a2[k]);
-    d1[k] = -(gi * a1[k] + gc[k] * (1.0f - a1[k]));
-    da[k] = dA * pl[1 - k];
-  }
-  return L;
-}
-
-// b: roi / anchor, g: ground truth (absolute corners), d: raw deltas. Returns L, gd[4] = dL / d(raw delta).
-// iou (optional): see box_iou_core. Callers that pass none compile to what they were.
-__device__ __forceinline__ float box_iou_loss_elem(const float4 b, const float4 g, const float* d, const BoxStds sd,
-                                                   const int kind, float* gd, float* iou = nullptr) {
-  const float b1[2] = {b.x, b.y}, b2[2] = {b.z, b.w}, ga[2] = {g.x, g.y}, gb[2] = {g.z, g.w};
-  const float sc[2] = {sd.x, sd.y}, ss[2] = {sd.w, sd.h};
-  float len[2], pc[2], pl[2], p1[2], p2[2], g1[2], g2[2], ck[2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    g1[k] = ga[k] - b1[k];
-    g2[k] = gb[k] - b1[k];
-    len[k] = b2[k] - b1[k] + 1.0f;
-    const float c0 = 0.5f * (len[k] - 1.0f);
-    float t = d[2 + k] * ss[k];
-    ck[k] = tie_step(MXDET_BBOX_XFORM_CLIP, t);
-    if (t > MXDET_BBOX_XFORM_CLIP) t = MXDET_BBOX_XFORM_CLIP;
-    float c = d[k] * sc[k];
-    c = c * len[k];
-    pc[k] = c + c0;
-    pl[k] = mxdet_expf(t) * len[k];
-    const float hl = 0.5f * (pl[k] - 1.0f);
-    p1[k] = pc[k] - hl;
-    p2[k] = pc[k] + hl;
-  }
-  float d1[2], d2[2], gp[2], da[2];
-  const float L = box_iou_core(p1, p2, pc, pl, g1, g2, kind, d1, d2, gp, da, iou);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const float dpl = da[k] + 0.5f * (d2[k] - d1[k]);
-    gd[k] = (d1[k] + d2[k] + gp[k]) * (sc[k] * len[k]);
-    gd[2 + k] = dpl * (pl[k] * ss[k]) * ck[k];
-  }
-  return L;
-}
-
-__device__ __forceinline__ void load_deltas4(const void* p, long long i, int dtype, float* d) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) d[k] = load_as_f32(p, i + k, dtype);
-}
-
 // the unfused primitive: one thread per box
 __global__ void __launch_bounds__(256)
 box_iou_loss_kernel(const float4* __restrict__ boxes, const float4* __restrict__ gt, const void* __restrict__ deltas,
@@ -417,68 +250,26 @@ rcnn_loss_iou_kernel(const void* __restrict__ cls, const void* __restrict__ reg,
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Quality-aware class losses: the matched class column is trained against y = the IoU of the predicted box
-// with its ground truth (a constant of the class loss), every other element against y = 0.
-//   QFL (Li et al. 2020):   L = |y - s|^beta * BCE(s, y), beta in `gamma`; alpha unused
-//   VFL (Zhang et al. 2021): y > 0: L = y * BCE(s, y);  y == 0: L = -alpha * s^gamma * log(1 - s)
-// One element: logit x, target y in [0, 1]. Returns L, g = dL / dx. The logs are those of the focal code.
-__device__ __forceinline__ float quality_cls_elem(const float x, const float y, const int cls_kind, const float alpha,
-                                                  const float gamma, float& g) {
-  float p, q, sp;
-  sigmoid_softplus(x, p, q, sp);
-  const float logp = -((x < 0.0f ? -x : 0.0f) + sp);
-  const float log1mp = -((x > 0.0f ? x : 0.0f) + sp);
-  if (cls_kind == MXDET_CLS_LOSS_QFL) {
-    const float e = p - y;
-    const float bce = -y * logp - (1.0f - y) * log1mp;
-    float mod, dmod;                                       // |e|^beta and beta * |e|^(beta - 1) * sign(e)
-    if (gamma == 2.0f) {
-      mod = e * e;
-      dmod = 2.0f * e;
-    } else {
-      const float ae = e < 0.0f ? -e : e, aec = ae > 1e-30f ? ae : 1e-30f;
-      mod = mxdet_expf(gamma * mxdet_logf(aec));
-      dmod = gamma * (mod / aec);
-      if (e < 0.0f) dmod = -dmod;
-    }
-    g = dmod * (p * q) * bce + mod * e;
-    return mod * bce;
-  }
-  // both sides and two selects: a branch on y would split nearly every wave that holds a foreground anchor
-  const float bce = -y * logp - (1.0f - y) * log1mp;
-  const float mod = (gamma == 2.0f) ? p * p : mxdet_expf(gamma * mxdet_logf(p > 1e-30f ? p : 1e-30f));
-  const float gneg = alpha * (gamma * mod * q * (-log1mp) + mod * p);
-  const float lneg = -alpha * mod * log1mp;
-  g = y > 0.0f ? y * (p - y) : gneg;
-  return y > 0.0f ? y * bce : lneg;
-}
-
-// the unfused primitive: focal_kernel with a per-row quality as the target of the row's own class column
+// the unfused primitive: four lanes per row
 __global__ void __launch_bounds__(256)
-quality_focal_loss_kernel(const void* __restrict__ logits, int dtype, const int32_t* __restrict__ labels,
-                          const float* __restrict__ quality, long long n, int C, int cls_kind, float alpha, float gamma,
-                          float grad_scale, const int* __restrict__ num_fg, void* __restrict__ grad,
-                          float* __restrict__ partial) {
-  __shared__ float red[8];
-  const long long total = n * C;
-  int nf = *num_fg;
-  float inv_norm = 1.0f / (float)(nf > 1 ? nf : 1);
-  float acc = 0.0f;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    long long r = i / C;
-    int c = (int)(i - r * C);
-    int lab = labels[r];
-    float g = 0.0f;
-    if (lab >= 0) {
-      const float y = (lab == c + 1) ? quality[r] : 0.0f;
-      acc += quality_cls_elem(load_as_f32(logits, i, dtype), y, cls_kind, alpha, gamma, g);
-    }
-    store_from_f32(grad, i, dtype, g * inv_norm * grad_scale);
+box_dist_loss_kernel(const float4* __restrict__ boxes, const float4* __restrict__ gt, const void* __restrict__ logits,
+                     int dtype, int ld, long long n, int R, float stride, int kind, float reg_weight, float dfl_weight,
+                     float grad_scale, float* __restrict__ loss_box, float* __restrict__ loss_dfl,
+                     float* __restrict__ quality, void* __restrict__ grad) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long i = t >> 2;
+  const int side = (int)(t & 3);
+  if (i >= n) return;                                     // whole quads leave together
+  float dfl, q;
+  const float L = dist_box_quad(logits, i * ld + side * (R + 1), dtype, R, side, boxes[i], gt[i], stride, kind, reg_weight,
+                                dfl_weight, grad_scale, grad, dfl, q);
+  const int q0 = lane_id() & ~3;
+  const float dsum = ((__shfl(dfl, q0 + 0) + __shfl(dfl, q0 + 1)) + __shfl(dfl, q0 + 2)) + __shfl(dfl, q0 + 3);
+  if (side == 0) {
+    loss_box[i] = reg_weight * L;
+    loss_dfl[i] = dfl_weight * 0.25f * dsum;
+    if (quality) quality[i] = q;
   }
-  float s = block_sum_fixed(acc, red);
-  if (threadIdx.x == 0) partial[blockIdx.x] = s * inv_norm;
 }
 
 }  // namespace mxdet
@@ -515,6 +306,24 @@ extern "C" size_t mxdet_loss_workspace_bytes(int64_t n) {
   return (a > b ? a : b) + 256;
 }
 
+// count the foreground rows, run cls_loss_kernel<Elem>, finalize: the two unfused class-loss entries after their checks
+template <class Elem>
+static int cls_loss_launch(const char* entry, const void* logits, int32_t dtype, const int32_t* labels, const float* quality,
+                           int64_t n, int32_t C, const Elem elem, float grad_scale, float* loss_out, void* grad_logits,
+                           void* workspace, hipStream_t s) {
+  int* cnt = (int*)workspace;
+  float* partial = (float*)((char*)workspace + 256);
+  hipError_t e = zero_async(cnt, 256, s);
+  MXDET_REQUIRE(e == hipSuccess, MXDET_EHIP, "%s: memset failed", entry);
+  hipLaunchKernelGGL(count_fg_kernel, dim3((unsigned)ceil_div<int64_t>(n, 256)), dim3(256), 0, s, labels, (long long)n, cnt);
+  long long total = (long long)n * C;
+  int blocks = (int)(ceil_div<long long>(total, 256) < 2048 ? ceil_div<long long>(total, 256) : 2048);
+  hipLaunchKernelGGL(cls_loss_kernel<Elem>, dim3(blocks), dim3(256), 0, s, logits, dtype, labels, quality, (long long)n, C, elem,
+                     grad_scale, cnt, grad_logits, partial);
+  hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, partial, blocks, 1, loss_out);
+  return check_launch(entry);
+}
+
 extern "C" int mxdet_focal_loss(const void* logits, int32_t dtype, const int32_t* labels, int64_t n,
                                 int32_t C, float alpha, float gamma, float grad_scale,
                                 float* loss_out, void* grad_logits, void* workspace,
@@ -525,22 +334,9 @@ extern "C" int mxdet_focal_loss(const void* logits, int32_t dtype, const int32_t
   MXDET_REQUIRE(logits && labels && loss_out && grad_logits, MXDET_EINVAL, "focal_loss: null pointer");
   MXDET_REQUIRE(workspace && workspace_bytes >= mxdet_loss_workspace_bytes(n), MXDET_EWORKSPACE,
                 "focal_loss: workspace too small");
-  hipStream_t s = as_stream(stream);
-  int* cnt = (int*)workspace;
-  float* partial = (float*)((char*)workspace + 256);
-  hipError_t e = zero_async(cnt, 256, s);
-  MXDET_REQUIRE(e == hipSuccess, MXDET_EHIP, "focal_loss: memset failed");
-  hipLaunchKernelGGL(count_fg_kernel, dim3((unsigned)ceil_div<int64_t>(n, 256)), dim3(256), 0, s,
-                     labels, (long long)n, cnt);
-  long long total = (long long)n * C;
-  int blocks = (int)(ceil_div<long long>(total, 256) < 2048 ? ceil_div<long long>(total, 256) : 2048);
-  hipLaunchKernelGGL(focal_kernel, dim3(blocks), dim3(256), 0, s, logits, dtype, labels, (long long)n,
-                     C, alpha, gamma, grad_scale, cnt, grad_logits, partial);
-  hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, partial, blocks, 1, loss_out);
-  return check_launch("focal_loss");
+  return cls_loss_launch("focal_loss", logits, dtype, labels, nullptr, n, C, FocalElem{alpha, gamma}, grad_scale, loss_out,
+                         grad_logits, workspace, as_stream(stream));
 }
-
-static bool cls_kind_ok(int32_t k) { return k == MXDET_CLS_LOSS_QFL || k == MXDET_CLS_LOSS_VFL; }
 
 extern "C" int mxdet_quality_focal_loss(const void* logits, int32_t dtype, const int32_t* labels, const float* quality,
                                         int64_t n, int32_t C, int32_t cls_kind, float alpha, float gamma, float grad_scale,
@@ -561,17 +357,8 @@ extern "C" int mxdet_quality_focal_loss(const void* logits, int32_t dtype, const
   MXDET_REQUIRE(logits && labels && quality && grad_logits, MXDET_EINVAL, "quality_focal_loss: null pointer");
   MXDET_REQUIRE(workspace && workspace_bytes >= mxdet_loss_workspace_bytes(n), MXDET_EWORKSPACE,
                 "quality_focal_loss: workspace too small");
-  int* cnt = (int*)workspace;
-  float* partial = (float*)((char*)workspace + 256);
-  hipError_t e = zero_async(cnt, 256, s);
-  MXDET_REQUIRE(e == hipSuccess, MXDET_EHIP, "quality_focal_loss: memset failed");
-  hipLaunchKernelGGL(count_fg_kernel, dim3((unsigned)ceil_div<int64_t>(n, 256)), dim3(256), 0, s, labels, (long long)n, cnt);
-  long long total = (long long)n * C;
-  int blocks = (int)(ceil_div<long long>(total, 256) < 2048 ? ceil_div<long long>(total, 256) : 2048);
-  hipLaunchKernelGGL(quality_focal_loss_kernel, dim3(blocks), dim3(256), 0, s, logits, dtype, labels, quality, (long long)n, C,
-                     cls_kind, alpha, gamma, grad_scale, cnt, grad_logits, partial);
-  hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, partial, blocks, 1, loss_out);
-  return check_launch("quality_focal_loss");
+  return cls_loss_launch("quality_focal_loss", logits, dtype, labels, quality, n, C, QualityElem{cls_kind, alpha, gamma},
+                         grad_scale, loss_out, grad_logits, workspace, s);
 }
 
 extern "C" int32_t mxdet_rpn_loss_num_partials(int32_t N, int32_t H, int32_t W) {
@@ -633,11 +420,6 @@ extern "C" int mxdet_rcnn_loss(const void* cls_logits, const void* bbox_pred, in
   return check_launch("rcnn_loss");
 }
 
-static bool iou_kind_ok(int32_t kind) {
-  return kind == MXDET_IOU_LOSS_IOU || kind == MXDET_IOU_LOSS_GIOU || kind == MXDET_IOU_LOSS_DIOU;
-}
-static bool stds_ok(float a, float b, float c, float d) { return a > 0.0f && b > 0.0f && c > 0.0f && d > 0.0f; }
-
 extern "C" int mxdet_box_iou_loss(const float* boxes, const float* gt, const void* deltas, int32_t dtype, int32_t ld,
                                   const float* weight, int64_t n, int32_t kind, float std_x, float std_y, float std_w,
                                   float std_h, float grad_scale, float* loss, void* grad_deltas, mxdet_stream_t stream) {
@@ -685,739 +467,6 @@ extern "C" int mxdet_rcnn_loss_iou(const void* cls_logits, const void* bbox_pred
   return check_launch("rcnn_loss_iou");
 }
 
-// ------------------------------------------------------------------------------------------------
-// RetinaNet (BASELINE.json config 5): dense-anchor class labels and the fused focal + box loss of one level.
-namespace mxdet {
-
-// cls_label = class of the matched GT for foreground anchors, else the {-1, 0} label itself
-__global__ void anchor_class_labels_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict__ matched,
-                                           const float* __restrict__ gt, long long A_total, int G_max, long long total,
-                                           int32_t* __restrict__ cls_labels, int* __restrict__ num_fg) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  int lab = -1;
-  bool fg = false;
-  if (i < total) {
-    lab = labels[i];
-    if (lab == 1) {
-      int n = (int)(i / A_total);
-      lab = (int)gt[((long long)n * G_max + matched[i]) * 5 + 4];
-      fg = true;
-    }
-    cls_labels[i] = lab;
-  }
-  unsigned long long m = __ballot(fg);
-  if (lane_id() == 0 && m) atomicAdd(num_fg, __popcll(m));
-}
-
-// focal half of the vector form: the workgroup's 256 anchors, 16 bytes of class logits per lane and step. Returns this
-// thread's loss sum. Shared by retina_loss_vec_kernel and retina_loss_iou_kernel<true>: same code, same bits.
-__device__ __forceinline__ float retina_focal_vec(const uint16_t* __restrict__ cls, int HW, int A, int C, int ld_cls,
-                                                  const int32_t* __restrict__ cls_labels, long long A_total,
-                                                  long long level_offset, float alpha, float gamma, float inv,
-                                                  float loss_scale, long long a_first, long long total,
-                                                  uint16_t* __restrict__ gcls) {
-  const int CH = C >> 3;
-  float lc = 0.0f;
-  for (int it = threadIdx.x; it < 256 * CH; it += 256) {
-    const int al = it / CH, ck = it - al * CH;
-    const long long idx = a_first + al;
-    if (idx >= total) continue;
-    const int a = (int)(idx % A);
-    const long long cell = idx / A;
-    const int n = (int)(cell / HW);
-    const long long local = cell - (long long)n * HW;
-    const int lab = cls_labels[(long long)n * A_total + level_offset + local * A + a];
-    const long long off = cell * ld_cls + (long long)a * C + ck * 8;
-    uint4 o = make_uint4(0u, 0u, 0u, 0u);
-    if (lab >= 0) {
-      const uint4 zv = *(const uint4*)(cls + off);
-      const unsigned zw[4] = {zv.x, zv.y, zv.z, zv.w};
-      unsigned ow[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        unsigned packed = 0u;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int c = ck * 8 + 2 * k + h;
-          const float x = h ? __uint_as_float(zw[k] & 0xffff0000u) : __uint_as_float(zw[k] << 16);
-          float p, q, sp;
-          sigmoid_softplus(x, p, q, sp);
-          const float logp = -((x < 0.0f ? -x : 0.0f) + sp);
-          const float log1mp = -((x > 0.0f ? x : 0.0f) + sp);
-          float g;
-          if (lab == c + 1) {
-            const float mod = (gamma == 2.0f) ? q * q : mxdet_expf(gamma * mxdet_logf(q > 1e-30f ? q : 1e-30f));
-            lc += -alpha * mod * logp;
-            g = -alpha * mod * (q - gamma * p * logp);
-          } else {
-            const float mod = (gamma == 2.0f) ? p * p : mxdet_expf(gamma * mxdet_logf(p > 1e-30f ? p : 1e-30f));
-            lc += -(1.0f - alpha) * mod * log1mp;
-            g = (1.0f - alpha) * mod * (p - gamma * q * log1mp);
-          }
-          packed |= (unsigned)f32_to_bf16_bits(g * inv * loss_scale) << (16 * h);
-        }
-        ow[k] = packed;
-      }
-      o = make_uint4(ow[0], ow[1], ow[2], ow[3]);
-    }
-    *(uint4*)(gcls + off) = o;
-  }
-  return lc;
-}
-
-// one thread per (cell, anchor): C contiguous class logits at cls[cell*ld_cls + a*C], 4 deltas at reg[cell*ld_reg + a*4]
-// Vectorised form (C % 8 == 0): a workgroup still owns 256 consecutive anchors (so the partial-sum layout is unchanged),
-// but the class logits are walked 16 bytes per lane with consecutive lanes on consecutive addresses -- the scalar form
-// below has every lane striding C*2 bytes apart with 2-byte accesses (920 us per step on RetinaNet-R101 for 129 MB).
-__global__ void __launch_bounds__(256)
-retina_loss_vec_kernel(const uint16_t* __restrict__ cls, const uint16_t* __restrict__ reg, int N, int HW, int A, int C,
-                       int ld_cls, int ld_reg, const int32_t* __restrict__ cls_labels,
-                       const float4* __restrict__ targets, long long A_total, long long level_offset, float alpha,
-                       float gamma, float sigma2, const int* __restrict__ num_fg, float loss_scale,
-                       uint16_t* __restrict__ gcls, uint16_t* __restrict__ greg, float* __restrict__ partial) {
-  __shared__ float red[8];
-  const long long total = (long long)N * HW * A;
-  const long long a_first = (long long)blockIdx.x * 256;
-  const int nf = *num_fg;
-  const float inv = 1.0f / (float)(nf > 1 ? nf : 1);
-  const float lc = retina_focal_vec(cls, HW, A, C, ld_cls, cls_labels, A_total, level_offset, alpha, gamma, inv, loss_scale,
-                                    a_first, total, gcls);
-  float lr = 0.0f;
-  {   // box part: one lane per anchor, 8 bytes in, 8 bytes out
-    const long long idx = a_first + threadIdx.x;
-    if (idx < total) {
-      const int a = (int)(idx % A);
-      const long long cell = idx / A;
-      const int n = (int)(cell / HW);
-      const long long local = cell - (long long)n * HW;
-      const long long gi = (long long)n * A_total + level_offset + local * A + a;
-      const int lab = cls_labels[gi];
-      const uint16_t* d = reg + cell * ld_reg + a * 4;
-      uint16_t* gd = greg + cell * ld_reg + a * 4;
-      uint2 go = make_uint2(0u, 0u);
-      if (lab > 0) {
-        const float4 t = targets[gi];
-        const uint2 dv = *(const uint2*)d;
-        float dd[4];
-        unpack4_bf16(dv, dd);
-        const float tt[4] = {t.x, t.y, t.z, t.w};
-        unsigned short gb[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float e = dd[k] - tt[k];
-          lr += mxdet_smooth_l1(e, sigma2);
-          gb[k] = f32_to_bf16_bits(mxdet_smooth_l1_grad(e, sigma2) * inv * loss_scale);
-        }
-        go = make_uint2((unsigned)gb[0] | ((unsigned)gb[1] << 16), (unsigned)gb[2] | ((unsigned)gb[3] << 16));
-      }
-      *(uint2*)gd = go;
-    }
-  }
-  float s0 = block_sum_fixed(lc, red);
-  float s1 = block_sum_fixed(lr, red);
-  if (threadIdx.x == 0) {
-    partial[2 * blockIdx.x + 0] = s0 * inv;
-    partial[2 * blockIdx.x + 1] = s1 * inv;
-  }
-}
-
-// focal half of the scalar form: the C class logits of one anchor. Shared with retina_loss_iou_kernel<false>.
-__device__ __forceinline__ float retina_focal_anchor(const uint16_t* __restrict__ z, int C, int lab, float alpha, float gamma,
-                                                     float inv, float loss_scale, uint16_t* __restrict__ gz) {
-  float lc = 0.0f;
-  for (int c = 0; c < C; ++c) {
-    float g = 0.0f;
-    if (lab >= 0) {
-      float x = bf16_bits_to_f32(z[c]);
-      float p, q, sp;
-      sigmoid_softplus(x, p, q, sp);
-      float logp = -((x < 0.0f ? -x : 0.0f) + sp);
-      float log1mp = -((x > 0.0f ? x : 0.0f) + sp);
-      if (lab == c + 1) {
-        float mod = (gamma == 2.0f) ? q * q : mxdet_expf(gamma * mxdet_logf(q > 1e-30f ? q : 1e-30f));
-        lc += -alpha * mod * logp;
-        g = -alpha * mod * (q - gamma * p * logp);
-      } else {
-        float mod = (gamma == 2.0f) ? p * p : mxdet_expf(gamma * mxdet_logf(p > 1e-30f ? p : 1e-30f));
-        lc += -(1.0f - alpha) * mod * log1mp;
-        g = (1.0f - alpha) * mod * (p - gamma * q * log1mp);
-      }
-    }
-    gz[c] = f32_to_bf16_bits(g * inv * loss_scale);
-  }
-  return lc;
-}
-
-__global__ void __launch_bounds__(256)
-retina_loss_kernel(const uint16_t* __restrict__ cls, const uint16_t* __restrict__ reg, int N, int HW, int A, int C,
-                   int ld_cls, int ld_reg, const int32_t* __restrict__ cls_labels, const float4* __restrict__ targets,
-                   long long A_total, long long level_offset, float alpha, float gamma, float sigma2,
-                   const int* __restrict__ num_fg, float loss_scale, uint16_t* __restrict__ gcls,
-                   uint16_t* __restrict__ greg, float* __restrict__ partial) {
-  __shared__ float red[8];
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long total = (long long)N * HW * A;
-  const int nf = *num_fg;
-  const float inv = 1.0f / (float)(nf > 1 ? nf : 1);
-  float lc = 0.0f, lr = 0.0f;
-  if (idx < total) {
-    const int a = (int)(idx % A);
-    const long long cell = idx / A;                 // n*HW + local cell
-    const int n = (int)(cell / HW);
-    const long long local = cell - (long long)n * HW;
-    const long long gi = (long long)n * A_total + level_offset + local * A + a;
-    const int lab = cls_labels[gi];
-    const uint16_t* z = cls + cell * ld_cls + (long long)a * C;
-    uint16_t* gz = gcls + cell * ld_cls + (long long)a * C;
-    lc = retina_focal_anchor(z, C, lab, alpha, gamma, inv, loss_scale, gz);
-    const uint16_t* d = reg + cell * ld_reg + a * 4;
-    uint16_t* gd = greg + cell * ld_reg + a * 4;
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (lab > 0) t = targets[gi];
-    const float tt[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float g = 0.0f;
-      if (lab > 0) {
-        float e = bf16_bits_to_f32(d[k]) - tt[k];
-        lr += mxdet_smooth_l1(e, sigma2);
-        g = mxdet_smooth_l1_grad(e, sigma2) * inv * loss_scale;
-      }
-      gd[k] = f32_to_bf16_bits(g);
-    }
-  }
-  float s0 = block_sum_fixed(lc, red);
-  float s1 = block_sum_fixed(lr, red);
-  if (threadIdx.x == 0) {
-    partial[2 * blockIdx.x + 0] = s0 * inv;
-    partial[2 * blockIdx.x + 1] = s1 * inv;
-  }
-}
-
-// The level loss with an IoU-family box term: grid, partial sums and the focal half are those of the two kernels above
-// (VEC = the 16-byte form). Box part: one lane per anchor -- anchor and GT row as 16-byte loads, the four deltas as one
-// 8-byte load (VEC) -- and nothing staged: it is a few bytes per anchor next to the C class logits.
-template <bool VEC>
-__global__ void __launch_bounds__(256)
-retina_loss_iou_kernel(const uint16_t* __restrict__ cls, const uint16_t* __restrict__ reg, int N, int HW, int A, int C,
-                       int ld_cls, int ld_reg, const int32_t* __restrict__ cls_labels, const float4* __restrict__ anchors,
-                       const int32_t* __restrict__ matched, const float* __restrict__ gt, int G_max, long long A_total,
-                       long long level_offset, float alpha, float gamma, int kind, BoxStds sd, float reg_weight,
-                       const int* __restrict__ num_fg, float loss_scale, uint16_t* __restrict__ gcls,
-                       uint16_t* __restrict__ greg, float* __restrict__ partial) {
-  __shared__ float red[8];
-  const long long total = (long long)N * HW * A;
-  const long long a_first = (long long)blockIdx.x * 256;
-  const long long idx = a_first + threadIdx.x;
-  const int nf = *num_fg;
-  const float inv = 1.0f / (float)(nf > 1 ? nf : 1);
-  float lc = 0.0f, lr = 0.0f;
-  if (VEC)
-    lc = retina_focal_vec(cls, HW, A, C, ld_cls, cls_labels, A_total, level_offset, alpha, gamma, inv, loss_scale, a_first,
-                          total, gcls);
-  if (idx < total) {
-    const int a = (int)(idx % A);
-    const long long cell = idx / A;
-    const int n = (int)(cell / HW);
-    const long long local = cell - (long long)n * HW;
-    const long long ai = level_offset + local * A + a;
-    const long long gi = (long long)n * A_total + ai;
-    const int lab = cls_labels[gi];
-    if (!VEC)
-      lc = retina_focal_anchor(cls + cell * ld_cls + (long long)a * C, C, lab, alpha, gamma, inv, loss_scale,
-                               gcls + cell * ld_cls + (long long)a * C);
-    const uint16_t* d = reg + cell * ld_reg + a * 4;
-    uint16_t* gd = greg + cell * ld_reg + a * 4;
-    unsigned short gb[4] = {0, 0, 0, 0};
-    const int m = lab > 0 ? matched[gi] : -1;
-    if (m >= 0 && m < G_max) {                          // a match outside gt_boxes: the anchor regresses nothing
-      float dd[4], g4[4];
-      if (VEC) {
-        unpack4_bf16(*(const uint2*)d, dd);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dd[k] = bf16_bits_to_f32(d[k]);
-      }
-      const float4 g = load_f4_a4(gt + ((long long)n * G_max + m) * 5);
-      lr = reg_weight * box_iou_loss_elem(anchors[ai], g, dd, sd, kind, g4);
-      const float gs = reg_weight * inv * loss_scale;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) gb[k] = f32_to_bf16_bits(g4[k] * gs);
-    }
-    if (VEC) {
-      *(uint2*)gd = make_uint2((unsigned)gb[0] | ((unsigned)gb[1] << 16), (unsigned)gb[2] | ((unsigned)gb[3] << 16));
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) gd[k] = gb[k];
-    }
-  }
-  float s0 = block_sum_fixed(lc, red);
-  float s1 = block_sum_fixed(lr, red);
-  if (threadIdx.x == 0) {
-    partial[2 * blockIdx.x + 0] = s0 * inv;
-    partial[2 * blockIdx.x + 1] = s1 * inv;
-  }
-}
-
-// Class walk of the 16-byte form with a quality target: the lane mapping of retina_focal_vec; qs[al] is the quality of the
-// workgroup's anchor al (0 unless it is foreground with a match inside gt_boxes), written by the box part.
-__device__ __forceinline__ float retina_quality_vec(const uint16_t* __restrict__ cls, int HW, int A, int C, int ld_cls,
-                                                    const int32_t* __restrict__ cls_labels, long long A_total,
-                                                    long long level_offset, int cls_kind, float alpha, float gamma, float inv,
-                                                    float loss_scale, long long a_first, long long total,
-                                                    const float* __restrict__ qs, uint16_t* __restrict__ gcls) {
-  const int CH = C >> 3;
-  float lc = 0.0f;
-  for (int it = threadIdx.x; it < 256 * CH; it += 256) {
-    const int al = it / CH, ck = it - al * CH;
-    const long long idx = a_first + al;
-    if (idx >= total) continue;
-    const int a = (int)(idx % A);
-    const long long cell = idx / A;
-    const int n = (int)(cell / HW);
-    const long long local = cell - (long long)n * HW;
-    const int lab = cls_labels[(long long)n * A_total + level_offset + local * A + a];
-    const long long off = cell * ld_cls + (long long)a * C + ck * 8;
-    uint4 o = make_uint4(0u, 0u, 0u, 0u);
-    if (lab >= 0) {
-      const float qa = qs[al];
-      const uint4 zv = *(const uint4*)(cls + off);
-      const unsigned zw[4] = {zv.x, zv.y, zv.z, zv.w};
-      unsigned ow[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        unsigned packed = 0u;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int c = ck * 8 + 2 * k + h;
-          const float x = h ? __uint_as_float(zw[k] & 0xffff0000u) : __uint_as_float(zw[k] << 16);
-          float g;
-          lc += quality_cls_elem(x, lab == c + 1 ? qa : 0.0f, cls_kind, alpha, gamma, g);
-          packed |= (unsigned)f32_to_bf16_bits(g * inv * loss_scale) << (16 * h);
-        }
-        ow[k] = packed;
-      }
-      o = make_uint4(ow[0], ow[1], ow[2], ow[3]);
-    }
-    *(uint4*)(gcls + off) = o;
-  }
-  return lc;
-}
-
-// class walk of the scalar form: the C logits of one anchor, its quality in a register
-__device__ __forceinline__ float retina_quality_anchor(const uint16_t* __restrict__ z, int C, int lab, float qa, int cls_kind,
-                                                       float alpha, float gamma, float inv, float loss_scale,
-                                                       uint16_t* __restrict__ gz) {
-  float lc = 0.0f;
-  for (int c = 0; c < C; ++c) {
-    float g = 0.0f;
-    if (lab >= 0) lc += quality_cls_elem(bf16_bits_to_f32(z[c]), lab == c + 1 ? qa : 0.0f, cls_kind, alpha, gamma, g);
-    gz[c] = f32_to_bf16_bits(g * inv * loss_scale);
-  }
-  return lc;
-}
-
-// The level loss with a quality-aware class term: grid, partial sums, vector / scalar split and the box part
-// are those of retina_loss_iou_kernel<VEC>. The box part runs FIRST -- lane t on anchor a_first + t -- and leaves the
-// anchor's quality inter / union; the 16-byte class walk visits the workgroup's anchors with another lane mapping, so the
-// 256 qualities cross through LDS behind one barrier that every lane reaches. The scalar form keeps it in a register.
-template <bool VEC>
-__global__ void __launch_bounds__(256)
-retina_loss_quality_kernel(const uint16_t* __restrict__ cls, const uint16_t* __restrict__ reg, int N, int HW, int A, int C,
-                           int ld_cls, int ld_reg, const int32_t* __restrict__ cls_labels,
-                           const float4* __restrict__ anchors, const int32_t* __restrict__ matched,
-                           const float* __restrict__ gt, int G_max, long long A_total, long long level_offset, int cls_kind,
-                           float alpha, float gamma, int kind, BoxStds sd, float reg_weight, const int* __restrict__ num_fg,
-                           float loss_scale, uint16_t* __restrict__ gcls, uint16_t* __restrict__ greg,
-                           float* __restrict__ partial) {
-  __shared__ float red[8];
-  __shared__ float qs[256];
-  const long long total = (long long)N * HW * A;
-  const long long a_first = (long long)blockIdx.x * 256;
-  const long long idx = a_first + threadIdx.x;
-  const int nf = *num_fg;
-  const float inv = 1.0f / (float)(nf > 1 ? nf : 1);
-  float lc = 0.0f, lr = 0.0f, qa = 0.0f;
-  int lab = -1;
-  long long coff = 0;                                     // this lane's anchor: first class logit
-  if (idx < total) {
-    const int a = (int)(idx % A);
-    const long long cell = idx / A;
-    const int n = (int)(cell / HW);
-    const long long local = cell - (long long)n * HW;
-    const long long ai = level_offset + local * A + a;
-    const long long gi = (long long)n * A_total + ai;
-    lab = cls_labels[gi];
-    coff = cell * ld_cls + (long long)a * C;
-    const uint16_t* d = reg + cell * ld_reg + a * 4;
-    uint16_t* gd = greg + cell * ld_reg + a * 4;
-    unsigned short gb[4] = {0, 0, 0, 0};
-    const int m = lab > 0 ? matched[gi] : -1;
-    if (m >= 0 && m < G_max) {                            // a match outside gt_boxes: regresses nothing, quality 0
-      float dd[4], g4[4];
-      if (VEC) {
-        unpack4_bf16(*(const uint2*)d, dd);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dd[k] = bf16_bits_to_f32(d[k]);
-      }
-      const float4 g = load_f4_a4(gt + ((long long)n * G_max + m) * 5);
-      lr = reg_weight * box_iou_loss_elem(anchors[ai], g, dd, sd, kind, g4, &qa);
-      const float gs = reg_weight * inv * loss_scale;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) gb[k] = f32_to_bf16_bits(g4[k] * gs);
-    }
-    if (VEC) {
-      *(uint2*)gd = make_uint2((unsigned)gb[0] | ((unsigned)gb[1] << 16), (unsigned)gb[2] | ((unsigned)gb[3] << 16));
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) gd[k] = gb[k];
-    }
-  }
-  if (VEC) {
-    qs[threadIdx.x] = qa;
-    __syncthreads();
-    lc = retina_quality_vec(cls, HW, A, C, ld_cls, cls_labels, A_total, level_offset, cls_kind, alpha, gamma, inv, loss_scale,
-                            a_first, total, qs, gcls);
-  } else if (idx < total) {
-    lc = retina_quality_anchor(cls + coff, C, lab, qa, cls_kind, alpha, gamma, inv, loss_scale, gcls + coff);
-  }
-  float s0 = block_sum_fixed(lc, red);
-  float s1 = block_sum_fixed(lr, red);
-  if (threadIdx.x == 0) {
-    partial[2 * blockIdx.x + 0] = s0 * inv;
-    partial[2 * blockIdx.x + 1] = s1 * inv;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Distribution box regression (definition in include/mxdet.h): four lanes per box, lane `side` (l, t, r, b)
-// on the R + 1 logits at x[off ..]. All four lanes of a quad call this together: the expectations cross by lane reads
-// inside the quad, then every lane evaluates the (cheap) IoU core on the whole box and keeps its own side's dL / dE.
-// Writes the side's R + 1 gradients: (reg_weight * dL/dE * p_k (k - E) + dfl_weight / 4 * (p_k - target_k)) * gscale.
-// Returns L (unweighted, equal on the four lanes); dfl = this side's DFL, q = inter / union.
-__device__ __forceinline__ float dist_box_quad(const void* x, long long off, int dtype, int R, int side, const float4 b,
-                                               const float4 g, float s, int kind, float reg_weight, float dfl_weight,
-                                               float gscale, void* gx, float& dfl, float& q) {
-  float xv[kDistBins], m, Z;                              // the logits, then e_k = exp(x_k - m)
-  dist_load(x, off, 1, dtype, R, xv);
-  const float E = dist_expect(xv, R, m, Z);
-  const int q0 = lane_id() & ~3;
-  const float El = __shfl(E, q0 + 0), Et = __shfl(E, q0 + 1), Er = __shfl(E, q0 + 2), Eb = __shfl(E, q0 + 3);
-  const float cx = 0.5f * (b.x + b.z), cy = 0.5f * (b.y + b.w);
-  const float g1[2] = {g.x - cx, g.y - cy}, g2[2] = {g.z - cx, g.w - cy};
-  const float p1[2] = {-(s * El), -(s * Et)}, p2[2] = {s * Er, s * Eb};
-  float pl[2], pc[2], d1[2], d2[2], gp[2], da[2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    pl[k] = p2[k] - p1[k] + 1.0f;
-    pc[k] = 0.5f * (p1[k] + p2[k]);
-  }
-  const float L = box_iou_core(p1, p2, pc, pl, g1, g2, kind, d1, d2, gp, da, &q);
-  const int ax = side & 1;
-  // pc = (p1 + p2) / 2 and pl = p2 - p1 + 1: dL / d p1 = d1 + gp / 2 - da, dL / d p2 = d2 + gp / 2 + da
-  const float dp = side < 2 ? d1[ax] + 0.5f * gp[ax] - da[ax] : d2[ax] + 0.5f * gp[ax] + da[ax];
-  const float dE = side < 2 ? -(s * dp) : s * dp;
-  const float dist = side < 2 ? -g1[ax] : g2[ax];
-  const float ymax = (float)R - 0.1f;
-  float y = dist / s;
-  y = y < 0.0f ? 0.0f : y;
-  y = y > ymax ? ymax : y;
-  const int yl = (int)y;                                  // y >= 0: truncation is floor
-  const float wl = (float)yl + 1.0f - y, wr = y - (float)yl;
-  const float lse = m + mxdet_logf(Z);
-  dfl = wl * (lse - load_as_f32(x, off + yl, dtype)) + wr * (lse - load_as_f32(x, off + yl + 1, dtype));
-  const float gb = reg_weight * dE, gd = dfl_weight * 0.25f;
-#pragma unroll
-  for (int k = 0; k < kDistBins; ++k)
-    if (k <= R) {
-      const float p = xv[k] / Z;
-      const float t = (k == yl ? wl : 0.0f) + (k == yl + 1 ? wr : 0.0f);
-      store_from_f32(gx, off + k, dtype, (gb * (p * ((float)k - E)) + gd * (p - t)) * gscale);
-    }
-  return L;
-}
-
-// the unfused primitive: four lanes per row
-__global__ void __launch_bounds__(256)
-box_dist_loss_kernel(const float4* __restrict__ boxes, const float4* __restrict__ gt, const void* __restrict__ logits,
-                     int dtype, int ld, long long n, int R, float stride, int kind, float reg_weight, float dfl_weight,
-                     float grad_scale, float* __restrict__ loss_box, float* __restrict__ loss_dfl,
-                     float* __restrict__ quality, void* __restrict__ grad) {
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long i = t >> 2;
-  const int side = (int)(t & 3);
-  if (i >= n) return;                                     // whole quads leave together
-  float dfl, q;
-  const float L = dist_box_quad(logits, i * ld + side * (R + 1), dtype, R, side, boxes[i], gt[i], stride, kind, reg_weight,
-                                dfl_weight, grad_scale, grad, dfl, q);
-  const int q0 = lane_id() & ~3;
-  const float dsum = ((__shfl(dfl, q0 + 0) + __shfl(dfl, q0 + 1)) + __shfl(dfl, q0 + 2)) + __shfl(dfl, q0 + 3);
-  if (side == 0) {
-    loss_box[i] = reg_weight * L;
-    loss_dfl[i] = dfl_weight * 0.25f * dsum;
-    if (quality) quality[i] = q;
-  }
-}
-
-// The level loss of the distribution head: the grid of the other level kernels (256 anchors per workgroup),
-// three partial sums per workgroup (class, box, DFL). Phases, each behind a barrier that every lane reaches:
-//   1  lane t on anchor a_first + t: label and match -> ms[t] (>= 0: the anchor regresses against that row of gt_boxes)
-//   2  zeros into the 4 (R + 1) gradient channels of every anchor that does not regress: 8-byte stores on consecutive
-//      addresses (VEC) or 2-byte ones; an anchor's channels start a multiple of 8 bytes into its 8-byte aligned row
-//   3  four lanes per regressing anchor, 64 anchors per pass over the workgroup's COMPACTED list of them (dist_box_quad);
-//      side 0 keeps the sums and leaves the quality in qs[]. A workgroup holds a handful of positives: one pass, where
-//      a fixed anchor-to-quad map needs four, each as long as its slowest quad.
-//   4  the class walk of retina_loss_iou_kernel (FOCAL) or retina_loss_quality_kernel: same code, same bits.
-template <bool VEC, bool FOCAL>
-__global__ void __launch_bounds__(256)
-retina_loss_dfl_kernel(const uint16_t* __restrict__ cls, const uint16_t* __restrict__ reg, int N, int HW, int A, int C,
-                       int ld_cls, int ld_reg, const int32_t* __restrict__ cls_labels, const float4* __restrict__ anchors,
-                       const int32_t* __restrict__ matched, const float* __restrict__ gt, int G_max, long long A_total,
-                       long long level_offset, int cls_kind, float alpha, float gamma, int kind, int R, float stride,
-                       float reg_weight, float dfl_weight, const int* __restrict__ num_fg, float loss_scale,
-                       uint16_t* __restrict__ gcls, uint16_t* __restrict__ greg, float* __restrict__ partial) {
-  __shared__ float red[8];
-  __shared__ float qs[256];
-  __shared__ int ms[256];
-  __shared__ long long roff[256];                         // first gradient channel of the workgroup's anchors
-  __shared__ int plist[256], cnt[5];                      // the regressing anchors, in anchor order
-  const long long total = (long long)N * HW * A;
-  const long long a_first = (long long)blockIdx.x * 256;
-  const long long idx = a_first + threadIdx.x;
-  const int nf = *num_fg;
-  const float inv = 1.0f / (float)(nf > 1 ? nf : 1);
-  const int nb = R + 1;
-  float lc = 0.0f, lr = 0.0f, ldf = 0.0f;
-  int lab = -1, mt = -2;                                  // mt -2: no such anchor
-  long long coff = 0, goff = 0;
-  if (idx < total) {
-    const int a = (int)(idx % A);
-    const long long cell = idx / A;
-    const int n = (int)(cell / HW);
-    const long long local = cell - (long long)n * HW;
-    const long long gi = (long long)n * A_total + level_offset + local * A + a;
-    lab = cls_labels[gi];
-    coff = cell * ld_cls + (long long)a * C;
-    goff = cell * ld_reg + (long long)a * (4 * nb);
-    const int m = lab > 0 ? matched[gi] : -1;
-    mt = (m >= 0 && m < G_max) ? m : -1;                  // a match outside gt_boxes: regresses nothing, quality 0
-  }
-  ms[threadIdx.x] = mt;
-  roff[threadIdx.x] = goff;
-  qs[threadIdx.x] = 0.0f;
-  int npos;
-  const int rank = block_excl_count(mt >= 0, cnt, &npos);
-  if (mt >= 0) plist[rank] = threadIdx.x;
-  __syncthreads();
-  const int per = VEC ? nb : 4 * nb;                      // stores per anchor (<= 128: it < 2^15, fast_divmod is exact)
-  const float rper = 1.0f / (float)per;
-  for (int it = threadIdx.x; it < 256 * per; it += 256) {
-    int ck;
-    const int al = fast_divmod(it, per, rper, &ck);
-    if (ms[al] != -1) continue;
-    const long long off = roff[al];
-    if (VEC)
-      *(uint2*)(greg + off + 4 * ck) = make_uint2(0u, 0u);
-    else
-      greg[off + ck] = 0;
-  }
-  for (int j = threadIdx.x >> 2; j < npos; j += 64) {     // the four lanes of a quad share j
-    const int al = plist[j], side = threadIdx.x & 3;
-    const int m = ms[al];
-    const long long ix = a_first + al;
-    const int a = (int)(ix % A);
-    const long long cell = ix / A;
-    const int n = (int)(cell / HW);
-    const long long ai = level_offset + (cell - (long long)n * HW) * A + a;
-    const float4 g = load_f4_a4(gt + ((long long)n * G_max + m) * 5);
-    float dfl, q;
-    const float L = dist_box_quad(reg, roff[al] + side * nb, MXDET_DTYPE_BF16, R, side,
-                                  anchors[ai], g, stride, kind, reg_weight, dfl_weight, inv * loss_scale, greg, dfl, q);
-    const int q0 = lane_id() & ~3;
-    const float dsum = ((__shfl(dfl, q0 + 0) + __shfl(dfl, q0 + 1)) + __shfl(dfl, q0 + 2)) + __shfl(dfl, q0 + 3);
-    if (side == 0) {
-      lr += reg_weight * L;
-      ldf += dfl_weight * 0.25f * dsum;
-      qs[al] = q;
-    }
-  }
-  __syncthreads();
-  if (VEC) {
-    if (FOCAL)
-      lc = retina_focal_vec(cls, HW, A, C, ld_cls, cls_labels, A_total, level_offset, alpha, gamma, inv, loss_scale, a_first,
-                            total, gcls);
-    else
-      lc = retina_quality_vec(cls, HW, A, C, ld_cls, cls_labels, A_total, level_offset, cls_kind, alpha, gamma, inv,
-                              loss_scale, a_first, total, qs, gcls);
-  } else if (idx < total) {
-    if (FOCAL)
-      lc = retina_focal_anchor(cls + coff, C, lab, alpha, gamma, inv, loss_scale, gcls + coff);
-    else
-      lc = retina_quality_anchor(cls + coff, C, lab, qs[threadIdx.x], cls_kind, alpha, gamma, inv, loss_scale, gcls + coff);
-  }
-  float s0 = block_sum_fixed(lc, red);
-  float s1 = block_sum_fixed(lr, red);
-  float s2 = block_sum_fixed(ldf, red);
-  if (threadIdx.x == 0) {
-    partial[3 * blockIdx.x + 0] = s0 * inv;
-    partial[3 * blockIdx.x + 1] = s1 * inv;
-    partial[3 * blockIdx.x + 2] = s2 * inv;
-  }
-}
-
-}  // namespace mxdet
-
-extern "C" int mxdet_anchor_class_labels(const int32_t* labels, const int32_t* matched_gt, const float* gt_boxes,
-                                         int32_t N, int64_t A_total, int32_t G_max, int32_t* cls_labels,
-                                         int32_t* num_fg, mxdet_stream_t stream) {
-  clear_error();
-  MXDET_REQUIRE(N > 0 && A_total > 0 && G_max > 0, MXDET_ESHAPE, "anchor_class_labels: bad shape");
-  MXDET_REQUIRE(labels && matched_gt && gt_boxes && cls_labels && num_fg, MXDET_EINVAL, "anchor_class_labels: null pointer");
-  hipStream_t s = as_stream(stream);
-  hipError_t e = zero_async(num_fg, sizeof(int32_t), s);
-  MXDET_REQUIRE(e == hipSuccess, MXDET_EHIP, "anchor_class_labels: memset failed");
-  long long total = (long long)N * A_total;
-  hipLaunchKernelGGL(anchor_class_labels_kernel, dim3((unsigned)ceil_div<long long>(total, 256)), dim3(256), 0, s, labels,
-                     matched_gt, gt_boxes, (long long)A_total, G_max, total, cls_labels, num_fg);
-  return check_launch("anchor_class_labels");
-}
-
-extern "C" int32_t mxdet_retina_loss_num_partials(int32_t N, int32_t H, int32_t W, int32_t A) {
-  return (int32_t)(((long long)N * H * W * A + 255) / 256);
-}
-
-extern "C" int mxdet_retina_loss_level(const uint16_t* cls, const uint16_t* reg, int32_t N, int32_t H, int32_t W,
-                                       int32_t A, int32_t C, int32_t ld_cls, int32_t ld_reg,
-                                       const int32_t* cls_labels, const float* bbox_targets, int64_t A_total,
-                                       int64_t level_offset, float alpha, float gamma, float sigma,
-                                       const int32_t* num_fg, float loss_scale, uint16_t* grad_cls,
-                                       uint16_t* grad_reg, float* partial, mxdet_stream_t stream) {
-  clear_error();
-  MXDET_REQUIRE(N > 0 && H > 0 && W > 0 && A > 0 && C > 0 && ld_cls >= A * C && ld_reg >= 4 * A, MXDET_ESHAPE,
-                "retina_loss_level: bad shape");
-  MXDET_REQUIRE(cls && reg && cls_labels && bbox_targets && num_fg && grad_cls && grad_reg && partial, MXDET_EINVAL,
-                "retina_loss_level: null pointer");
-  MXDET_REQUIRE(level_offset >= 0 && level_offset + (int64_t)H * W * A <= A_total, MXDET_ESHAPE,
-                "retina_loss_level: level outside the anchor range");
-  int blocks = mxdet_retina_loss_num_partials(N, H, W, A);
-  // 16-byte path: whole 8-channel chunks per anchor and 16-B / 8-B aligned rows
-  const bool vec = (C % 8 == 0) && (ld_cls % 8 == 0) && (ld_reg % 4 == 0) && (((uintptr_t)cls | (uintptr_t)grad_cls) % 16 == 0) &&
-                   (((uintptr_t)reg | (uintptr_t)grad_reg) % 8 == 0);
-  if (route_probe_on()) {   // mxdet_debug_route_probe: say which form would run, touch nothing
-    const int32_t rec[kRouteWords] = {MXDET_ROUTE_RETINA_LOSS, vec ? 1 : 0, blocks};
-    route_record(rec);
-    return MXDET_OK;
-  }
-  if (vec)
-    hipLaunchKernelGGL(retina_loss_vec_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), cls, reg, N, H * W, A, C,
-                       ld_cls, ld_reg, cls_labels, (const float4*)bbox_targets, (long long)A_total, (long long)level_offset,
-                       alpha, gamma, sigma * sigma, (const int*)num_fg, loss_scale, grad_cls, grad_reg, partial);
-  else
-    hipLaunchKernelGGL(retina_loss_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), cls, reg, N, H * W, A, C, ld_cls,
-                       ld_reg, cls_labels, (const float4*)bbox_targets, (long long)A_total, (long long)level_offset, alpha,
-                       gamma, sigma * sigma, (const int*)num_fg, loss_scale, grad_cls, grad_reg, partial);
-  return check_launch("retina_loss_level");
-}
-
-// What an anchor-based level entry (_iou, _quality, _dfl) needs to launch: the grid, the form, and whether the route probe
-// took the call (then nothing runs).
-struct LevelLaunch {
-  int blocks;
-  bool vec, probed;
-};
-
-// The checks common to the three anchor-based level entries, in the order each has had them: shape, the entry's own
-// parameter checks (param_error: the message of the first that fails, evaluated by the entry, or null), null pointers, the
-// anchor table's alignment, the level's range. Fills *out and records the route if the probe is on.
-static int retina_level_prepare(const char* entry, const uint16_t* cls, const uint16_t* reg, int32_t N, int32_t H, int32_t W,
-                                int32_t A, int32_t C, int32_t ld_cls, int32_t ld_reg, const int32_t* cls_labels,
-                                const float* anchors, const int32_t* matched_gt, const float* gt_boxes, int32_t G_max,
-                                int64_t A_total, int64_t level_offset, const int32_t* num_fg, const uint16_t* grad_cls,
-                                const uint16_t* grad_reg, const float* partial, const char* param_error,
-                                int box_channels_per_anchor, int route_id, LevelLaunch* out) {
-  MXDET_REQUIRE(N > 0 && H > 0 && W > 0 && A > 0 && C > 0 && ld_cls >= A * C && ld_reg >= box_channels_per_anchor * A &&
-                    G_max > 0,
-                MXDET_ESHAPE, "%s: bad shape", entry);
-  MXDET_REQUIRE(!param_error, MXDET_EINVAL, "%s: %s", entry, param_error);
-  MXDET_REQUIRE(cls && reg && cls_labels && anchors && matched_gt && gt_boxes && num_fg && grad_cls && grad_reg && partial,
-                MXDET_EINVAL, "%s: null pointer", entry);
-  MXDET_REQUIRE((uintptr_t)anchors % 16 == 0, MXDET_EINVAL, "%s: anchors must be 16-byte aligned", entry);
-  MXDET_REQUIRE(level_offset >= 0 && level_offset + (int64_t)H * W * A <= A_total, MXDET_ESHAPE,
-                "%s: level outside the anchor range", entry);
-  out->blocks = mxdet_retina_loss_num_partials(N, H, W, A);
-  // the vec condition of mxdet_retina_loss_level
-  out->vec = (C % 8 == 0) && (ld_cls % 8 == 0) && (ld_reg % 4 == 0) && (((uintptr_t)cls | (uintptr_t)grad_cls) % 16 == 0) &&
-             (((uintptr_t)reg | (uintptr_t)grad_reg) % 8 == 0);
-  out->probed = route_probe_on();
-  if (out->probed) {
-    const int32_t rec[kRouteWords] = {route_id, out->vec ? 1 : 0, out->blocks};
-    route_record(rec);
-  }
-  return MXDET_OK;
-}
-
-// the entries' own parameter checks: the message of the first one that fails, or null
-static bool cls_kind_dfl_ok(int32_t k) { return k == MXDET_CLS_LOSS_FOCAL || cls_kind_ok(k); }
-static const char* iou_kind_error(int32_t kind) {
-  return iou_kind_ok(kind) ? nullptr : "kind must be MXDET_IOU_LOSS_IOU, _GIOU or _DIOU";
-}
-static const char* quality_cls_error(int32_t cls_kind, bool focal_too, float gamma) {
-  if (!(focal_too ? cls_kind_dfl_ok(cls_kind) : cls_kind_ok(cls_kind)))
-    return focal_too ? "cls_kind must be MXDET_CLS_LOSS_FOCAL, _QFL or _VFL" : "cls_kind must be MXDET_CLS_LOSS_QFL or _VFL";
-  return gamma > 0.0f ? nullptr : "gamma must be positive";
-}
-static const char* delta_box_error(int32_t kind, float std_x, float std_y, float std_w, float std_h, float reg_weight) {
-  if (const char* e = iou_kind_error(kind)) return e;
-  return stds_ok(std_x, std_y, std_w, std_h) && reg_weight > 0.0f ? nullptr : "stds and reg_weight must be positive";
-}
-
-extern "C" int mxdet_retina_loss_level_iou(const uint16_t* cls, const uint16_t* reg, int32_t N, int32_t H, int32_t W,
-                                           int32_t A, int32_t C, int32_t ld_cls, int32_t ld_reg,
-                                           const int32_t* cls_labels, const float* anchors, const int32_t* matched_gt,
-                                           const float* gt_boxes, int32_t G_max, int64_t A_total, int64_t level_offset,
-                                           float alpha, float gamma, int32_t kind, float std_x, float std_y, float std_w,
-                                           float std_h, float reg_weight, const int32_t* num_fg, float loss_scale,
-                                           uint16_t* grad_cls, uint16_t* grad_reg, float* partial, mxdet_stream_t stream) {
-  clear_error();
-  LevelLaunch L;
-  const int rc = retina_level_prepare("retina_loss_level_iou", cls, reg, N, H, W, A, C, ld_cls, ld_reg, cls_labels, anchors,
-                                      matched_gt, gt_boxes, G_max, A_total, level_offset, num_fg, grad_cls, grad_reg, partial,
-                                      delta_box_error(kind, std_x, std_y, std_w, std_h, reg_weight), 4,
-                                      MXDET_ROUTE_RETINA_LOSS_IOU, &L);
-  if (rc != MXDET_OK || L.probed) return rc;
-  const BoxStds sd = {std_x, std_y, std_w, std_h};
-  hipLaunchKernelGGL(L.vec ? retina_loss_iou_kernel<true> : retina_loss_iou_kernel<false>, dim3(L.blocks), dim3(256), 0,
-                     as_stream(stream), cls, reg, N, H * W, A, C, ld_cls, ld_reg, cls_labels, (const float4*)anchors, matched_gt,
-                     gt_boxes, G_max, (long long)A_total, (long long)level_offset, alpha, gamma, kind, sd, reg_weight,
-                     (const int*)num_fg, loss_scale, grad_cls, grad_reg, partial);
-  return check_launch("retina_loss_level_iou");
-}
-
-extern "C" int mxdet_retina_loss_level_quality(const uint16_t* cls, const uint16_t* reg, int32_t N, int32_t H, int32_t W,
-                                               int32_t A, int32_t C, int32_t ld_cls, int32_t ld_reg,
-                                               const int32_t* cls_labels, const float* anchors, const int32_t* matched_gt,
-                                               const float* gt_boxes, int32_t G_max, int64_t A_total, int64_t level_offset,
-                                               int32_t cls_kind, float alpha, float gamma, int32_t kind, float std_x,
-                                               float std_y, float std_w, float std_h, float reg_weight, const int32_t* num_fg,
-                                               float loss_scale, uint16_t* grad_cls, uint16_t* grad_reg, float* partial,
-                                               mxdet_stream_t stream) {
-  clear_error();
-  const char* bad = quality_cls_error(cls_kind, false, gamma);
-  if (!bad) bad = delta_box_error(kind, std_x, std_y, std_w, std_h, reg_weight);
-  LevelLaunch L;
-  const int rc = retina_level_prepare("retina_loss_level_quality", cls, reg, N, H, W, A, C, ld_cls, ld_reg, cls_labels, anchors,
-                                      matched_gt, gt_boxes, G_max, A_total, level_offset, num_fg, grad_cls, grad_reg, partial, bad,
-                                      4, MXDET_ROUTE_RETINA_LOSS_QUALITY, &L);
-  if (rc != MXDET_OK || L.probed) return rc;
-  const BoxStds sd = {std_x, std_y, std_w, std_h};
-  hipLaunchKernelGGL(L.vec ? retina_loss_quality_kernel<true> : retina_loss_quality_kernel<false>, dim3(L.blocks), dim3(256), 0,
-                     as_stream(stream), cls, reg, N, H * W, A, C, ld_cls, ld_reg, cls_labels, (const float4*)anchors, matched_gt,
-                     gt_boxes, G_max, (long long)A_total, (long long)level_offset, cls_kind, alpha, gamma, kind, sd, reg_weight,
-                     (const int*)num_fg, loss_scale, grad_cls, grad_reg, partial);
-  return check_launch("retina_loss_level_quality");
-}
-
 extern "C" int mxdet_box_dist_loss(const float* boxes, const float* gt, const void* logits, int32_t dtype, int32_t ld,
                                    int64_t n, int32_t reg_max, float stride, int32_t kind, float reg_weight,
                                    float dfl_weight, float grad_scale, float* loss_box, float* loss_dfl, float* quality,
@@ -1439,32 +488,4 @@ extern "C" int mxdet_box_dist_loss(const float* boxes, const float* gt, const vo
                      (const float4*)boxes, (const float4*)gt, logits, dtype, ld, (long long)n, reg_max, stride, kind,
                      reg_weight, dfl_weight, grad_scale, loss_box, loss_dfl, quality, grad_logits);
   return check_launch("box_dist_loss");
-}
-
-extern "C" int mxdet_retina_loss_level_dfl(const uint16_t* cls, const uint16_t* reg, int32_t N, int32_t H, int32_t W, int32_t A,
-                                           int32_t C, int32_t ld_cls, int32_t ld_reg, const int32_t* cls_labels,
-                                           const float* anchors, const int32_t* matched_gt, const float* gt_boxes,
-                                           int32_t G_max, int64_t A_total, int64_t level_offset, int32_t cls_kind, float alpha,
-                                           float gamma, int32_t kind, int32_t reg_max, float stride, float reg_weight,
-                                           float dfl_weight, const int32_t* num_fg, float loss_scale, uint16_t* grad_cls,
-                                           uint16_t* grad_reg, float* partial, mxdet_stream_t stream) {
-  clear_error();
-  MXDET_REQUIRE(reg_max >= 1 && reg_max <= MXDET_REG_MAX_LIMIT, MXDET_EINVAL, "retina_loss_level_dfl: reg_max %d not in 1..%d",
-                reg_max, MXDET_REG_MAX_LIMIT);
-  const char* bad = quality_cls_error(cls_kind, true, gamma);
-  if (!bad) bad = iou_kind_error(kind);
-  if (!bad && !(stride > 0.0f && reg_weight > 0.0f && dfl_weight > 0.0f)) bad = "stride, reg_weight and dfl_weight must be positive";
-  LevelLaunch L;
-  const int rc = retina_level_prepare("retina_loss_level_dfl", cls, reg, N, H, W, A, C, ld_cls, ld_reg, cls_labels, anchors,
-                                      matched_gt, gt_boxes, G_max, A_total, level_offset, num_fg, grad_cls, grad_reg, partial, bad,
-                                      4 * (reg_max + 1), MXDET_ROUTE_RETINA_LOSS_DFL, &L);
-  if (rc != MXDET_OK || L.probed) return rc;
-  const bool focal = cls_kind == MXDET_CLS_LOSS_FOCAL;
-  const auto k = L.vec ? (focal ? retina_loss_dfl_kernel<true, true> : retina_loss_dfl_kernel<true, false>)
-                       : (focal ? retina_loss_dfl_kernel<false, true> : retina_loss_dfl_kernel<false, false>);
-  hipLaunchKernelGGL(k, dim3(L.blocks), dim3(256), 0, as_stream(stream), cls, reg, N, H * W, A, C, ld_cls, ld_reg, cls_labels,
-                     (const float4*)anchors, matched_gt, gt_boxes, G_max, (long long)A_total, (long long)level_offset, cls_kind,
-                     alpha, gamma, kind, reg_max, stride, reg_weight, dfl_weight, (const int*)num_fg, loss_scale, grad_cls,
-                     grad_reg, partial);
-  return check_launch("retina_loss_level_dfl");
 }

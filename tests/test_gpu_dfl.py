@@ -1,4 +1,4 @@
-"""The distribution box head's entries (mxdet_box_dist_loss, mxdet_retina_loss_level_dfl in csrc/losses.hip,
+"""The distribution box head's entries (mxdet_box_dist_loss, mxdet_retina_loss_level_dfl in csrc/losses.hip / retina_loss.hip,
 mxdet_retina_detect_dfl in csrc/postprocess.hip) on the case tables of tests/test_dfl_cases_cpu.py.
 
 Losses: per row / per element against the float64 autograd reference within the bounds measured in the CPU module (plus one

@@ -1,4 +1,4 @@
-"""The IoU / GIoU / DIoU box-loss entries (csrc/losses.hip) on the case tables of tests/test_iou_loss_cases_cpu.py.
+"""The IoU / GIoU / DIoU box-loss entries (csrc/losses.hip, retina_loss.hip) on the case tables of tests/test_iou_loss_cases_cpu.py.
 
 For every case: gradients against the float64 autograd reference after division by `unit` (ATOL_GRAD of the stds setting, as
 measured in the CPU module, plus one bf16 step 2^-8 * |ref| for bf16 outputs), per-box losses within ATOL_LOSS, summed

@@ -1,4 +1,4 @@
-"""The fused loss kernels (csrc/losses.hip, mask_loss_kernel) on the case tables of tests/test_loss_cases_cpu.py.
+"""The fused loss kernels (csrc/losses.hip, retina_loss.hip, mask_loss_kernel) on the case tables of tests/test_loss_cases_cpu.py.
 
 For every case: gradients against the float64 autograd reference (after division by norm * loss_scale; ATOL_CE / ATOL_FOCAL
 as derived in the CPU module, plus one bf16 step 2^-8 * |ref| for bf16 outputs), loss scalars within 3e-5 of the float64

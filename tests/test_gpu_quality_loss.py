@@ -1,4 +1,4 @@
-"""The quality-aware class-loss entries (mxdet_quality_focal_loss, mxdet_retina_loss_level_quality in csrc/losses.hip) on the
+"""The quality-aware class-loss entries (mxdet_quality_focal_loss, mxdet_retina_loss_level_quality in csrc/losses.hip / retina_loss.hip) on the
 case tables of tests/test_quality_loss_cases_cpu.py.
 
 For every case: class gradients against the float64 autograd reference after division by inv * loss_scale (ATOL_CLS_GRAD as

@@ -1,5 +1,5 @@
 """Case tables, float64 references and CPU proofs of the IoU / GIoU / DIoU box losses (mxdet_box_iou_loss, mxdet_rcnn_loss_iou,
-mxdet_retina_loss_level_iou in csrc/losses.hip). tests/test_gpu_iou_loss.py runs the same tables on the GPU.
+mxdet_retina_loss_level_iou in csrc/losses.hip / retina_loss.hip). tests/test_gpu_iou_loss.py runs the same tables on the GPU.
 
 References: float64 torch autograd on the definition of DESIGN.md 5f written in ABSOLUTE image coordinates with torch.exp,
 torch.maximum and torch.minimum (whose gradient at an exact tie is 1/2 to each side: test_torch_maximum_splits_a_tie);

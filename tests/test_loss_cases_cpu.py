@@ -1,4 +1,4 @@
-"""Case tables and float64 references of the fused loss kernel tests (csrc/losses.hip, mask_loss_kernel in csrc/mask.hip),
+"""Case tables and float64 references of the fused loss kernel tests (csrc/losses.hip, csrc/retina_loss.hip, mask_loss_kernel in csrc/mask.hip),
 and the proof -- without a GPU -- that every case is what it is named after. tests/test_gpu_losses.py runs the same tables
 on the GPU.
 
@@ -19,7 +19,7 @@ Tolerances of the gradient comparison (on gradients divided by `unit`; bf16 outp
                       float64 reference by at most 2.94e-6 over every bf16-exact logit k/2 in [-90, 90], gamma in {0, 0.5,
                       1.5, 2, 5}, both targets (the general branch computes x^gamma as exp(gamma*log(x)), which multiplies
                       log's rounding error by gamma*|log x|); times 4, rounded up to a power of two. With the
-                      cancellation-free sigmoid_softplus of csrc/losses.hip, which focal_fp32 below restates,
+                      cancellation-free sigmoid_softplus of csrc/loss_elem.h, which focal_fp32 below restates,
                       test_focal_fp32_error_budget measures 5.6e-7 (grid plus 1500 float32 logits ~ 3*N(0,1)) and bounds it
                       by ATOL_FOCAL / 4; the bound itself is kept at the value derived for the formula as it was.
 Loss scalars: rtol 3e-5 against the float64 sum (the bound of the project's fixed-order fp32 reductions), exactly 0 where
@@ -43,7 +43,7 @@ BF16_STEP = 2.0 ** -8
 LOSS_RTOL = 3e-5
 F32_MIN_NORMAL = 2.0 ** -126
 GAMMAS = (0.0, 0.5, 1.5, 2.0, 5.0)
-FOCAL_MAX_ELEMS_ONE_PASS = 2048 * 256       # focal_kernel's grid cap times its block size
+FOCAL_MAX_ELEMS_ONE_PASS = 2048 * 256       # cls_loss_kernel's grid cap times its block size
 
 
 def O():
@@ -472,10 +472,10 @@ def ids(cases):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# float32 restatement of focal_kernel's formula (CPU; only used to size ATOL_FOCAL, never as a reference)
+# float32 restatement of focal_cls_elem's formula (CPU; only used to size ATOL_FOCAL, never as a reference)
 # ---------------------------------------------------------------------------------------------------------------------
 def focal_fp32(z, positive, alpha, gamma):
-    """(loss term, d(focal)/dz) per element as focal_kernel evaluates them: float32 throughout, oracle.expf / oracle.logf."""
+    """(loss term, d(focal)/dz) per element as focal_cls_elem evaluates them: float32 throughout, oracle.expf / oracle.logf."""
     o, f = O(), np.float32
     z = np.asarray(z, f)
     t = o.expf(-np.abs(z))
@@ -777,7 +777,7 @@ def test_references_agree_with_the_c_oracle_focal_and_retina():
 
 
 def test_focal_fp32_error_budget():
-    """ATOL_FOCAL: float32 evaluation of focal_kernel's formula (oracle.expf / oracle.logf) against float64 autograd over
+    """ATOL_FOCAL: float32 evaluation of focal_cls_elem's formula (oracle.expf / oracle.logf) against float64 autograd over
     every bf16-exact logit k/2 in [-90, 90], both targets, every gamma of the table."""
     import torch
     z = np.concatenate([np.arange(-180, 181) * 0.5, (np.random.default_rng(5).standard_normal(1500) * 3).astype(np.float32)])

@@ -1,5 +1,5 @@
 """Case tables and CPU proofs of the quality-aware class losses (mxdet_quality_focal_loss, mxdet_retina_loss_level_quality in
-csrc/losses.hip). tests/test_gpu_quality_loss.py runs the same tables on the GPU; the references are in
+csrc/losses.hip / retina_loss.hip). tests/test_gpu_quality_loss.py runs the same tables on the GPU; the references are in
 tests/_quality_loss_ref.py.
 
 Level tables: the four RETINA_SHAPES of tests/test_iou_loss_cases_cpu.py on THEIR data (boxes, deltas, labels, logits) plus
