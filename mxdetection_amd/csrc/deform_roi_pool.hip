@@ -15,15 +15,15 @@
 // Why not RoIAlign's segment gather: its per-roi separable grid is gone (every bin is shifted on its own) and 49 x S row
 // samples exceed its 32-lane sample tables; why not deform_conv.hip's inverted index: under unbounded overlap (1024
 // identical proposals) one pixel's list is thousands of entries long, beyond its 64-entry wave sort.
-#include "common.h"
+// The pyramid argument, the roi header clamp, packed spans and the gather's skeleton (level of a workgroup, ascending LDS
+// roi list, row write-out) are roi_gather.h's, shared with roi_align.hip.
+#include "roi_gather.h"
 
 namespace mxdet {
 
 struct DPoolArgs {
-  int num_levels, lvl_min, N, C, PH, PW, NB, S, mod, ts, ms, acc;
-  int H[8], W[8];
-  float scale[8];
-  void* feat[8];
+  FeatPyr p;
+  int C, PH, PW, NB, S, mod, ts, ms, acc;
   float trans_std;
 };
 
@@ -36,12 +36,9 @@ __device__ __forceinline__ DRoi dpool_roi(const DPoolArgs& a, const float* __res
                                           const int32_t* __restrict__ levels, long long r) {
   DRoi g;
   const float* q = rois + r * 5;
-  int l = levels[r] - a.lvl_min;
-  l = l < 0 ? 0 : (l >= a.num_levels ? a.num_levels - 1 : l);
-  int n = (int)q[0];
-  n = n < 0 ? 0 : (n >= a.N ? a.N - 1 : n);          // never index outside the batch
-  const float s = a.scale[l];
-  g.n = n; g.lvl = l; g.H = a.H[l]; g.W = a.W[l];
+  roi_image_level(a.p, rois, levels, r, &g.lvl, &g.n);
+  const float s = a.p.scale[g.lvl];
+  g.H = a.p.H[g.lvl]; g.W = a.p.W[g.lvl];
   g.rsw = roundf(q[1]) * s - 0.5f;                    // C round: half away from zero
   g.rsh = roundf(q[2]) * s - 0.5f;
   const float rew = (roundf(q[3]) + 1.0f) * s - 0.5f;
@@ -98,7 +95,7 @@ dpool_fwd_kernel(DPoolArgs a, const float* __restrict__ rois, const int32_t* __r
   const long long r = blockIdx.x;
   const DRoi g = dpool_roi(a, rois, levels, r);
   const int CG = a.C >> 3;
-  const uint16_t* feat = (const uint16_t*)a.feat[g.lvl] + (long long)g.n * g.H * g.W * a.C;
+  const uint16_t* feat = (const uint16_t*)a.p.feat[g.lvl] + (long long)g.n * g.H * g.W * a.C;
   for (int it = threadIdx.x; it < a.NB * CG; it += blockDim.x) {
     const int cg = it % CG, b = it / CG;
     float ws, hs, m;
@@ -159,7 +156,7 @@ dpool_bwd_trans_kernel(DPoolArgs a, long long R, const float* __restrict__ rois,
   const DRoi g = dpool_roi(a, rois, levels, r);
   float ws, hs, m;
   dpool_bin(a, g, trans, mask, r, b, &ws, &hs, &m);
-  const uint16_t* feat = (const uint16_t*)a.feat[g.lvl] + (long long)g.n * g.H * g.W * a.C;
+  const uint16_t* feat = (const uint16_t*)a.p.feat[g.lvl] + (long long)g.n * g.H * g.W * a.C;
   const uint16_t* drow = dout + (r * a.NB + b) * a.C;
   float gx = 0.0f, gy = 0.0f, gm = 0.0f;
   for (int c0 = lane * 4; c0 < a.C; c0 += 256) {
@@ -229,14 +226,10 @@ dpool_bwd_trans_kernel(DPoolArgs a, long long R, const float* __restrict__ rois,
   }
 }
 
-// ---- feature adjoint: records + gather ----------------------------------------------------------------------------------
-constexpr int kDpSegW = 8;        // pixels per wave
-constexpr int kDpWaves = 4;       // waves (segments) per workgroup
-constexpr int kDpChunk = 1024;    // rois per list round
-
+// ---- feature adjoint: records + gather (kSegW pixels per wave, kSegWaves waves per workgroup: roi_gather.h) -------------
 struct DpRoiRec {                 // 32 B
   int nl;                         // image | level << 16 (level 0xffff: no valid sample)
-  unsigned yy, xx;                // ylo | yhi << 16, xlo | xhi << 16: pixel box of its valid samples' corners
+  unsigned yy, xx;                // span_pack(ylo, yhi), span_pack(xlo, xhi): pixel box of its valid samples' corners
   int pad0;
   float sub_h, sub_w;
   int pad1, pad2;
@@ -250,7 +243,7 @@ struct DpBinRec {                 // 32 B
 
 struct DpGrid {
   int block0[9];                  // first workgroup of level l
-  int chunks[8];                  // workgroups along a row (kDpWaves * kDpSegW pixels each)
+  int chunks[8];                  // workgroups along a row (kSegWaves * kSegW pixels each)
 };
 
 // one WAVE per roi, lane b = bin b; the roi's box is a butterfly min / max over its bins
@@ -278,8 +271,8 @@ dpool_prepare_kernel(DPoolArgs a, long long R, const float* __restrict__ rois, c
     DpBinRec e;
     e.ws = ws; e.hs = hs;
     e.scale = cnt ? m / (float)cnt : 0.0f;
-    e.yy = cnt ? (unsigned)ylo | ((unsigned)yhi << 16) : 0xffffu;            // lo 0xffff > hi 0: empty
-    e.xx = cnt ? (unsigned)xlo | ((unsigned)xhi << 16) : 0xffffu;
+    e.yy = cnt ? span_pack(ylo, yhi) : kSpanEmpty;
+    e.xx = cnt ? span_pack(xlo, xhi) : kSpanEmpty;
     e.pad0 = e.pad1 = e.pad2 = 0;
     bin[r * a.NB + lane] = e;
   }
@@ -294,103 +287,79 @@ dpool_prepare_kernel(DPoolArgs a, long long R, const float* __restrict__ rois, c
     DpRoiRec o;
     const bool any = yhi >= 0;
     o.nl = g.n | ((any ? g.lvl : 0xffff) << 16);
-    o.yy = any ? (unsigned)ylo | ((unsigned)yhi << 16) : 0xffffu;
-    o.xx = any ? (unsigned)xlo | ((unsigned)xhi << 16) : 0xffffu;
+    o.yy = any ? span_pack(ylo, yhi) : kSpanEmpty;
+    o.xx = any ? span_pack(xlo, xhi) : kSpanEmpty;
     o.sub_h = g.sub_h; o.sub_w = g.sub_w;
     o.pad0 = o.pad1 = o.pad2 = 0;
     roi[r] = o;
   }
 }
 
-__device__ __forceinline__ bool dp_span_hits(unsigned packed, int lo, int hi) {   // [plo, phi] meets [lo, hi]
-  return (int)(packed >> 16) >= lo && (int)(packed & 0xffffu) <= hi;
-}
-
-__device__ __forceinline__ float dp_readlane_f(float v, int l) {
-  return __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(v), l));
-}
-
-// acc[j] += w * go for a wave-uniform j in [0, kDpSegW) (registers cannot be indexed at run time)
-__device__ __forceinline__ void dp_add(float (&acc)[kDpSegW][4], int j, float w, const float* go) {
+// acc[j] += w * go for a wave-uniform j in [0, kSegW) (registers cannot be indexed at run time)
+__device__ __forceinline__ void dp_add(float (&acc)[kSegW][4], int j, float w, const float* go) {
 #pragma unroll
-  for (int i = 0; i < kDpSegW; ++i) {
+  for (int i = 0; i < kSegW; ++i) {
     const float wi = i == j ? w : 0.0f;        // adds +0 elsewhere: the sums are unchanged
 #pragma unroll
     for (int k = 0; k < 4; ++k) acc[i][k] = acc[i][k] + wi * go[k];
   }
 }
 
-__global__ void __launch_bounds__(kDpWaves * 64)
+__global__ void __launch_bounds__(kSegWaves * 64)
 dpool_gather_kernel(DPoolArgs a, DpGrid gr, int R, const DpRoiRec* __restrict__ roi, const DpBinRec* __restrict__ bin,
                     const uint16_t* __restrict__ dout) {
-  __shared__ int e_r[kDpChunk];
-  __shared__ unsigned e_xx[kDpChunk];
-  __shared__ int wcnt[kDpWaves];
+  __shared__ int e_r[kSegChunk];
+  __shared__ unsigned e_xx[kSegChunk];
+  __shared__ int wcnt[kSegWaves];
   __shared__ int s_cnt;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int bid = (int)blockIdx.x;
-  int l = 0;
-  while (l + 1 < a.num_levels && bid >= gr.block0[l + 1]) ++l;
+  const int l = level_of_block(gr.block0, a.p.num_levels, bid);
   const int rel = bid - gr.block0[l];
   const int rowrel = rel / gr.chunks[l], chunk = rel - rowrel * gr.chunks[l];
-  const int H = a.H[l], W = a.W[l];
+  const int H = a.p.H[l], W = a.p.W[l];
   const int n = rowrel / H, Y = rowrel - n * H;
-  const int X0 = chunk * kDpWaves * kDpSegW;
-  const int X1 = X0 + kDpWaves * kDpSegW - 1 < W - 1 ? X0 + kDpWaves * kDpSegW - 1 : W - 1;
-  const int x0 = X0 + wid * kDpSegW;
-  const int x1 = x0 + kDpSegW - 1 < W - 1 ? x0 + kDpSegW - 1 : W - 1;
+  const int X0 = chunk * kSegWaves * kSegW;
+  const int X1 = X0 + kSegWaves * kSegW - 1 < W - 1 ? X0 + kSegWaves * kSegW - 1 : W - 1;
+  const int x0 = X0 + wid * kSegW;
+  const int x1 = x0 + kSegW - 1 < W - 1 ? x0 + kSegW - 1 : W - 1;
   const bool wave_live = x0 < W;
   const int c0 = (int)blockIdx.y * 256 + lane * 4;
   const bool live = c0 < a.C;
   const int key = n | (l << 16);
-  float acc[kDpSegW][4];
+  float acc[kSegW][4];
 #pragma unroll
-  for (int j = 0; j < kDpSegW; ++j)
+  for (int j = 0; j < kSegW; ++j)
 #pragma unroll
     for (int k = 0; k < 4; ++k) acc[j][k] = 0.0f;
   bool touched = false;
-  for (int rc = 0; rc < R; rc += kDpChunk) {
-    // ---- the list of this round: rois rc .. rc+kDpChunk-1 that reach the workgroup's row span, ascending ----
+  for (int rc = 0; rc < R; rc += kSegChunk) {
+    // ---- the list of this round: rois rc .. rc+kSegChunk-1 that reach the workgroup's row span, ascending ----
     __syncthreads();
     if (tid == 0) s_cnt = 0;
     __syncthreads();
-    const int rend = rc + kDpChunk < R ? rc + kDpChunk : R;
-    for (int rb = rc; rb < rend; rb += kDpWaves * 64) {
+    const int rend = rc + kSegChunk < R ? rc + kSegChunk : R;
+    for (int rb = rc; rb < rend; rb += kSegWaves * 64) {
       const int r = rb + tid;
       bool hit = false;
       unsigned xx = 0u;
       if (r < rend) {
         const DpRoiRec t = roi[r];
         xx = t.xx;
-        hit = t.nl == key && dp_span_hits(t.yy, Y, Y) && dp_span_hits(t.xx, X0, X1);
+        hit = t.nl == key && span_hits(t.yy, Y, Y) && span_hits(t.xx, X0, X1);
       }
-      const unsigned long long mk = __ballot(hit);
-      if (lane == 0) wcnt[wid] = __popcll(mk);
-      __syncthreads();
-      int base = s_cnt;
-#pragma unroll
-      for (int w = 0; w < kDpWaves; ++w) base += (w < wid) ? wcnt[w] : 0;
-      if (hit) {
-        const int k = base + __popcll(mk & ((1ull << lane) - 1ull));
+      block_compact_ascending<kSegWaves>(hit, lane, wid, wcnt, &s_cnt, [&](int k) {
         e_r[k] = r;
         e_xx[k] = xx;
-      }
-      __syncthreads();
-      if (tid == 0) {
-        int tt = s_cnt;
-#pragma unroll
-        for (int w = 0; w < kDpWaves; ++w) tt += wcnt[w];
-        s_cnt = tt;
-      }
-      __syncthreads();
+      });
     }
     const int cnt = s_cnt;
     if (!wave_live) continue;             // (every wave reaches the barriers above)
     // ---- walk: rois ascending, their bins ascending, samples ih-major ----
     for (int base = 0; base < cnt; base += 64) {
       const int kk = base + lane;
-      const bool hitk = kk < cnt && dp_span_hits(e_xx[kk < cnt ? kk : 0], x0, x1);
+      const bool hitk = kk < cnt && span_hits(e_xx[kk < cnt ? kk : 0], x0, x1);
       unsigned long long mr = __ballot(hitk);
       while (mr) {
         const int kb = base + __ffsll((long long)mr) - 1;
@@ -401,7 +370,7 @@ dpool_gather_kernel(DPoolArgs a, DpGrid gr, int R, const DpRoiRec* __restrict__ 
         bool hb = false;
         if (lane < a.NB) {
           e = bin[(long long)r * a.NB + lane];
-          hb = dp_span_hits(e.yy, Y, Y) && dp_span_hits(e.xx, x0, x1);
+          hb = span_hits(e.yy, Y, Y) && span_hits(e.xx, x0, x1);
         } else {
           e.ws = e.hs = e.scale = 0.0f;
         }
@@ -410,7 +379,7 @@ dpool_gather_kernel(DPoolArgs a, DpGrid gr, int R, const DpRoiRec* __restrict__ 
         while (mb) {
           const int b = __ffsll((long long)mb) - 1;
           mb &= mb - 1;
-          const float ws = dp_readlane_f(e.ws, b), hs = dp_readlane_f(e.hs, b), sc = dp_readlane_f(e.scale, b);
+          const float ws = readlane_f(e.ws, b), hs = readlane_f(e.hs, b), sc = readlane_f(e.scale, b);
           float go[4] = {0.0f, 0.0f, 0.0f, 0.0f};
           if (live) {
             unpack4_bf16(*(const uint2*)(dout + ((long long)r * a.NB + b) * a.C + c0), go);
@@ -436,19 +405,11 @@ dpool_gather_kernel(DPoolArgs a, DpGrid gr, int R, const DpRoiRec* __restrict__ 
     }
   }
   if (!wave_live || !live || (a.acc && !touched)) return;     // nothing to add: leave the map as it is
-  uint16_t* out = (uint16_t*)a.feat[l] + ((long long)(n * H + Y) * W + x0) * a.C + c0;
+  uint16_t* out = (uint16_t*)a.p.feat[l] + ((long long)(n * H + Y) * W + x0) * a.C + c0;
 #pragma unroll
-  for (int j = 0; j < kDpSegW; ++j) {
+  for (int j = 0; j < kSegW; ++j) {
     if (x0 + j > x1) break;
-    uint16_t* o = out + (long long)j * a.C;
-    float v[4] = {acc[j][0], acc[j][1], acc[j][2], acc[j][3]};
-    if (a.acc) {
-      float old[4];
-      unpack4_bf16(*(const uint2*)o, old);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = v[k] + old[k];
-    }
-    *(uint2*)o = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+    seg_store4<false>(out + (long long)j * a.C, acc[j], a.acc);
   }
 }
 
@@ -475,13 +436,11 @@ static int dpool_check(const mxdet_dpool_desc_t* d, DPoolArgs* a, long long R, c
   MXDET_REQUIRE(!d->modulated || d->mask_stride >= NB, MXDET_ESHAPE, "%s: mask_stride %d < PH * PW", who,
                 d->mask_stride);
   memset(a, 0, sizeof(*a));
-  a->num_levels = f.num_levels; a->lvl_min = f.lvl_min; a->N = d->N; a->C = d->C;
+  pyr_copy(a->p, f, d->N);
+  a->C = d->C;
   a->PH = d->PH; a->PW = d->PW; a->NB = NB; a->S = d->sample_per_part;
   a->mod = d->modulated ? 1 : 0; a->ts = d->trans_stride; a->ms = d->mask_stride; a->acc = d->accumulate ? 1 : 0;
   a->trans_std = d->trans_std;
-  for (int l = 0; l < f.num_levels; ++l) {
-    a->H[l] = f.H[l]; a->W[l] = f.W[l]; a->scale[l] = f.spatial_scale[l]; a->feat[l] = f.feat[l];
-  }
   return MXDET_OK;
 }
 
@@ -553,14 +512,13 @@ extern "C" int mxdet_dpool_bwd_feat(const mxdet_dpool_desc_t* d, const float* ro
                        a.mod ? mask_logit : nullptr, roi, bin);
   DpGrid gr;
   memset(&gr, 0, sizeof(gr));
-  int blocks = 0;
-  for (int l = 0; l < a.num_levels; ++l) {
-    gr.chunks[l] = ceil_div(a.W[l], kDpWaves * kDpSegW);
-    gr.block0[l] = blocks;
-    blocks += a.N * a.H[l] * gr.chunks[l];
+  int blocks_of[8];
+  for (int l = 0; l < a.p.num_levels; ++l) {
+    gr.chunks[l] = ceil_div(a.p.W[l], kSegWaves * kSegW);
+    blocks_of[l] = a.p.N * a.p.H[l] * gr.chunks[l];
   }
-  gr.block0[a.num_levels] = blocks;
-  hipLaunchKernelGGL(dpool_gather_kernel, dim3((unsigned)blocks, (unsigned)ceil_div(a.C, 256)), dim3(kDpWaves * 64), 0, s,
+  const int blocks = layout_block0(gr.block0, blocks_of, a.p.num_levels);
+  hipLaunchKernelGGL(dpool_gather_kernel, dim3((unsigned)blocks, (unsigned)ceil_div(a.C, 256)), dim3(kSegWaves * 64), 0, s,
                      a, gr, (int)R, (const DpRoiRec*)roi, (const DpBinRec*)bin, dout);
   return check_launch("dpool_bwd_feat");
 }

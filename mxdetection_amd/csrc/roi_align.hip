@@ -5,16 +5,11 @@
 // plus a concat/gather. Channels-last makes every bilinear tap a contiguous C*2-byte row segment:
 // a lane owns 8 channels (one 16-B load per tap), so a 256-channel tap is one 512-B coalesced read.
 // HBM/L2-gather bound: algorithmic bytes = R*PH*PW*C*2 written + the touched feature rows read.
-#include "common.h"
+// The pyramid argument, the roi header clamp, packed spans and the tile-gather skeleton of the segment form (level of a
+// workgroup, ascending LDS roi list, row write-out) are roi_gather.h's, shared with deform_roi_pool.hip.
+#include "roi_gather.h"
 
 namespace mxdet {
-
-struct FeatPyr {
-  int num_levels, lvl_min, N;
-  int H[8], W[8];
-  float scale[8];
-  void* feat[8];
-};
 
 struct RoiGeom {
   float start_w, start_h, bin_w, bin_h;
@@ -26,11 +21,8 @@ __device__ __forceinline__ RoiGeom roi_geom(const FeatPyr& f, const float* __res
                                             int PW, int sampling_ratio) {
   RoiGeom g;
   const float* q = rois + r * 5;
-  int l = levels[r] - f.lvl_min;
-  l = l < 0 ? 0 : (l >= f.num_levels ? f.num_levels - 1 : l);
-  g.lvl = l;
-  g.batch = (int)q[0];
-  g.batch = g.batch < 0 ? 0 : (g.batch >= f.N ? f.N - 1 : g.batch);  // never index outside the batch
+  roi_image_level(f, rois, levels, r, &g.lvl, &g.batch);
+  const int l = g.lvl;
   float s = f.scale[l];
   g.start_w = q[1] * s;
   g.start_h = q[2] * s;
@@ -60,18 +52,41 @@ struct Taps {
   bool valid;
 };
 
+// coordinate of sample i of bin b of an axis with g samples per bin -- the one place this is computed; the forward
+// is bit-exact against the oracle, so: multiply; add; (i + 0.5f) * bin; divide by (float)g; add
+__device__ __forceinline__ float roi_sample_coord(float start, float bin, int b, int i, int g) {
+  float v = start + (float)b * bin;
+  return v + (((float)i + 0.5f) * bin) / (float)g;
+}
+
+// ... of sample s of the axis (bin = s / sr); SR = the sampling ratio when it is known at compile time (0: sr)
+template <int SR>
+__device__ __forceinline__ float roi_axis_coord(float start, float bin, int s, int sr) {
+  const int b = SR ? s / SR : s / sr, i = s - b * (SR ? SR : sr);
+  return roi_sample_coord(start, bin, b, i, SR ? SR : sr);
+}
+
+// one axis of a bilinear sample: the two pixels, their weights, and whether the sample counts
+struct AxisSample { int lo, hi; float wlo, whi; bool valid; };
+
+__device__ __forceinline__ AxisSample roi_axis_sample(float v, int L) {
+  AxisSample a;
+  a.valid = !(v < -1.0f || v > (float)L);
+  if (v <= 0.0f) v = 0.0f;
+  int lo = (int)v;
+  if (lo >= L - 1) { a.hi = lo = L - 1; v = (float)lo; } else { a.hi = lo + 1; }
+  a.lo = lo;
+  a.whi = v - (float)lo;
+  a.wlo = 1.0f - a.whi;
+  return a;
+}
+
 __device__ __forceinline__ Taps bilinear_taps(float y, float x, int H, int W) {
+  const AxisSample ay = roi_axis_sample(y, H), ax = roi_axis_sample(x, W);
   Taps t;
-  t.valid = !(y < -1.0f || y > (float)H || x < -1.0f || x > (float)W);
-  if (y <= 0.0f) y = 0.0f;
-  if (x <= 0.0f) x = 0.0f;
-  int yl = (int)y, xl = (int)x, yh, xh;
-  if (yl >= H - 1) { yh = yl = H - 1; y = (float)yl; } else { yh = yl + 1; }
-  if (xl >= W - 1) { xh = xl = W - 1; x = (float)xl; } else { xh = xl + 1; }
-  float ly = y - (float)yl, lx = x - (float)xl;
-  float hy = 1.0f - ly, hx = 1.0f - lx;
-  t.w1 = hy * hx; t.w2 = hy * lx; t.w3 = ly * hx; t.w4 = ly * lx;
-  t.yl = yl; t.yh = yh; t.xl = xl; t.xh = xh;
+  t.valid = ay.valid && ax.valid;
+  t.w1 = ay.wlo * ax.wlo; t.w2 = ay.wlo * ax.whi; t.w3 = ay.whi * ax.wlo; t.w4 = ay.whi * ax.whi;
+  t.yl = ay.lo; t.yh = ay.hi; t.xl = ax.lo; t.xh = ax.hi;
   return t;
 }
 
@@ -94,13 +109,13 @@ roi_align_fwd_kernel(FeatPyr f, int C, const float* __restrict__ rois,
 #pragma unroll
     for (int k = 0; k < 8; ++k) acc[k] = 0.0f;
     for (int iy = 0; iy < g.gh; ++iy) {
-      float y = g.start_h + (float)ph * g.bin_h;
-      y = y + (((float)iy + 0.5f) * g.bin_h) / (float)g.gh;
+      const float y = roi_sample_coord(g.start_h, g.bin_h, ph, iy, g.gh);
       for (int ix = 0; ix < g.gw; ++ix) {
-        float x = g.start_w + (float)pw * g.bin_w;
-        x = x + (((float)ix + 0.5f) * g.bin_w) / (float)g.gw;
-        Taps t = bilinear_taps(y, x, g.H, g.W);
+        const float x = roi_sample_coord(g.start_w, g.bin_w, pw, ix, g.gw);
+        const Taps t = bilinear_taps(y, x, g.H, g.W);
         if (!t.valid) continue;
+        // (this item loop is deform_roi_pool.hip's too, with another corner order; as one shared function taking the
+        // four corner pointers it compiled to two pairs of loads instead of four in flight: 44.1 against 43.5 us)
         const uint4 v1 = *(const uint4*)(feat + ((long long)t.yl * g.W + t.xl) * C + cg * 8);
         const uint4 v2 = *(const uint4*)(feat + ((long long)t.yl * g.W + t.xh) * C + cg * 8);
         const uint4 v3 = *(const uint4*)(feat + ((long long)t.yh * g.W + t.xl) * C + cg * 8);
@@ -147,12 +162,10 @@ roi_align_bwd_kernel(FeatPyr f, int C, const float* __restrict__ rois,
     float go = bf16_bits_to_f32(gout[(r * PH * PW + bin) * C + c]) / count;
     if (go == 0.0f) continue;
     for (int iy = 0; iy < g.gh; ++iy) {
-      float y = g.start_h + (float)ph * g.bin_h;
-      y = y + (((float)iy + 0.5f) * g.bin_h) / (float)g.gh;
+      const float y = roi_sample_coord(g.start_h, g.bin_h, ph, iy, g.gh);
       for (int ix = 0; ix < g.gw; ++ix) {
-        float x = g.start_w + (float)pw * g.bin_w;
-        x = x + (((float)ix + 0.5f) * g.bin_w) / (float)g.gw;
-        Taps t = bilinear_taps(y, x, g.H, g.W);
+        const float x = roi_sample_coord(g.start_w, g.bin_w, pw, ix, g.gw);
+        const Taps t = bilinear_taps(y, x, g.H, g.W);
         if (!t.valid) continue;
         atomicAdd(dfeat + ((long long)t.yl * g.W + t.xl) * C + c, t.w1 * go);
         atomicAdd(dfeat + ((long long)t.yl * g.W + t.xh) * C + c, t.w2 * go);
@@ -200,30 +213,11 @@ roi_bwd_tab_kernel(FeatPyr f, const float* __restrict__ rois, const int32_t* __r
   const int NS = isx ? PW * g.gw : PH * g.gh;
   int lo = 1 << 30, hi = -1;
   if (s < NS) {
-    if (!isx) {
-      const int ph = s / g.gh, iy = s - ph * g.gh;
-      float y = g.start_h + (float)ph * g.bin_h;
-      y = y + (((float)iy + 0.5f) * g.bin_h) / (float)g.gh;
-      const Taps tp = bilinear_taps(y, 0.0f, g.H, g.W);       // the row part does not depend on x
-      const bool vy = !(y < -1.0f || y > (float)g.H);
-      // hy, ly exactly as bilinear_taps derives them
-      float yy = y <= 0.0f ? 0.0f : y;
-      if ((int)yy >= g.H - 1) yy = (float)(g.H - 1);
-      const float lyv = yy - (float)tp.yl, hyv = 1.0f - lyv;
-      t.yl[s] = (short)tp.yl; t.yh[s] = (short)tp.yh; t.hy[s] = hyv; t.ly[s] = lyv; t.vy[s] = vy ? 1 : 0;
-      if (vy) { lo = tp.yl; hi = tp.yh; }
-    } else {
-      const int pw = s / g.gw, ix = s - pw * g.gw;
-      float x = g.start_w + (float)pw * g.bin_w;
-      x = x + (((float)ix + 0.5f) * g.bin_w) / (float)g.gw;
-      const Taps tp = bilinear_taps(0.0f, x, g.H, g.W);
-      const bool vx = !(x < -1.0f || x > (float)g.W);
-      float xx = x <= 0.0f ? 0.0f : x;
-      if ((int)xx >= g.W - 1) xx = (float)(g.W - 1);
-      const float lxv = xx - (float)tp.xl, hxv = 1.0f - lxv;
-      t.xl[s] = (short)tp.xl; t.xh[s] = (short)tp.xh; t.hx[s] = hxv; t.lx[s] = lxv; t.vx[s] = vx ? 1 : 0;
-      if (vx) { lo = tp.xl; hi = tp.xh; }
-    }
+    const AxisSample a = isx ? roi_axis_sample(roi_axis_coord<0>(g.start_w, g.bin_w, s, g.gw), g.W)
+                             : roi_axis_sample(roi_axis_coord<0>(g.start_h, g.bin_h, s, g.gh), g.H);
+    if (!isx) { t.yl[s] = (short)a.lo; t.yh[s] = (short)a.hi; t.hy[s] = a.wlo; t.ly[s] = a.whi; t.vy[s] = a.valid ? 1 : 0; }
+    else { t.xl[s] = (short)a.lo; t.xh[s] = (short)a.hi; t.hx[s] = a.wlo; t.lx[s] = a.whi; t.vx[s] = a.valid ? 1 : 0; }
+    if (a.valid) { lo = a.lo; hi = a.hi; }
   }
   // min / max inside each 32-lane half (rows | columns)
 #pragma unroll
@@ -243,7 +237,7 @@ roi_bwd_tab_kernel(FeatPyr f, const float* __restrict__ rois, const int32_t* __r
 }
 
 struct RoiRows {                       // row r of level l, image n has id row0[l] + n * H[l] + r
-  int row0[8], rows_total;
+  int row0[9], rows_total;           // row0[num_levels] = rows_total
   int tiles_w[8], block0[9];           // workgroups: block0[l] + (n * H[l] + y) * tiles_w[l] + tile
 };
 
@@ -253,8 +247,7 @@ roi_bwd_rows_kernel(FeatPyr f, RoiRows rr, const RoiBox* __restrict__ box, int R
                     unsigned short* __restrict__ row_list, int* __restrict__ row_count) {
   const int row = (int)blockIdx.x, lane = threadIdx.x;
   if (row >= rr.rows_total) return;
-  int l = 0;
-  while (l + 1 < f.num_levels && row >= rr.row0[l + 1]) ++l;
+  const int l = level_of_block(rr.row0, f.num_levels, row);
   const int rel = row - rr.row0[l];
   const int n = rel / f.H[l], y = rel - n * f.H[l];
   int cnt = 0;
@@ -281,9 +274,8 @@ __global__ void __launch_bounds__(64)
 roi_align_bwd_gather_kernel(FeatPyr f, RoiRows rr, int C, const RoiTab* __restrict__ tab, const RoiBox* __restrict__ box, int R,
                             const unsigned short* __restrict__ row_list, const int* __restrict__ row_count,
                             int PH, int PW, int sr, const uint16_t* __restrict__ gout, int accumulate) {
-  int l = 0;
   const int bid = (int)blockIdx.x, lane = threadIdx.x;
-  while (l + 1 < f.num_levels && bid >= rr.block0[l + 1]) ++l;
+  const int l = level_of_block(rr.block0, f.num_levels, bid);
   const int rel = bid - rr.block0[l];
   const int tw = rr.tiles_w[l];
   const int rowrel = rel / tw, tile = rel - rowrel * tw;
@@ -333,8 +325,7 @@ roi_align_bwd_gather_kernel(FeatPyr f, RoiRows rr, int C, const RoiTab* __restri
         const int sy = __ffsll((long long)my) - 1;
         my &= my - 1;
         const int yl = __builtin_amdgcn_readlane(yl_, sy), yh = __builtin_amdgcn_readlane(yh_, sy);
-        const float hy = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(hy_), sy));
-        const float ly = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(ly_), sy));
+        const float hy = readlane_f(hy_, sy), ly = readlane_f(ly_, sy);
         const int ph = sy / sr;
         unsigned long long m2 = mx;
         // two column samples per trip: their gradient loads are independent and overlap (the loop is otherwise one
@@ -353,10 +344,9 @@ roi_align_bwd_gather_kernel(FeatPyr f, RoiRows rr, int C, const RoiTab* __restri
             const int sx = half ? sxb : sxa;
             const uint2 gv = half ? gvb : gva;
             const int xl = __builtin_amdgcn_readlane(xl_, sx), xh = __builtin_amdgcn_readlane(xh_, sx);
-            const float hx = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(hx_), sx));
-            const float lx = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(lx_), sx));
-            // (here and at the two accumulate sites below the half-vector unpack stays spelled out: with unpack4_bf16
-            // hipcc emits different code for the gather and segment kernels)
+            const float hx = readlane_f(hx_, sx), lx = readlane_f(lx_, sx);
+            // (here, at the segment form's fold and in seg_store4 the half-vector unpack stays spelled out: with
+            // unpack4_bf16 hipcc emits different code for the gather and segment kernels)
             float go[4] = {__uint_as_float(gv.x << 16), __uint_as_float(gv.x & 0xffff0000u),
                            __uint_as_float(gv.y << 16), __uint_as_float(gv.y & 0xffff0000u)};
             // grad / count: a power-of-two count (sampling_ratio 1, 2, 4) divides exactly as a multiplication
@@ -385,17 +375,8 @@ roi_align_bwd_gather_kernel(FeatPyr f, RoiRows rr, int C, const RoiTab* __restri
 #pragma unroll
     for (int j = 0; j < kRoiTileW; ++j) {
       if (x0 + j >= W || !live) break;
-      uint16_t* o = out + (size_t)j * C + c0;
-      float v[4] = {a0[j], a1[j], a2[j], a3[j]};
-      if (accumulate) {
-        const uint2 e = *(const uint2*)o;
-        v[0] = v[0] + __uint_as_float(e.x << 16); v[1] = v[1] + __uint_as_float(e.x & 0xffff0000u);
-        v[2] = v[2] + __uint_as_float(e.y << 16); v[3] = v[3] + __uint_as_float(e.y & 0xffff0000u);
-      }
-      uint2 w;
-      w.x = (unsigned)f32_to_bf16_bits(v[0]) | ((unsigned)f32_to_bf16_bits(v[1]) << 16);
-      w.y = (unsigned)f32_to_bf16_bits(v[2]) | ((unsigned)f32_to_bf16_bits(v[3]) << 16);
-      *(uint2*)o = w;
+      const float v[4] = {a0[j], a1[j], a2[j], a3[j]};
+      seg_store4<true>(out + (size_t)j * C + c0, v, accumulate);
     }
   }
 }
@@ -412,10 +393,7 @@ roi_align_bwd_gather_kernel(FeatPyr f, RoiRows rr, int C, const RoiTab* __restri
 // (T[pw] = sum_by ay * dY) and distributes T over its 8 pixels with the column weights (lane 32+s holds column sample
 // s; v_readlane hands them out as scalars). Fixed summation order (roi ascending, row bins, column bins): bit-
 // reproducible. The sums differ from the oracle's sample-by-sample order in the last bits (tolerance in the test).
-constexpr int kSegW = 8;          // pixels per wave
-constexpr int kSegWaves = 4;      // waves (segment columns) per workgroup
-constexpr int kSegChunk = 1024;   // rois per list round
-
+// (kSegW pixels per wave, kSegWaves waves per workgroup, kSegChunk rois per list round: roi_gather.h)
 struct RoiSegGrid {
   int block0[9];                  // first workgroup of level l
   int chunks[8];                  // workgroups along a row
@@ -426,39 +404,17 @@ struct RoiSegGrid {
 
 struct RoiSeg {                   // per roi, 32 B
   int nl;                         // image | level << 16 (level 0xffff: no valid sample)
-  unsigned yy, xx;                // ylo | yhi << 16, xlo | xhi << 16: pixel bounding box of its valid samples
+  unsigned yy, xx;                // span_pack(ylo, yhi), span_pack(xlo, xhi): pixel bounding box of its valid samples
   int r;
   float start_h, bin_h, start_w, bin_w;
 };
 
-struct AxisSample { int lo, hi; float wlo, whi; bool valid; };
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 // value of lane + 1 inside a 16-lane row (DPP row_shl:1; the last lane of a row reads 0): the two samples of a bin
 // never straddle a row, so this replaces a ds_bpermute round trip per weight
 __device__ __forceinline__ float lane_plus1(float v) {
   return __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), 0x101, 0xf, 0xf, true));
-}
-
-// coordinate of sample s of an axis (bin = s / sr), exactly as the forward / the oracle computes it
-template <int SR>
-__device__ __forceinline__ float roi_axis_coord(float start, float bin, int s, int sr) {
-  const int b = SR ? s / SR : s / sr, i = s - b * (SR ? SR : sr);
-  float v = start + (float)b * bin;
-  return v + (((float)i + 0.5f) * bin) / (float)(SR ? SR : sr);
-}
-
-// the per-axis half of bilinear_taps
-__device__ __forceinline__ AxisSample roi_axis_sample(float v, int L) {
-  AxisSample a;
-  a.valid = !(v < -1.0f || v > (float)L);
-  if (v <= 0.0f) v = 0.0f;
-  int lo = (int)v;
-  if (lo >= L - 1) { a.hi = lo = L - 1; v = (float)lo; } else { a.hi = lo + 1; }
-  a.lo = lo;
-  a.whi = v - (float)lo;
-  a.wlo = 1.0f - a.whi;
-  return a;
 }
 
 // pixel range [lo, hi] touched by the valid samples of one axis (lo > hi: none)
@@ -483,8 +439,8 @@ roi_bwd_box_kernel(FeatPyr f, const float* __restrict__ rois, const int32_t* __r
   RoiSeg o;
   const bool any = ylo <= yhi && xlo <= xhi;
   o.nl = g.batch | ((any ? g.lvl : 0xffff) << 16);
-  o.yy = (unsigned)ylo | ((unsigned)yhi << 16);
-  o.xx = (unsigned)xlo | ((unsigned)xhi << 16);
+  o.yy = span_pack(ylo, yhi);
+  o.xx = span_pack(xlo, xhi);
   o.r = r;
   o.start_h = g.start_h; o.bin_h = g.bin_h; o.start_w = g.start_w; o.bin_w = g.bin_w;
   seg[r] = o;
@@ -502,9 +458,8 @@ roi_bwd_seg_kernel(FeatPyr f, RoiSegGrid gr, int C, const RoiSeg* __restrict__ s
   const int sr = SR ? SR : sr_;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int l = 0;
   const int bid = (int)blockIdx.x;
-  while (l + 1 < f.num_levels && bid >= gr.block0[l + 1]) ++l;
+  const int l = level_of_block(gr.block0, f.num_levels, bid);
   const int rel = bid - gr.block0[l];
   const int per_img = gr.bands[l] * gr.chunks[l];
   const int n = rel / per_img, rem = rel - n * per_img;
@@ -548,28 +503,12 @@ roi_bwd_seg_kernel(FeatPyr f, RoiSegGrid gr, int C, const RoiSeg* __restrict__ s
       RoiSeg t;
       if (r < rend) {
         t = seg[r];
-        hit = t.nl == key && (int)(t.yy >> 16) >= Y0 && (int)(t.yy & 0xffffu) <= Y1 &&
-              (int)(t.xx >> 16) >= X0 && (int)(t.xx & 0xffffu) <= X1;
+        hit = t.nl == key && span_hits(t.yy, Y0, Y1) && span_hits(t.xx, X0, X1);
       }
-      const unsigned long long m = __ballot(hit);
-      if (lane == 0) wcnt[wid] = __popcll(m);
-      __syncthreads();
-      int base = s_cnt;
-#pragma unroll
-      for (int w = 0; w < kSegWaves; ++w) base += (w < wid) ? wcnt[w] : 0;
-      if (hit) {
-        const int k = base + __popcll(m & ((1ull << lane) - 1ull));
+      block_compact_ascending<kSegWaves>(hit, lane, wid, wcnt, &s_cnt, [&](int k) {
         e_xx[k] = t.xx; e_yy[k] = t.yy; e_r[k] = t.r;
         e_g[k] = make_float4(t.start_h, t.bin_h, t.start_w, t.bin_w);
-      }
-      __syncthreads();
-      if (tid == 0) {
-        int tt = s_cnt;
-#pragma unroll
-        for (int w = 0; w < kSegWaves; ++w) tt += wcnt[w];
-        s_cnt = tt;
-      }
-      __syncthreads();
+      });
     }
     const int cnt = s_cnt;
     if (!wave_live) continue;             // (the barriers above are reached by every wave: `continue` re-enters the loop)
@@ -586,8 +525,7 @@ roi_bwd_seg_kernel(FeatPyr f, RoiSegGrid gr, int C, const RoiSeg* __restrict__ s
         const int kk = base + lane;
         unsigned xk = 0u, yk = 0u;
         if (kk < cnt) { xk = e_xx[kk]; yk = e_yy[kk]; }
-        const bool hitk = kk < cnt && (int)(xk >> 16) >= x0 && (int)(xk & 0xffffu) <= x1 &&
-                          (int)(yk >> 16) >= Y && (int)(yk & 0xffffu) <= Y;
+        const bool hitk = kk < cnt && span_hits(xk, x0, x1) && span_hits(yk, Y, Y);
         unsigned long long mr = __ballot(hitk);
         while (mr) {
           const int kb = base + __ffsll((long long)mr) - 1;
@@ -633,7 +571,7 @@ roi_bwd_seg_kernel(FeatPyr f, RoiSegGrid gr, int C, const RoiSeg* __restrict__ s
             for (int by = 0; by < 3; ++by) {
               const bool rowok = b0 + by <= pb1;
               const int ph = rowok ? b0 + by : pb1;
-              wyb[by] = rowok ? __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(ayb), ph * sr)) : 0.0f;
+              wyb[by] = rowok ? readlane_f(ayb, ph * sr) : 0.0f;
 #pragma unroll
               for (int pw = 0; pw < PWT; ++pw) {
                 g[by][pw] = make_uint2(0u, 0u);
@@ -661,7 +599,7 @@ roi_bwd_seg_kernel(FeatPyr f, RoiSegGrid gr, int C, const RoiSeg* __restrict__ s
               }
 #pragma unroll
               for (int j = 0; j < kSegW; ++j) {
-                const float w = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(axb[j]), 32 + pw * sr));
+                const float w = readlane_f(axb[j], 32 + pw * sr);
                 const f32x2_t wv = {w, w};
                 acc[j][0] = __builtin_elementwise_fma(wv, T0, acc[j][0]);
                 acc[j][1] = __builtin_elementwise_fma(wv, T1, acc[j][1]);
@@ -678,17 +616,8 @@ roi_bwd_seg_kernel(FeatPyr f, RoiSegGrid gr, int C, const RoiSeg* __restrict__ s
 #pragma unroll
       for (int j = 0; j < kSegW; ++j) {
         if (x0 + j >= W) break;
-        uint16_t* o = out + (size_t)j * C;
-        float v[4] = {acc[j][0][0], acc[j][0][1], acc[j][1][0], acc[j][1][1]};
-        if (add) {
-          const uint2 ee = *(const uint2*)o;
-          v[0] = v[0] + __uint_as_float(ee.x << 16); v[1] = v[1] + __uint_as_float(ee.x & 0xffff0000u);
-          v[2] = v[2] + __uint_as_float(ee.y << 16); v[3] = v[3] + __uint_as_float(ee.y & 0xffff0000u);
-        }
-        uint2 w;
-        w.x = (unsigned)f32_to_bf16_bits(v[0]) | ((unsigned)f32_to_bf16_bits(v[1]) << 16);
-        w.y = (unsigned)f32_to_bf16_bits(v[2]) | ((unsigned)f32_to_bf16_bits(v[3]) << 16);
-        *(uint2*)o = w;
+        const float v[4] = {acc[j][0][0], acc[j][0][1], acc[j][1][0], acc[j][1][1]};
+        seg_store4<true>(out + (size_t)j * C, v, add);
       }
     }
   }
@@ -697,15 +626,9 @@ roi_bwd_seg_kernel(FeatPyr f, RoiSegGrid gr, int C, const RoiSeg* __restrict__ s
 static int fill(FeatPyr& d, const mxdet_feat_pyramid_t* f, int N, const char* who) {
   MXDET_REQUIRE(f != nullptr, MXDET_EINVAL, "%s: null pyramid", who);
   MXDET_REQUIRE(f->num_levels > 0 && f->num_levels <= 8, MXDET_ESHAPE, "%s: bad level count", who);
-  memset(&d, 0, sizeof(d));
-  d.num_levels = f->num_levels;
-  d.lvl_min = f->lvl_min;
-  d.N = N;
-  for (int l = 0; l < f->num_levels; ++l) {
-    MXDET_REQUIRE(f->H[l] > 0 && f->W[l] > 0 && f->feat[l], MXDET_EINVAL, "%s: level %d incomplete",
-                  who, l);
-    d.H[l] = f->H[l]; d.W[l] = f->W[l]; d.scale[l] = f->spatial_scale[l]; d.feat[l] = f->feat[l];
-  }
+  for (int l = 0; l < f->num_levels; ++l)
+    MXDET_REQUIRE(f->H[l] > 0 && f->W[l] > 0 && f->feat[l], MXDET_EINVAL, "%s: level %d incomplete", who, l);
+  pyr_copy(d, *f, N);
   return MXDET_OK;
 }
 
@@ -748,16 +671,14 @@ extern "C" int mxdet_roi_align_bwd(const mxdet_feat_pyramid_t* f, int32_t N, int
 
 static size_t roi_gather_carve(const FeatPyr& d, long long R, RoiRows* rr, size_t* off_tab, size_t* off_list, size_t* off_cnt,
                                size_t* off_box) {
-  int rows = 0, blocks = 0;
+  int rows_of[8], blocks_of[8];
   for (int l = 0; l < d.num_levels; ++l) {
-    rr->row0[l] = rows;
-    rows += d.N * d.H[l];
+    rows_of[l] = d.N * d.H[l];
     rr->tiles_w[l] = ceil_div(d.W[l], kRoiTileW);
-    rr->block0[l] = blocks;
-    blocks += d.N * d.H[l] * rr->tiles_w[l];
+    blocks_of[l] = rows_of[l] * rr->tiles_w[l];
   }
-  rr->block0[d.num_levels] = blocks;
-  rr->rows_total = rows;
+  const int rows = rr->rows_total = layout_block0(rr->row0, rows_of, d.num_levels);
+  layout_block0(rr->block0, blocks_of, d.num_levels);
   size_t off = 0;
   *off_tab = off; off = align_up(off + (size_t)R * sizeof(RoiTab), 256);
   *off_list = off; off = align_up(off + (size_t)rows * (size_t)R * sizeof(unsigned short), 256);
@@ -769,9 +690,7 @@ static size_t roi_gather_carve(const FeatPyr& d, long long R, RoiRows* rr, size_
 extern "C" size_t mxdet_roi_align_bwd_gather_workspace_bytes(const mxdet_feat_pyramid_t* f, int32_t N, int64_t R) {
   if (!f || N <= 0 || R <= 0 || f->num_levels <= 0 || f->num_levels > 8) return 0;
   FeatPyr d;
-  memset(&d, 0, sizeof(d));
-  d.num_levels = f->num_levels; d.N = N;
-  for (int l = 0; l < f->num_levels; ++l) { d.H[l] = f->H[l]; d.W[l] = f->W[l]; }
+  pyr_copy(d, *f, N);
   RoiRows rr; size_t a, b, c, e;
   return roi_gather_carve(d, R, &rr, &a, &b, &c, &e);
 }
@@ -803,7 +722,7 @@ static int roi_bwd_gather_impl(const mxdet_feat_pyramid_t* f, int32_t N, int32_t
     RoiSeg* seg = (RoiSeg*)((char*)workspace + o_box);
     RoiSegGrid gr;
     memset(&gr, 0, sizeof(gr));
-    int blocks = 0;
+    int blocks_of[8];
     const int rows_big = (int)tuning(MXDET_TUNE_ROI_ROWS);
     for (int l = 0; l < d.num_levels; ++l) {
       const int segs = ceil_div(d.W[l], kSegW);
@@ -813,10 +732,9 @@ static int roi_bwd_gather_impl(const mxdet_feat_pyramid_t* f, int32_t N, int32_t
       // pixel -- keep one row per tile for parallelism; more rois than one list round: one row (sums stay in registers)
       gr.rows_per_wg[l] = (R > kSegChunk || d.H[l] < 64 || rows_big < 1) ? 1 : rows_big;
       gr.bands[l] = ceil_div(d.H[l], gr.rows_per_wg[l]);
-      gr.block0[l] = blocks;
-      blocks += d.N * gr.bands[l] * gr.chunks[l];
+      blocks_of[l] = d.N * gr.bands[l] * gr.chunks[l];
     }
-    gr.block0[d.num_levels] = blocks;
+    const int blocks = layout_block0(gr.block0, blocks_of, d.num_levels);
     if (mode != 2)
       hipLaunchKernelGGL(roi_bwd_box_kernel, dim3((unsigned)ceil_div((int)R, 256)), dim3(256), 0, s, d, rois, levels, (int)R,
                          PH, PW, sampling_ratio, seg);

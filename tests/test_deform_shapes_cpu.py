@@ -15,8 +15,8 @@ from test_gpu_deform_conv import _bf16, _offsets
 
 SCAN_BLOCK = 2048          # lists per scan workgroup (kScanThreads * kScanPerThread)
 SCAN_THREADS = 256         # block sums per pass of deform_scan_blocks_kernel
-DP_CHUNK = 1024            # rois per list round of dpool_gather_kernel (kDpChunk)
-DP_SEG = 8                 # pixels per wave (kDpSegW)
+DP_CHUNK = 1024            # rois per list round of dpool_gather_kernel (kSegChunk)
+DP_SEG = 8                 # pixels per wave (kSegW)
 DP_CLEAR = 2.0 ** -10      # px: every generated dpool sample keeps this distance from the lines below
 AWAY = -100.0              # an offset that puts a sample outside every map used here (|AWAY| < 128, bf16-exact)
 
