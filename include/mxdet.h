@@ -538,6 +538,46 @@ int mxdet_mask_loss(const uint16_t* logits, const int32_t* cls, const uint8_t* t
 size_t mxdet_mask_paste_workspace_bytes(int64_t R, int32_t S);
 int mxdet_mask_paste(const uint16_t* logits, const float* dets, int64_t R, int32_t S, int32_t Cpad, int32_t H, int32_t W,
                      float thresh, uint8_t* masks, void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
+/* Mask Scoring R-CNN (Huang et al., CVPR 2019): a MaskIoU head regresses the IoU between the predicted
+ * mask and its ground truth; the test-time mask score is the box score times that IoU. All fp32 arithmetic below is
+ * unfused, one IEEE operation per product / quotient / sum in the order written.
+ *
+ * MaskIoU target, out fp32 [R]. rois [R,5], matched_gt / cls [R] as mxdet_mask_target takes / writes them, gt_boxes
+ * [N,G_boxes,5] (class < 0: padding; G_boxes >= G, rows past G unused), gt_masks [N,G,H,W] u8, logits bf16 [R,S,S,Cpad], targets u8 [R,S,S]. Rows with
+ * cls <= 0 (or > Cpad), matched_gt outside [0,G) or an image index outside [0,N) give 0 and read no mask memory. Else,
+ * with n = (int)rois[r,0], g = matched_gt[r]:
+ *   a_full = set pixels of gt_masks[n,g] (0 for a padding instance: those are never read);
+ *   ix1 = max(0, floor(x1)), iy1 = max(0, floor(y1)), ix2 = min(W-1, ceil(x2)), iy2 = min(H-1, ceil(y2));
+ *   a_in = set pixels with ix1 <= x <= ix2, iy1 <= y <= iy2 (0 for an empty clipped box);
+ *   over the S x S map: pred = logit of channel cls-1 > 0; a_pred = sum pred, a_tgt = sum targets, a_ovr = sum pred & targets;
+ *   a_in == 0: 0; else gt_s = ((float)a_tgt * (float)a_full) / (float)a_in, uni = ((float)a_pred + gt_s) - (float)a_ovr,
+ *   out = (float)a_ovr / fmaxf(uni, 1e-7f).
+ * The counts are integers, so the result does not depend on the order of summation. N*G <= 65535. */
+size_t mxdet_maskiou_target_workspace_bytes(int32_t N, int32_t G);
+int mxdet_maskiou_target(const float* rois, const int32_t* matched_gt, const int32_t* cls, const float* gt_boxes,
+                         const uint8_t* gt_masks, const uint16_t* logits, const uint8_t* targets, int64_t R, int32_t N,
+                         int32_t G, int32_t G_boxes, int32_t H, int32_t W, int32_t S, int32_t Cpad, float* out,
+                         void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
+/* MaskIoU head input, out bf16 [R,S/2,S/2,Ctot] (Ctot % 8 == 0, Ctot > C, C % 8 == 0; every channel is written):
+ * channels [0,C) = mpooled [R,S/2,S/2,C]; channel C = bf16(sigmoid(z)), z = the max of the four logits
+ * [2y..2y+1, 2x..2x+1] of channel cls[r]-1 (sigmoid(z) = z >= 0 ? 1/(1+e^-z) : e^z/(1+e^z) with mxdet_expf), 0 for rows
+ * with cls <= 0 or > Cpad; channels (C,Ctot) = 0. */
+int mxdet_maskiou_input(const uint16_t* mpooled, const uint16_t* logits, const int32_t* cls, int64_t R, int32_t S,
+                        int32_t C, int32_t Cpad, int32_t Ctot, uint16_t* out, mxdet_stream_t stream);
+/* Its adjoint for the feature part (the mask channel is a constant): d_mpooled[p,c] = bf16((float)d_mpooled[p,c] +
+ * (float)d_in[p,c]) for c < C over `pixels` rows of d_in [pixels,Ctot] / d_mpooled [pixels,C]; channels >= C are not read. */
+int mxdet_maskiou_input_bwd(const uint16_t* d_in, int64_t pixels, int32_t C, int32_t Ctot, uint16_t* d_mpooled,
+                            mxdet_stream_t stream);
+/* L2 MaskIoU loss. pred / grad bf16 [R,ld] (ld % 8 == 0), cls [R], targets fp32 [R] (mxdet_maskiou_target).
+ * pos = {r: 0 < cls[r] <= ld and targets[r] > 0}, n_pos counted on the device, k = (loss_scale * weight) / (float)max(n_pos,1);
+ * loss_out[0] = k * sum_pos 0.5 * (d*d), d = (float)pred[r,cls-1] - targets[r] (fp32, fixed order: one workgroup);
+ * grad[r,cls-1] = bf16(d * k) for r in pos, every other entry of grad is written as zero. */
+int mxdet_maskiou_loss(const uint16_t* pred, const int32_t* cls, const float* targets, int64_t R, int32_t ld,
+                       float loss_scale, float weight, float* loss_out, uint16_t* grad, mxdet_stream_t stream);
+/* Test time: scores[r] = dets[r,4] * (float)pred[r, class-1] (one fp32 product) with class = (int)dets[r,5]; rows with
+ * class <= 0 (padding) or > ld give 0. dets [R,6] as mxdet_mask_paste takes them, pred bf16 [R,ld]. */
+int mxdet_maskiou_score(const float* dets, const uint16_t* pred, int64_t R, int32_t ld, float* scores,
+                        mxdet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * backbones / necks / rpn_heads / bbox_heads / mask_heads (README.md:27-31) -- dense contractions.

@@ -192,6 +192,13 @@ SIGNATURES = {
     "mxdet_pixel_shuffle2": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mxdet_mask_loss_workspace_bytes": (c_sz, [c_i64, c_i32]),
     "mxdet_mask_loss": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_maskiou_target_workspace_bytes": (c_sz, [c_i32, c_i32]),
+    "mxdet_maskiou_target": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                     c_i32, c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_maskiou_input": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "mxdet_maskiou_input_bwd": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
+    "mxdet_maskiou_loss": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp]),
+    "mxdet_maskiou_score": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "mxdet_conv2d_fwd": (c_i32, [P(ConvDescT), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mxdet_conv2d_fwd_chain": (c_i32, [P(ConvDescT), c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
                                        c_i32, c_vp, c_vp]),

@@ -17,14 +17,20 @@ def build_detector(cfg, device="cuda"):
         if net.assigner != "max_iou":
             raise ValueError("network.assigner = %r: %s keeps the RPN's sampler (atss is a retinanet option)"
                              % (net.assigner, net.type))
+        if net.mask_iou and net.type != "mask_rcnn":
+            raise ValueError("network.mask_iou = %r: %s has no mask branch to score (the MaskIoU head is a mask_rcnn option)"
+                             % (net.mask_iou, net.type))
         dpool = dict(roi_pool=str(net.roi_pool), dpool_trans_std=float(net.dpool_trans_std),
                      dpool_sample_per_part=int(net.dpool_sample_per_part), dpool_offset_fcs=int(net.dpool_offset_fcs))
         heads = dict(bbox_head=str(net.bbox_head), head_norm=str(net.head_norm), gn_groups=net.gn_groups)
         model = FasterRCNN(device, depth=net.backbone_depth, num_classes=net.num_classes, seed=net.seed,
                            rois_per_image=tr.batch_rois, pre_nms_top_n=tr.rpn_pre_nms_top_n,
                            post_nms_top_n=tr.rpn_post_nms_top_n, with_mask=(net.type == "mask_rcnn"), **dcn, **dpool, **heads,
-                           **reg)
+                           **reg, mask_iou=bool(net.mask_iou), mask_iou_weight=net.mask_iou_weight)
     elif net.type == "retinanet":
+        if net.mask_iou:
+            raise ValueError("network.mask_iou = %r: retinanet has no mask branch to score (the MaskIoU head is a mask_rcnn "
+                             "option)" % (net.mask_iou,))
         if net.roi_pool != "roi_align":
             raise ValueError("network.roi_pool = %r: retinanet has no RoI branch" % (net.roi_pool,))
         if net.bbox_head != "2fc" or net.head_norm != "none":

@@ -7,10 +7,11 @@ itself is not declared anywhere in the reference tree; thi
 """
 import torch
 
+from ..core import mask as M_
 from ..core.loss import check_reg_loss
 from .backbones import ResNet
 from .bbox_heads import BBoxHead, ConvFCBBoxHead
-from .mask_heads import FCNMaskHead
+from .mask_heads import FCNMaskHead, MaskIoUHead
 from .necks import FPN
 from .roi_extractors import DeformRoIExtractor, FPNRoIExtractor
 from .rpn_heads import RPNHead
@@ -37,7 +38,8 @@ class FasterRCNN(DetectorBase):
     def __init__(self, device="cuda", depth=50, num_classes=81, seed=7, rpn_seed=99, rois_per_image=512,
                  pre_nms_top_n=2000, post_nms_top_n=2000, with_mask=False, dcn_stages=(), dcn_modulated=True,
                  dcn_groups=1, roi_pool="roi_align", dpool_trans_std=0.1, dpool_sample_per_part=4, dpool_offset_fcs=3,
-                 bbox_head="2fc", head_norm="none", gn_groups=32, reg_loss="smooth_l1", reg_loss_weight=1.0):
+                 bbox_head="2fc", head_norm="none", gn_groups=32, reg_loss="smooth_l1", reg_loss_weight=1.0,
+                 mask_iou=False, mask_iou_weight=1.0):
         """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
         roi_pool: the box branch's RoI pooling -- 'roi_align', or deformable RoI pooling with its offset head, 'dpool'
         (v1) / 'mdpool' (v2, modulated) (roi_extractors.DeformRoIExtractor, options dpool_*). The mask branch keeps its
@@ -46,8 +48,17 @@ class FasterRCNN(DetectorBase):
         gn_groups groups after every conv of the 4conv1fc box head and of the mask head (bbox_heads.ConvFCBBoxHead,
         mask_heads.FCNMaskHead).
         reg_loss / reg_loss_weight: the box head's regression loss -- 'smooth_l1' on the encoded deltas, or 'iou' / 'giou' /
-        'diou' on the decoded box times reg_loss_weight (bbox_heads.BBoxHead). The RPN keeps smooth-L1."""
+        'diou' on the decoded box times reg_loss_weight (bbox_heads.BBoxHead). The RPN keeps smooth-L1.
+        mask_iou / mask_iou_weight: Mask Scoring R-CNN -- a MaskIoU head on the mask branch (mask_heads.MaskIoUHead) whose
+        L2 loss, times mask_iou_weight, is the step's fourth loss; predict(with_masks=True) then also returns the mask
+        scores. Needs with_mask. The head draws its initial weights from a generator of its own, so every other parameter
+        starts exactly as in the model without it."""
         check_head_options(bbox_head, head_norm, gn_groups, with_mask)
+        if mask_iou and not with_mask:
+            raise ValueError("mask_iou needs the mask branch (with_mask=True): the MaskIoU head scores the mask head's output")
+        if mask_iou and not (isinstance(mask_iou_weight, (int, float)) and not isinstance(mask_iou_weight, bool)
+                             and 0.0 < float(mask_iou_weight) < float("inf")):
+            raise ValueError("mask_iou_weight must be a positive finite number (got %r)" % (mask_iou_weight,))
         check_reg_loss(reg_loss, reg_loss_weight)
         if roi_pool not in ("roi_align", "dpool", "mdpool"):
             raise ValueError("roi_pool must be 'roi_align', 'dpool' or 'mdpool' (got %r)" % (roi_pool,))
@@ -60,8 +71,12 @@ class FasterRCNN(DetectorBase):
         # RoIAlign backward: deterministic gather form (no atomics, no fp32 accumulators, writes the bf16 maps directly);
         # False selects the fp32-atomic scatter form (310 us + zero-fill + finalize at the benchmark shape)
         self.roi_bwd_gather = True
-        self.mask_head = None
+        self.mask_head = self.mask_iou_head = None
         if with_mask:   # Mask R-CNN (BASELINE.json config 4): the mask branch's backward runs first
+            if mask_iou:    # ... and within it the MaskIoU head's, which sits behind the mask head's output
+                self.mask_iou_head = MaskIoUHead(256, self.arena, self.ws, device, torch.Generator().manual_seed(seed + 7919),
+                                                 num_classes=num_classes, rois_per_image=max(1, rois_per_image // 4),
+                                                 weight=mask_iou_weight)
             self.mask_head = FCNMaskHead(256, self.arena, self.ws, device, gen, num_classes=num_classes,
                                          rois_per_image=max(1, rois_per_image // 4), norm=head_norm, gn_groups=gn_groups)
             self.mask_roi_extractor = FPNRoIExtractor([4, 8, 16, 32], pooled=(14, 14), device=device)
@@ -97,6 +112,8 @@ class FasterRCNN(DetectorBase):
         norms = self.bbox_head.norm_layers()
         if with_mask:
             layers = self.mask_head.layers() + layers
+            if self.mask_iou_head is not None:
+                layers = self.mask_iou_head.layers() + layers
             norms = self.mask_head.norm_layers() + norms
         self._finalize_params(layers, norm_layers=norms)
 
@@ -116,6 +133,8 @@ class FasterRCNN(DetectorBase):
             self.dpool.plan(N * self.bbox_head.R)
         if self.with_mask:
             self.mask_head.plan(N)
+            if self.mask_iou_head is not None:
+                self.mask_iou_head.plan(N, g_max)
         self.ws.get()
         self.ws_rpn.get()
         # one flat bf16 buffer (levels are views, finest first): the RoI extractor finalizes P2..P5 with one launch
@@ -157,16 +176,26 @@ class FasterRCNN(DetectorBase):
         pooled = self.roi_extractor.forward(P, rois_s, prepare_gather=self.roi_bwd_gather)
         self.bbox_head.forward(pooled)
         rcnn_loss = self.bbox_head.loss_and_grad()
-        mask_loss = None
+        mask_loss = maskiou_loss = None
+        iou_head = self.mask_iou_head
         if self.with_mask:
             mrois = self.mask_head.select_rois(self.bbox_head)
             self.mask_head.targets(gt_masks)
             mpooled = self.mask_roi_extractor.forward(P, mrois, prepare_gather=self.roi_bwd_gather)
             self.mask_head.forward(mpooled)
             mask_loss = self.mask_head.loss_and_grad()
+            if iou_head is not None:
+                iou_head.targets(self.mask_head, gt_boxes, gt_masks)
+                iou_head.forward(mpooled, self.mask_head.o, self.mask_head.cls)
+                maskiou_loss = iou_head.loss_and_grad()
         # ---- backward ----
         if self.with_mask:
+            # the MaskIoU head's backward completes first; its input gradient joins the mask head's at the RoI features
+            # (the mask channel of its input is a constant: nothing flows into the mask logits)
+            d_iou_in = iou_head.backward() if iou_head is not None else None
             d_mpooled = self.mask_head.backward()
+            if iou_head is not None:
+                M_.maskiou_input_bwd(d_iou_in, d_mpooled)
         d_pooled = self.bbox_head.backward()
         if self.roi_bwd_gather:
             self._join_branch()                                       # dP[l] holds the RPN part
@@ -197,6 +226,8 @@ class FasterRCNN(DetectorBase):
             self._reduce(lo, self.mark_fpn)
             lo = self.mark_fpn
         self._backbone_backward(lo)
+        if iou_head is not None:
+            return rpn_loss, rcnn_loss, mask_loss, maskiou_loss
         if self.with_mask:
             return rpn_loss, rcnn_loss, mask_loss
         return rpn_loss, rcnn_loss
@@ -206,7 +237,9 @@ class FasterRCNN(DetectorBase):
         """Inference: forward, proposals, box head, then softmax / decode / per-class NMS / top-k on the GPU
         (core/evaluation, SURVEY.md section 8f rank 3); nms_method "linear" / "gaussian": Soft-NMS per class. Returns (dets [N,max_per_image,6] = x1,y1,x2,y2,score,class;
         num_dets [N]); with_masks (Mask R-CNN) adds the pasted-back instance masks [N,max_per_image,H,W] u8 in the
-        frame of the network input: mask head on the detected boxes, sigmoid, bilinear resize into the box, threshold."""
+        frame of the network input: mask head on the detected boxes, sigmoid, bilinear resize into the box, threshold. A
+        model with the MaskIoU head (mask_iou) returns a fourth value, the mask scores [N,max_per_image] f32: the
+        detection's score times the IoU the head predicts for its class (0 on padding rows); dets are unchanged."""
         from ..core.evaluation import DetectionPostprocess
         N, _, H, W = image.shape
         g_max = self.planned[3] if self.planned is not None and self.planned[:3] == (N, H, W) else 100
@@ -226,7 +259,6 @@ class FasterRCNN(DetectorBase):
         if not with_masks:
             return dets, num
         assert self.with_mask, "with_masks needs a model built with the mask head"
-        from ..core import mask as M_
         M = dets.shape[1]
         flat = dets.view(N * M, 6)
         drois = torch.empty((N * M, 5), dtype=torch.float32, device=dets.device)
@@ -235,4 +267,8 @@ class FasterRCNN(DetectorBase):
         mpooled = self.mask_roi_extractor.forward(P, drois)
         logits = self.mask_head.forward(mpooled)
         masks = M_.mask_paste(logits, flat, H, W, mask_thresh)
-        return dets, num, masks.view(N, M, H, W)
+        if self.mask_iou_head is None:
+            return dets, num, masks.view(N, M, H, W)
+        pred = self.mask_iou_head.forward(mpooled, logits, flat[:, 5].to(torch.int32))
+        scores = M_.maskiou_score(flat, pred.view(N * M, -1))
+        return dets, num, masks.view(N, M, H, W), scores.view(N, M)

@@ -1,2 +1,3 @@
 """models/mask_heads (/root/reference/README.md:30)."""
 from .fcn_mask_head import FCNMaskHead  # noqa: F401
+from .mask_iou_head import MaskIoUHead  # noqa: F401

@@ -60,6 +60,8 @@ DEFAULTS = {
         "anchor_scales_per_octave": 3,    # ... times this many sizes per octave ...
         "anchor_scale": 4.0,              # ... starting at anchor_scale * stride (ATSS as published: [1.0], 1, 8.0)
         "dpool_offset_fcs": 3,            # FCs of the offset head (1: Deformable-ConvNets' FPN head, 3: DCN v2 / mmdetection)
+        "mask_iou": False,                # mask_rcnn: Mask Scoring R-CNN's MaskIoU head (Huang et al. 2019); segm detections are scored box score x predicted mask IoU
+        "mask_iou_weight": 1.0,           # weight of the MaskIoU head's L2 loss
     },
     "dataset": {
         "type": "synthetic",              # synthetic | coco | voc (ann_file = Annotations directory)

@@ -8,8 +8,9 @@ padded to 1344, weight gradients grouped on a side stream, RPN branch on its own
     python tools/bench_dcn.py --dcn-stages '' --bbox-head 4conv1fc --head-norm gn     # the GN box head on the plain backbone
     python tools/bench_dcn.py --dcn-stages '' --mask 1 --bbox-head 4conv1fc --head-norm gn     # Mask R-CNN, GN in both heads
     python tools/bench_dcn.py --dcn-stages '' --reg-loss giou --reg-loss-weight 10     # GIoU loss on the decoded box in the box head
+    python tools/bench_dcn.py --dcn-stages '' --mask 1 --mask-iou 1     # Mask Scoring R-CNN: the MaskIoU head on the mask branch
 
-Prints one JSON line: {"dcn_stages", "modulated", "groups", "roi_pool", "mask", "img_per_s", "step_ms", "losses"}.
+Prints one JSON line: {"dcn_stages", "modulated", "groups", "roi_pool", "mask", "mask_iou", "img_per_s", "step_ms", "losses"}.
 """
 import argparse
 import json
@@ -33,9 +34,13 @@ def main():
     ap.add_argument("--reg-loss", default="smooth_l1", choices=("smooth_l1", "iou", "giou", "diou"))
     ap.add_argument("--reg-loss-weight", type=float, default=1.0)
     ap.add_argument("--mask", type=int, default=0, help="1 = Mask R-CNN (ground-truth masks: an ellipse in every box, as bench.py)")
+    ap.add_argument("--mask-iou", type=int, default=0, help="1 = Mask Scoring R-CNN's MaskIoU head (needs --mask 1)")
+    ap.add_argument("--mask-iou-weight", type=float, default=1.0)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     args = ap.parse_args()
+    if args.mask_iou and not args.mask:
+        ap.error("--mask-iou 1 needs --mask 1: the MaskIoU head scores the mask head's output")
     import torch
     from bench import BATCH_PER_GPU, IM_H, PAD_W, synth_batch
     from mxdetection_amd.models import FasterRCNN
@@ -44,7 +49,8 @@ def main():
     model = FasterRCNN(device, depth=50, seed=7, dcn_stages=stages, dcn_modulated=bool(args.modulated),
                        dcn_groups=args.groups, roi_pool=args.roi_pool, bbox_head=args.bbox_head,
                        head_norm=args.head_norm, gn_groups=args.gn_groups, with_mask=bool(args.mask),
-                       reg_loss=args.reg_loss, reg_loss_weight=args.reg_loss_weight)
+                       reg_loss=args.reg_loss, reg_loss_weight=args.reg_loss_weight, mask_iou=bool(args.mask_iou),
+                       mask_iou_weight=args.mask_iou_weight)
     model.enable_wgrad_stream()
     model.enable_branch_stream()
     model.enable_grouped_wgrad()
@@ -74,7 +80,7 @@ def main():
     dt = time.perf_counter() - t0
     vals = [float(v) for v in torch.cat(list(losses)).cpu().numpy()]
     print(json.dumps({"dcn_stages": list(stages), "modulated": bool(args.modulated), "groups": args.groups,
-                      "roi_pool": args.roi_pool, "mask": bool(args.mask), "bbox_head": args.bbox_head, "head_norm": args.head_norm,
+                      "roi_pool": args.roi_pool, "mask": bool(args.mask), "mask_iou": bool(args.mask_iou), "bbox_head": args.bbox_head, "head_norm": args.head_norm,
                       "reg_loss": args.reg_loss,
                       "img_per_s": round(BATCH_PER_GPU * args.steps / dt, 2),
                       "step_ms": round(1e3 * dt / args.steps, 3), "losses": vals}), flush=True)

@@ -37,8 +37,11 @@ def main():
     sgts, sdts = [], []          # mask evaluation, in the frame of the network input (both sides rasterised there)
     for k, batch in enumerate(loader):
         if segm:
-            dets, num, masks = model.predict(batch["image"], batch["im_info"], te.score_thresh, te.nms, te.max_per_image,
-                                             with_masks=True, nms_method=te.nms_method, soft_sigma=te.soft_sigma)
+            out = model.predict(batch["image"], batch["im_info"], te.score_thresh, te.nms, te.max_per_image,
+                                with_masks=True, nms_method=te.nms_method, soft_sigma=te.soft_sigma)
+            dets, num, masks = out[:3]
+            # Mask Scoring R-CNN (network.mask_iou): segm detections are ranked by box score x predicted mask IoU
+            mask_scores = out[3].cpu().numpy() if len(out) > 3 else None
         else:
             dets, num = model.predict(batch["image"], batch["im_info"], te.score_thresh, te.nms, te.max_per_image,
                                       nms_method=te.nms_method, soft_sigma=te.soft_sigma)
@@ -53,7 +56,8 @@ def main():
             for n in fresh:
                 e = roidb[ids[n]]
                 for j in range(int(nn[n])):
-                    sdts.append({"image_id": e["id"], "category_id": int(dn[n, j, 5]), "score": float(dn[n, j, 4]), "mask": mk[n, j] > 0})
+                    score = float(dn[n, j, 4] if mask_scores is None else mask_scores[n, j])
+                    sdts.append({"image_id": e["id"], "category_id": int(dn[n, j, 5]), "score": score, "mask": mk[n, j] > 0})
                 for g in range(min(e["boxes"].shape[0], gm.shape[1])):
                     sgts.append({"image_id": e["id"], "category_id": int(e["gt_classes"][g]), "mask": gm[n, g] > 0})
         for n in fresh:

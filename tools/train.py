@@ -68,6 +68,7 @@ def main():
             it += 1
             seen += tr.batch_images * world
             if rank == 0 and tr.log_period and it % tr.log_period == 0:
+                # rpn (cls, box), rcnn (cls, box), then the mask loss (mask_rcnn) and the MaskIoU loss (network.mask_iou)
                 vals = [float(v) for v in torch.cat(list(losses)).cpu().numpy()]
                 dt = time.perf_counter() - t0
                 print("epoch %d iter %d lr %.5f losses %s  %.1f img/s" % (epoch, it, lr, ["%.4f" % v for v in vals], seen / dt),
