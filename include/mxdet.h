@@ -240,6 +240,44 @@ int mxdet_proposal_target(const float* rois, const int32_t* num_rois, int32_t ro
                           int32_t* num_fg, mxdet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * core/bbox -- online hard example mining for the box head (Shrivastava et al., CVPR 2016).
+ * An image's pool of P rows is a proposal-target output with rois_per_image = P, fg_fraction = 1: every candidate,
+ * foreground first, then padding (label -1). A read-only forward of the box head over the N*P pool rows is scored, the
+ * candidates are ordered by score, deduplicated by NMS, and the first R survivors become the head's training rois.
+ * All entries: host argument checks before any launch, no allocation, no host synchronisation, no float atomics;
+ * capturable, and a pure function of the inputs. P <= 16384 + 1024 and R >= 1, else MXDET_ESHAPE.
+ *
+ * mxdet_ohem_roi_score: score[r] (f32 [R]) = cls_r + reg_r in one fp32 add, where cls_r / reg_r are loss_out[0] / [1] of
+ * mxdet_rcnn_loss (kind = -1: bbox_targets, bbox_weights, sigma are read; rois, matched_gt, gt_boxes may be NULL) or of
+ * mxdet_rcnn_loss_iou (kind = MXDET_IOU_LOSS_*: rois, matched_gt, gt_boxes, N, G_max, stds, reg_weight are read;
+ * bbox_targets, bbox_weights may be NULL) called on row r alone with R = 1, norm = 1, loss_scale = 1 -- the same device
+ * code, the same bits. Rows with labels[r] < 0 get -1.0f. Writes no gradients. One wave per row. */
+int mxdet_ohem_roi_score(const void* cls_logits, const void* bbox_pred, int32_t dtype, int32_t ld_cls, int32_t ld_reg,
+                         const int32_t* labels, const float* bbox_targets, const float* bbox_weights, const float* rois,
+                         const int32_t* matched_gt, const float* gt_boxes, int32_t N, int32_t G_max, int64_t R,
+                         int32_t num_classes, int32_t reg_dim, int32_t kind, float sigma, float std_x, float std_y,
+                         float std_w, float std_h, float reg_weight, float* score, mxdet_stream_t stream);
+/* mxdet_ohem_select: score / labels [N,P], rois [N,P,5]. Candidates of image n: rows with label >= 0. Order: the
+ * score's IEEE bit pattern as uint32 descending, then pool slot ascending (for scores >= 0 the numeric order; a NaN comes
+ * first; the order is total). Dedup: greedy NMS over that order on rois[:, 1:5] -- a kept box suppresses a later one when
+ * mxdet_iou ("+1" convention) > nms_thresh, as mxdet_nms_batched; nms_thresh >= 1 launches no NMS; nms_thresh < 1
+ * needs P <= 4096 (the keep scan's limit), else MXDET_ESHAPE. The first min(R, kept) kept candidates are chosen.
+ * sel [N,R] int32: the chosen pool slots, foreground (label > 0) in ascending slot, then background in ascending slot,
+ * then -1. num_sel [N]: chosen; num_fg [N]: chosen foreground. */
+size_t mxdet_ohem_select_workspace_bytes(int32_t N, int32_t P);
+int mxdet_ohem_select(const float* score, const int32_t* labels, const float* rois, int32_t N, int32_t P, int32_t R,
+                      float nms_thresh, int32_t* sel, int32_t* num_sel, int32_t* num_fg, void* workspace,
+                      size_t workspace_bytes, mxdet_stream_t stream);
+/* mxdet_ohem_gather: output row (n, s) = pool row (n, sel[n, s]) in mxdet_proposal_target's layout (out_rois [N,R,5],
+ * labels [N,R], bbox_targets / bbox_weights [N,R,reg_dim], matched_gt [N,R]); sel < 0: the padding row of
+ * mxdet_proposal_target (roi (n,0,0,0,0), label -1, matched -1, zero targets and weights). The four target / weight
+ * pointers (16-byte aligned, reg_dim % 4 == 0) may be NULL together: the IoU-family losses do not read them. */
+int mxdet_ohem_gather(const int32_t* sel, const float* pool_rois, const int32_t* pool_labels,
+                      const int32_t* pool_matched_gt, const float* pool_bbox_targets, const float* pool_bbox_weights,
+                      int32_t N, int32_t P, int32_t R, int32_t reg_dim, float* out_rois, int32_t* labels,
+                      float* bbox_targets, float* bbox_weights, int32_t* matched_gt, mxdet_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * roi_extractors (README.md:32) -- FPN level map + RoIAlign. MXNet role: contrib.ROIAlign
  * (Detectron aligned=False semantics), one call covering all pyramid levels.
  * feats[l]: bf16 [N,H[l],W[l],C] channels-last; rois[R,5]; levels[R] int32 in [lvl_min, lvl_min+L).

@@ -25,6 +25,8 @@ PER_FILE = {
     "mask.hip": ["-ffp-contract=off"],
     # the MaskIoU target / loss / score are compared bit for bit with a numpy-float32 restatement
     "mask_iou.hip": EXACT,
+    # the OHEM score is the box-head loss entries' per-roi loss bit for bit (one definition, loss_elem.h)
+    "ohem.hip": EXACT,
     "wgrad.hip": [],
     "dense_misc.hip": [],
     # backward's recomputed ReLU mask (y == NULL) must reproduce the bits forward stored: no FMA contraction

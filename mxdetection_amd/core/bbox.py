@@ -54,3 +54,67 @@ def sample_rois(rois, num_rois, gt_boxes, rois_per_image=512, fg_fraction=0.25, 
                                     seed, step, ptr(step_dev), image_offset, ptr(out_rois), ptr(labels), ptr(tgt), ptr(wgt),
                                     ptr(matched), ptr(num_fg), stream_ptr()), "proposal_target")
     return out_rois, labels, tgt, wgt, matched, num_fg
+
+
+# ---- online hard example mining for the box head (include/mxdet.h) ----
+OHEM_MAX_POOL = 16384 + 1024
+OHEM_NMS_MAX_POOL = 4096
+
+
+def check_ohem(ohem_nms):
+    """The OHEM option of FasterRCNN, checked before anything is allocated: ohem_nms in (0, 1]; 1 = no dedup."""
+    v = ohem_nms
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 < float(v) <= 1.0:
+        raise ValueError("ohem_nms must be a number in (0, 1] (got %r)" % (v,))
+
+
+def ohem_pool_size(rois_stride, g_max):
+    """Rows of an image's candidate pool: every proposal and every ground-truth box, rounded up to a multiple of 64 (the
+    box head's fc1 then stays on its split-K route)."""
+    return (rois_stride + g_max + 63) // 64 * 64
+
+
+def ohem_select_workspace(N, P, device):
+    lib = _lib.load()
+    return torch.empty((max(lib.mxdet_ohem_select_workspace_bytes(N, P), 256),), dtype=torch.uint8, device=device)
+
+
+def ohem_select(score, labels, rois, rois_per_image, nms_thresh=0.7, workspace=None, sel=None, num_sel=None, num_fg=None):
+    """score / labels [N,P], rois [N,P,5] -> (sel [N,R] i32 pool slot or -1, num_sel [N] i32, num_fg [N] i32): the R
+    highest-score candidates (label >= 0) that survive NMS at nms_thresh (>= 1: none), foreground first."""
+    lib = _lib.load()
+    _f32c(score), _f32c(rois)
+    N, P = labels.shape
+    R = rois_per_image
+    dev = score.device
+    if workspace is None:
+        workspace = ohem_select_workspace(N, P, dev)
+    if sel is None:
+        sel = torch.empty((N, R), dtype=torch.int32, device=dev)
+    if num_sel is None:
+        num_sel = torch.empty((N,), dtype=torch.int32, device=dev)
+    if num_fg is None:
+        num_fg = torch.empty((N,), dtype=torch.int32, device=dev)
+    check(lib.mxdet_ohem_select(ptr(score), ptr(labels), ptr(rois), N, P, R, nms_thresh, ptr(sel), ptr(num_sel), ptr(num_fg),
+                                ptr(workspace), workspace.numel(), stream_ptr()), "ohem_select")
+    return sel, num_sel, num_fg
+
+
+def ohem_gather(sel, pool_rois, pool_labels, pool_matched, pool_tgt=None, pool_wgt=None, out=None):
+    """Rows sel [N,R] of the pool (rois [N,P,5], labels / matched [N,P], targets / weights [N,P,D] or both None) in
+    sample_rois' layout: (rois [N,R,5], labels [N,R], bbox_targets, bbox_weights [N,R,D] or None, matched_gt [N,R]);
+    sel < 0 gives sample_rois' padding row. out: those five, preallocated."""
+    lib = _lib.load()
+    N, R = sel.shape
+    P = pool_labels.shape[1]
+    dev = sel.device
+    D = 0 if pool_tgt is None else pool_tgt.shape[2]
+    if out is None:
+        out = (torch.empty((N, R, 5), dtype=torch.float32, device=dev), torch.empty((N, R), dtype=torch.int32, device=dev),
+               None if pool_tgt is None else torch.empty((N, R, D), dtype=torch.float32, device=dev),
+               None if pool_tgt is None else torch.empty((N, R, D), dtype=torch.float32, device=dev),
+               torch.empty((N, R), dtype=torch.int32, device=dev))
+    o_rois, o_lab, o_tgt, o_wgt, o_m = out
+    check(lib.mxdet_ohem_gather(ptr(sel), ptr(pool_rois), ptr(pool_labels), ptr(pool_matched), ptr(pool_tgt), ptr(pool_wgt), N, P,
+                                R, D, ptr(o_rois), ptr(o_lab), ptr(o_tgt), ptr(o_wgt), ptr(o_m), stream_ptr()), "ohem_gather")
+    return out

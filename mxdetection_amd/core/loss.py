@@ -275,3 +275,25 @@ def retina_loss_level_dfl(cls, reg, A, C, cls_labels, anchors, matched_gt, gt_bo
                                           IOU_LOSS_KINDS[kind], reg_max, stride, reg_weight, dfl_weight, ptr(num_fg),
                                           loss_scale, ptr(grad_cls), ptr(grad_reg), ptr(partial), stream_ptr()),
           "retina_loss_level_dfl")
+
+
+# ---- online hard example mining for the box head (include/mxdet.h) ----
+def ohem_roi_score(cls_logits, bbox_pred, labels, num_classes, reg_dim, ld_cls, ld_reg, reg_loss="smooth_l1", bbox_targets=None,
+                   bbox_weights=None, sigma=1.0, rois=None, matched_gt=None, gt_boxes=None, stds=(0.1, 0.1, 0.2, 0.2),
+                   reg_weight=1.0, score=None):
+    """The per-roi loss rcnn_loss (reg_loss 'smooth_l1': bbox_targets / bbox_weights / sigma) or rcnn_loss_iou (an IoU kind:
+    rois / matched_gt / gt_boxes / stds / reg_weight) reports for each row alone, cls + reg, as f32 [R]; -1 for label < 0.
+    No gradients are written."""
+    lib = _lib.load()
+    if reg_loss not in REG_LOSSES:
+        raise ValueError("reg_loss must be one of %s (got %r)" % (", ".join(REG_LOSSES), reg_loss))
+    R = labels.numel()
+    if score is None:
+        score = torch.empty((R,), dtype=torch.float32, device=labels.device)
+    kind = -1 if reg_loss == "smooth_l1" else IOU_LOSS_KINDS[reg_loss]
+    N, G = (gt_boxes.shape[0], gt_boxes.shape[1]) if gt_boxes is not None else (0, 0)
+    check(lib.mxdet_ohem_roi_score(ptr(cls_logits), ptr(bbox_pred), _DT[cls_logits.dtype], ld_cls, ld_reg, ptr(labels),
+                                   ptr(bbox_targets), ptr(bbox_weights), ptr(rois), ptr(matched_gt), ptr(gt_boxes), N, G, R,
+                                   num_classes, reg_dim, kind, sigma, stds[0], stds[1], stds[2], stds[3], reg_weight, ptr(score),
+                                   stream_ptr()), "ohem_roi_score")
+    return score

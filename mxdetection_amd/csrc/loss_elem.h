@@ -1,7 +1,8 @@
-// loss_elem.h -- the device pieces that more than one loss kernel uses (losses.hip, retina_loss.hip): the fixed-order block
-// sum and its partial-sum epilogue, the sigmoid / softplus helpers, the focal and quality class elements with their
-// functors, the IoU-family box element, and the entries' small host predicates. Float32, no FMA contraction (both files
-// are built with -ffp-contract=off): one definition each, so "same code, same bits" holds by construction.
+// loss_elem.h -- the device pieces that more than one loss kernel uses (losses.hip, retina_loss.hip, ohem.hip): the
+// fixed-order block sum and its partial-sum epilogue, the sigmoid / softplus helpers, the focal and quality class elements
+// with their functors, the IoU-family box element, the box head's per-roi walks, and the entries' small host predicates.
+// Float32, no FMA contraction (the three files are built with -ffp-contract=off): one definition each, so "same code, same
+// bits" holds by construction.
 #pragma once
 #include "common.h"
 #include "dist_box.h"
@@ -295,6 +296,104 @@ __device__ __forceinline__ float dist_box_quad(const void* x, long long off, int
       store_from_f32(gx, off + k, dtype, (gb * (p * ((float)k - E)) + gd * (p - t)) * gscale);
     }
   return L;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The box head's per-roi walks, one wave per roi (rcnn_loss_kernel, rcnn_loss_iou_kernel in losses.hip; ohem_score_kernel
+// in ohem.hip). kGrad = false evaluates the same loss and writes nothing: the gradient is no operand of the loss, so the
+// two instantiations return the same bits.
+//
+// softmax CE of roi r (ignore label -1); kGrad: writes columns [0, num_classes) of the grad_cls row. Every lane returns
+// the row's loss (fixed xor tree).
+template <bool kGrad>
+__device__ __forceinline__ float rcnn_softmax_ce(const void* __restrict__ cls, int dtype, int ld_cls, long long r, int lab,
+                                                 int lane, int num_classes, float norm, float loss_scale,
+                                                 void* __restrict__ gcls) {
+  float mx = -3.0e38f;
+  for (int c = lane; c < num_classes; c += 64) {
+    float z = load_as_f32(cls, r * ld_cls + c, dtype);
+    mx = z > mx ? z : mx;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    float o = __shfl_xor(mx, off);
+    mx = o > mx ? o : mx;
+  }
+  float se = 0.0f;
+  for (int c = lane; c < num_classes; c += 64)
+    se += mxdet_expf(load_as_f32(cls, r * ld_cls + c, dtype) - mx);
+  for (int off = 32; off > 0; off >>= 1) se += __shfl_xor(se, off);
+  float lse = mxdet_logf(se);
+  float lcls = 0.0f;
+  for (int c = lane; c < num_classes; c += 64) {
+    float z = load_as_f32(cls, r * ld_cls + c, dtype);
+    float g = 0.0f;
+    if (lab >= 0) {
+      if (kGrad) {
+        float p = mxdet_expf(z - mx) / se;
+        g = (p - (c == lab ? 1.0f : 0.0f)) * norm * loss_scale;
+      }
+      if (c == lab) lcls = -(z - mx - lse);
+    }
+    if (kGrad) store_from_f32(gcls, r * ld_cls + c, dtype, g);
+  }
+  for (int off = 32; off > 0; off >>= 1) lcls += __shfl_xor(lcls, off);
+  return lcls;
+}
+
+// smooth-L1 of roi r's reg_dim columns against its targets / weights; kGrad: writes columns [0, reg_dim) of the grad_reg
+// row. Every lane returns the row's loss.
+template <bool kGrad>
+__device__ __forceinline__ float rcnn_reg_smooth_l1(const void* __restrict__ reg, int dtype, int ld_reg, long long r, int lab,
+                                                    int lane, const float* __restrict__ tgt, const float* __restrict__ wgt,
+                                                    int reg_dim, float sigma2, float norm, float loss_scale,
+                                                    void* __restrict__ greg) {
+  float lreg = 0.0f;
+  for (int c = lane; c < reg_dim; c += 64) {
+    float w = wgt[r * reg_dim + c];
+    float g = 0.0f;
+    if (w != 0.0f && lab > 0) {
+      float d = (load_as_f32(reg, r * ld_reg + c, dtype) - tgt[r * reg_dim + c]) * w;
+      lreg += mxdet_smooth_l1(d, sigma2);
+      if (kGrad) g = mxdet_smooth_l1_grad(d, sigma2) * w * norm * loss_scale;
+    }
+    if (kGrad) store_from_f32(greg, r * ld_reg + c, dtype, g);
+  }
+  // fixed xor tree: every lane ends with the same value
+  for (int off = 32; off > 0; off >>= 1) lreg += __shfl_xor(lreg, off);
+  return lreg;
+}
+
+// The IoU-family term of roi r: every lane evaluates the roi's one box (wave-uniform); kGrad: the lanes share the row's
+// reg_dim gradient columns. Returns reg_weight * L (0 for a roi that regresses nothing).
+template <bool kGrad>
+__device__ __forceinline__ float rcnn_reg_iou(const void* __restrict__ reg, int dtype, int ld_reg, long long r, int lab, int lane,
+                                              const float* __restrict__ rois, const int32_t* __restrict__ matched,
+                                              const float* __restrict__ gt, int N, int G_max, int num_classes, int reg_dim,
+                                              int kind, BoxStds sd, float reg_weight, float norm, float loss_scale,
+                                              void* __restrict__ greg) {
+  float lreg = 0.0f, gd[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  int first = -4;                                       // first column of the label's four deltas; none for label <= 0
+  if (lab > 0 && lab < num_classes) {
+    const float* ro = rois + r * 5;
+    const int img = (int)ro[0], m = matched[r];
+    if (img >= 0 && img < N && m >= 0 && m < G_max) {   // an index outside gt_boxes: the roi regresses nothing
+      first = 4 * lab;
+      float d[4];
+      load_deltas4(reg, r * ld_reg + first, dtype, d);
+      const float4 g = load_f4_a4(gt + ((long long)img * G_max + m) * 5);
+      lreg = reg_weight * box_iou_loss_elem(make_float4(ro[1], ro[2], ro[3], ro[4]), g, d, sd, kind, gd);
+    }
+  }
+  if (kGrad) {
+    const float gs = reg_weight * norm * loss_scale;
+    for (int c = lane; c < reg_dim; c += 64) {
+      const int k = c - first;
+      float gv = 0.0f;
+      if (k >= 0 && k < 4) gv = (k == 0 ? gd[0] : k == 1 ? gd[1] : k == 2 ? gd[2] : gd[3]) * gs;
+      store_from_f32(greg, r * ld_reg + c, dtype, gv);
+    }
+  }
+  return lreg;
 }
 
 // ---------------------------------------------------------------------------------------------

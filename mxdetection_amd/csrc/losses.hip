@@ -129,40 +129,8 @@ rpn_loss_kernel(const uint16_t* __restrict__ head, int N, int H, int W, int A, i
 }
 
 // ---------------------------------------------------------------------------------------------
-// softmax CE of roi r by one wave (ignore label -1); writes columns [0, num_classes) of the grad_cls row; every lane
-// returns the row's loss (fixed xor tree). Shared by rcnn_loss_kernel and rcnn_loss_iou_kernel: same code, same bits.
-__device__ __forceinline__ float rcnn_softmax_ce(const void* __restrict__ cls, int dtype, int ld_cls, long long r, int lab,
-                                                 int lane, int num_classes, float norm, float loss_scale,
-                                                 void* __restrict__ gcls) {
-  float mx = -3.0e38f;
-  for (int c = lane; c < num_classes; c += 64) {
-    float z = load_as_f32(cls, r * ld_cls + c, dtype);
-    mx = z > mx ? z : mx;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    float o = __shfl_xor(mx, off);
-    mx = o > mx ? o : mx;
-  }
-  float se = 0.0f;
-  for (int c = lane; c < num_classes; c += 64)
-    se += mxdet_expf(load_as_f32(cls, r * ld_cls + c, dtype) - mx);
-  for (int off = 32; off > 0; off >>= 1) se += __shfl_xor(se, off);
-  float lse = mxdet_logf(se);
-  float lcls = 0.0f;
-  for (int c = lane; c < num_classes; c += 64) {
-    float z = load_as_f32(cls, r * ld_cls + c, dtype);
-    float g = 0.0f;
-    if (lab >= 0) {
-      float p = mxdet_expf(z - mx) / se;
-      g = (p - (c == lab ? 1.0f : 0.0f)) * norm * loss_scale;
-      if (c == lab) lcls = -(z - mx - lse);
-    }
-    store_from_f32(gcls, r * ld_cls + c, dtype, g);
-  }
-  for (int off = 32; off > 0; off >>= 1) lcls += __shfl_xor(lcls, off);
-  return lcls;
-}
-
+// (rcnn_softmax_ce / rcnn_reg_smooth_l1 / rcnn_reg_iou, the per-roi walks of the two kernels below, live in loss_elem.h:
+// ohem.hip scores rows with the same code.)
 // Box-head losses: one wave per roi.
 __global__ void __launch_bounds__(256)
 rcnn_loss_kernel(const void* __restrict__ cls, const void* __restrict__ reg, int dtype, int ld_cls,
@@ -174,21 +142,8 @@ rcnn_loss_kernel(const void* __restrict__ cls, const void* __restrict__ reg, int
   if (r >= R) return;
   const int lane = lane_id();
   int lab = labels[r];
-  const float lcls = rcnn_softmax_ce(cls, dtype, ld_cls, r, lab, lane, num_classes, norm, loss_scale, gcls);
-  // smooth-L1
-  float lreg = 0.0f;
-  for (int c = lane; c < reg_dim; c += 64) {
-    float w = wgt[r * reg_dim + c];
-    float g = 0.0f;
-    if (w != 0.0f && lab > 0) {
-      float d = (load_as_f32(reg, r * ld_reg + c, dtype) - tgt[r * reg_dim + c]) * w;
-      lreg += mxdet_smooth_l1(d, sigma2);
-      g = mxdet_smooth_l1_grad(d, sigma2) * w * norm * loss_scale;
-    }
-    store_from_f32(greg, r * ld_reg + c, dtype, g);
-  }
-  // fixed xor tree: every lane ends with the same value
-  for (int off = 32; off > 0; off >>= 1) lreg += __shfl_xor(lreg, off);
+  const float lcls = rcnn_softmax_ce<true>(cls, dtype, ld_cls, r, lab, lane, num_classes, norm, loss_scale, gcls);
+  const float lreg = rcnn_reg_smooth_l1<true>(reg, dtype, ld_reg, r, lab, lane, tgt, wgt, reg_dim, sigma2, norm, loss_scale, greg);
   if (lane == 0) {
     partial[2 * r + 0] = lcls * norm;
     partial[2 * r + 1] = lreg * norm;
@@ -222,28 +177,9 @@ rcnn_loss_iou_kernel(const void* __restrict__ cls, const void* __restrict__ reg,
   if (r >= R) return;
   const int lane = lane_id();
   int lab = labels[r];
-  const float lcls = rcnn_softmax_ce(cls, dtype, ld_cls, r, lab, lane, num_classes, norm, loss_scale, gcls);
-  // every lane evaluates the roi's one box (wave-uniform); the lanes share the row's reg_dim gradient columns
-  float lreg = 0.0f, gd[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  int first = -4;                                       // first column of the label's four deltas; none for label <= 0
-  if (lab > 0 && lab < num_classes) {
-    const float* ro = rois + r * 5;
-    const int img = (int)ro[0], m = matched[r];
-    if (img >= 0 && img < N && m >= 0 && m < G_max) {   // an index outside gt_boxes: the roi regresses nothing
-      first = 4 * lab;
-      float d[4];
-      load_deltas4(reg, r * ld_reg + first, dtype, d);
-      const float4 g = load_f4_a4(gt + ((long long)img * G_max + m) * 5);
-      lreg = reg_weight * box_iou_loss_elem(make_float4(ro[1], ro[2], ro[3], ro[4]), g, d, sd, kind, gd);
-    }
-  }
-  const float gs = reg_weight * norm * loss_scale;
-  for (int c = lane; c < reg_dim; c += 64) {
-    const int k = c - first;
-    float gv = 0.0f;
-    if (k >= 0 && k < 4) gv = (k == 0 ? gd[0] : k == 1 ? gd[1] : k == 2 ? gd[2] : gd[3]) * gs;
-    store_from_f32(greg, r * ld_reg + c, dtype, gv);
-  }
+  const float lcls = rcnn_softmax_ce<true>(cls, dtype, ld_cls, r, lab, lane, num_classes, norm, loss_scale, gcls);
+  const float lreg = rcnn_reg_iou<true>(reg, dtype, ld_reg, r, lab, lane, rois, matched, gt, N, G_max, num_classes, reg_dim, kind, sd,
+                                        reg_weight, norm, loss_scale, greg);
   if (lane == 0) {
     partial[2 * r + 0] = lcls * norm;
     partial[2 * r + 1] = lreg * norm;

@@ -21,10 +21,15 @@ from ..utils.layers import ConvLayer, GroupNormLayer, cached_buf
 class BBoxHead:
     def __init__(self, in_features, arena, ws, device, gen, num_classes=81, fc_dim=1024, rois_per_image=512,
                  fg_fraction=0.25, fg_thresh=0.5, bg_hi=0.5, bg_lo=0.0, stds=(0.1, 0.1, 0.2, 0.2), sigma=1.0,
-                 seed=99, reg_loss="smooth_l1", reg_loss_weight=1.0):
+                 seed=99, reg_loss="smooth_l1", reg_loss_weight=1.0, ohem=False, ohem_nms=0.7):
         """reg_loss: 'smooth_l1' on the encoded deltas (core.loss.rcnn_loss), or 'iou' / 'giou' / 'diou' on the decoded
-        box times reg_loss_weight (core.loss.rcnn_loss_iou; the head still predicts deltas, inference is the same)."""
+        box times reg_loss_weight (core.loss.rcnn_loss_iou; the head still predicts deltas, inference is the same).
+        ohem / ohem_nms: online hard example mining (sample): the training RoIs are the rois_per_image highest-loss
+        candidates of a read-only pass, deduplicated by NMS at ohem_nms (1 = none); fg_fraction is not used."""
         L_.check_reg_loss(reg_loss, reg_loss_weight)
+        B_.check_ohem(ohem_nms)
+        self.ohem, self.ohem_nms = bool(ohem), float(ohem_nms)
+        self.ohem_extractor = None        # the detector's box RoI extractor (set by the detector that owns both)
         self.reg_loss, self.reg_loss_weight = reg_loss, float(reg_loss_weight)
         kw = dict(arena=arena, ws=ws, device=device, gen=gen)
         self.nc = num_classes
@@ -66,12 +71,52 @@ class BBoxHead:
         self.loss = torch.zeros((2,), dtype=torch.float32, device=self.device)
         self.loss_ws = L_.loss_workspace(R, self.device)
 
-    def sample(self, rois, num_rois, gt_boxes, step, image_offset, step_dev=None):
+    def sample(self, rois, num_rois, gt_boxes, step, image_offset, step_dev=None, feats=None):
         """proposal-target: returns rois [N*R,5] and keeps labels / targets / weights (and the ground truth, which the
-        IoU-family losses read on the device) for the loss."""
+        IoU-family losses read on the device) for the loss. feats (the pyramid) is read by the OHEM route only."""
+        if self.ohem:
+            return self._sample_ohem(rois, num_rois, gt_boxes, step, image_offset, step_dev, feats)
         out = B_.sample_rois(rois, num_rois, gt_boxes, self.R, self.fg_fraction, self.fg_thresh, self.bg_hi, self.bg_lo,
                              self.nc, False, (0.0, 0.0, 0.0, 0.0), self.stds, self.seed, step, image_offset, step_dev)
         self.rois, self.labels, self.tgt, self.wgt, self.matched, self.num_fg = out
+        self.gt_boxes = gt_boxes
+        return self.rois.view(-1, 5)
+
+    def _sample_ohem(self, rois, num_rois, gt_boxes, step, image_offset, step_dev, feats):
+        """Online hard example mining (Shrivastava et al. 2016), all on the device:
+          1. the pool: proposal-target with rois_per_image = P and fg_fraction = 1 returns EVERY candidate of an image (all
+             foreground, then all background, ascending, then padding) -- the Philox keys decide nothing;
+          2. a read-only pass of the RoI extractor and of this head over the N * P pool rows, in buffers of that row count
+             (nothing of it is read by backward: the training pass runs forward again on the chosen rows);
+          3. the per-roi loss, the order by it, NMS dedup, the first R survivors (core.bbox.ohem_select);
+          4. their rows, foreground first (FCNMaskHead.select_rois relies on it), in the attributes sample() always fills.
+        The pool (pool_*), ohem_score [N,P] and ohem_sel [N,R] stay for inspection."""
+        if feats is None or self.ohem_extractor is None:
+            raise ValueError("ohem: sample() needs the pyramid (feats) and the box RoI extractor (ohem_extractor)")
+        N, S, G = rois.shape[0], rois.shape[1], gt_boxes.shape[1]
+        P = B_.ohem_pool_size(S, G)
+        pool = B_.sample_rois(rois, num_rois, gt_boxes, P, 1.0, self.fg_thresh, self.bg_hi, self.bg_lo, self.nc, False,
+                              (0.0, 0.0, 0.0, 0.0), self.stds, self.seed, step, image_offset, step_dev)
+        self.pool_rois, self.pool_labels, self.pool_tgt, self.pool_wgt, self.pool_matched, self.pool_num_fg = pool
+        pooled = self.ohem_extractor.forward(feats, self.pool_rois.view(-1, 5), prepare_gather=False)
+        o2 = self.forward(pooled).view(N * P, self.ld)
+        iou = self.reg_loss != "smooth_l1"
+        score = L_.ohem_roi_score(o2, o2[:, self.nc:], self.pool_labels, self.nc, self.reg_dim, self.ld, self.ld, self.reg_loss,
+                                  bbox_targets=self.pool_tgt, bbox_weights=self.pool_wgt, sigma=self.sigma,
+                                  rois=self.pool_rois, matched_gt=self.pool_matched, gt_boxes=gt_boxes, stds=self.stds,
+                                  reg_weight=self.reg_loss_weight, score=self._buf("ohem_score", (N * P,), torch.float32))
+        self.ohem_score = score.view(N, P)
+        ws = self.bufs.get(("ohem_ws", N, P))
+        if ws is None:
+            ws = self.bufs[("ohem_ws", N, P)] = B_.ohem_select_workspace(N, P, self.device)
+        self.ohem_sel, self.ohem_num_sel, self.num_fg = B_.ohem_select(
+            self.ohem_score, self.pool_labels, self.pool_rois, self.R, self.ohem_nms, workspace=ws,
+            sel=self._buf("ohem_sel", (N, self.R), torch.int32), num_sel=self._buf("ohem_num_sel", (N,), torch.int32),
+            num_fg=self._buf("ohem_num_fg", (N,), torch.int32))
+        # the IoU-family losses read neither targets nor weights: their 2 x 4 * num_classes floats per row stay in the pool
+        self.rois, self.labels, self.tgt, self.wgt, self.matched = B_.ohem_gather(
+            self.ohem_sel, self.pool_rois, self.pool_labels, self.pool_matched, None if iou else self.pool_tgt,
+            None if iou else self.pool_wgt)
         self.gt_boxes = gt_boxes
         return self.rois.view(-1, 5)
 

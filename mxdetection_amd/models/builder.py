@@ -26,8 +26,12 @@ def build_detector(cfg, device="cuda"):
         model = FasterRCNN(device, depth=net.backbone_depth, num_classes=net.num_classes, seed=net.seed,
                            rois_per_image=tr.batch_rois, pre_nms_top_n=tr.rpn_pre_nms_top_n,
                            post_nms_top_n=tr.rpn_post_nms_top_n, with_mask=(net.type == "mask_rcnn"), **dcn, **dpool, **heads,
-                           **reg, mask_iou=bool(net.mask_iou), mask_iou_weight=net.mask_iou_weight)
+                           **reg, mask_iou=bool(net.mask_iou), mask_iou_weight=net.mask_iou_weight, ohem=bool(net.ohem),
+                           ohem_nms=net.ohem_nms)
     elif net.type == "retinanet":
+        if net.ohem:
+            raise ValueError("network.ohem = %r: retinanet has no box head to mine RoIs for (OHEM is a faster_rcnn / mask_rcnn "
+                             "option)" % (net.ohem,))
         if net.mask_iou:
             raise ValueError("network.mask_iou = %r: retinanet has no mask branch to score (the MaskIoU head is a mask_rcnn "
                              "option)" % (net.mask_iou,))

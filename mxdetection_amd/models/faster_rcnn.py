@@ -8,6 +8,7 @@ itself is not declared anywhere in the reference tree; thi
 import torch
 
 from ..core import mask as M_
+from ..core.bbox import check_ohem
 from ..core.loss import check_reg_loss
 from .backbones import ResNet
 from .bbox_heads import BBoxHead, ConvFCBBoxHead
@@ -39,7 +40,7 @@ class FasterRCNN(DetectorBase):
                  pre_nms_top_n=2000, post_nms_top_n=2000, with_mask=False, dcn_stages=(), dcn_modulated=True,
                  dcn_groups=1, roi_pool="roi_align", dpool_trans_std=0.1, dpool_sample_per_part=4, dpool_offset_fcs=3,
                  bbox_head="2fc", head_norm="none", gn_groups=32, reg_loss="smooth_l1", reg_loss_weight=1.0,
-                 mask_iou=False, mask_iou_weight=1.0):
+                 mask_iou=False, mask_iou_weight=1.0, ohem=False, ohem_nms=0.7):
         """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
         roi_pool: the box branch's RoI pooling -- 'roi_align', or deformable RoI pooling with its offset head, 'dpool'
         (v1) / 'mdpool' (v2, modulated) (roi_extractors.DeformRoIExtractor, options dpool_*). The mask branch keeps its
@@ -52,7 +53,10 @@ class FasterRCNN(DetectorBase):
         mask_iou / mask_iou_weight: Mask Scoring R-CNN -- a MaskIoU head on the mask branch (mask_heads.MaskIoUHead) whose
         L2 loss, times mask_iou_weight, is the step's fourth loss; predict(with_masks=True) then also returns the mask
         scores. Needs with_mask. The head draws its initial weights from a generator of its own, so every other parameter
-        starts exactly as in the model without it."""
+        starts exactly as in the model without it.
+        ohem / ohem_nms: online hard example mining (Shrivastava et al. 2016) -- the box head trains on the rois_per_image
+        highest-loss RoIs of a read-only pass over every candidate of the image (proposals and ground truth), deduplicated
+        by NMS at IoU ohem_nms in (0, 1] (1 = none), with no fg:bg quota (bbox_heads.BBoxHead.sample). It adds no parameter."""
         check_head_options(bbox_head, head_norm, gn_groups, with_mask)
         if mask_iou and not with_mask:
             raise ValueError("mask_iou needs the mask branch (with_mask=True): the MaskIoU head scores the mask head's output")
@@ -60,6 +64,9 @@ class FasterRCNN(DetectorBase):
                              and 0.0 < float(mask_iou_weight) < float("inf")):
             raise ValueError("mask_iou_weight must be a positive finite number (got %r)" % (mask_iou_weight,))
         check_reg_loss(reg_loss, reg_loss_weight)
+        if not isinstance(ohem, (bool, int)):
+            raise ValueError("ohem must be a bool (got %r)" % (ohem,))
+        check_ohem(ohem_nms)
         if roi_pool not in ("roi_align", "dpool", "mdpool"):
             raise ValueError("roi_pool must be 'roi_align', 'dpool' or 'mdpool' (got %r)" % (roi_pool,))
         self.roi_pool = roi_pool
@@ -84,11 +91,11 @@ class FasterRCNN(DetectorBase):
         if bbox_head == "4conv1fc":
             self.bbox_head = ConvFCBBoxHead(7 * 7 * 256, self.arena, self.ws, device, gen, norm=head_norm, gn_groups=gn_groups,
                                             num_classes=num_classes, rois_per_image=rois_per_image, seed=rpn_seed,
-                                            reg_loss=reg_loss, reg_loss_weight=reg_loss_weight)
+                                            reg_loss=reg_loss, reg_loss_weight=reg_loss_weight, ohem=ohem, ohem_nms=ohem_nms)
         else:
             self.bbox_head = BBoxHead(7 * 7 * 256, self.arena, self.ws, device, gen, num_classes=num_classes,
                                       rois_per_image=rois_per_image, seed=rpn_seed, reg_loss=reg_loss,
-                                      reg_loss_weight=reg_loss_weight)
+                                      reg_loss_weight=reg_loss_weight, ohem=ohem, ohem_nms=ohem_nms)
         self.dpool = None
         if roi_pool != "roi_align":
             # the offset head belongs to the head bucket: its backward runs in the slot of the RoI extractor's
@@ -107,6 +114,7 @@ class FasterRCNN(DetectorBase):
         self.backbone = ResNet(depth, self.arena, self.ws, device, gen, dcn_stages=dcn_stages,
                                dcn_modulated=dcn_modulated, dcn_groups=dcn_groups)
         self.roi_extractor = self.dpool if self.dpool is not None else FPNRoIExtractor(self.strides[:4], device=device)
+        self.bbox_head.ohem_extractor = self.roi_extractor
         layers = self.bbox_head.layers() + (self.dpool.layers() if self.dpool is not None else [])
         layers += self.rpn_head.layers() + self.neck.layers() + self.backbone.layers()
         norms = self.bbox_head.norm_layers()
@@ -172,7 +180,7 @@ class FasterRCNN(DetectorBase):
             rpn_loss = self.rpn_head.loss_and_grad(gt_boxes, im_info, step, image_offset, step_dev=step_dev, assigned=early)
             self.rpn_head.backward(self.dP, [False] * 5, flush=not defer_rpn)
         rois, _, _, num_rois = self.rpn_head.get_proposals(im_info)
-        rois_s = self.bbox_head.sample(rois, num_rois, gt_boxes, step, image_offset, step_dev)
+        rois_s = self.bbox_head.sample(rois, num_rois, gt_boxes, step, image_offset, step_dev, feats=P)
         pooled = self.roi_extractor.forward(P, rois_s, prepare_gather=self.roi_bwd_gather)
         self.bbox_head.forward(pooled)
         rcnn_loss = self.bbox_head.loss_and_grad()

@@ -62,6 +62,8 @@ DEFAULTS = {
         "dpool_offset_fcs": 3,            # FCs of the offset head (1: Deformable-ConvNets' FPN head, 3: DCN v2 / mmdetection)
         "mask_iou": False,                # mask_rcnn: Mask Scoring R-CNN's MaskIoU head (Huang et al. 2019); segm detections are scored box score x predicted mask IoU
         "mask_iou_weight": 1.0,           # weight of the MaskIoU head's L2 loss
+        "ohem": False,                    # faster_rcnn / mask_rcnn: online hard example mining (Shrivastava et al. 2016) -- the box head trains on the batch_rois highest-loss RoIs of a read-only pass over every candidate, no fg:bg quota
+        "ohem_nms": 0.7,                  # IoU above which a higher-loss RoI suppresses a lower-loss one before the choice, in (0, 1]; 1 = no dedup
     },
     "dataset": {
         "type": "synthetic",              # synthetic | coco | voc (ann_file = Annotations directory)

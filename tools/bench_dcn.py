@@ -9,8 +9,9 @@ padded to 1344, weight gradients grouped on a side stream, RPN branch on its own
     python tools/bench_dcn.py --dcn-stages '' --mask 1 --bbox-head 4conv1fc --head-norm gn     # Mask R-CNN, GN in both heads
     python tools/bench_dcn.py --dcn-stages '' --reg-loss giou --reg-loss-weight 10     # GIoU loss on the decoded box in the box head
     python tools/bench_dcn.py --dcn-stages '' --mask 1 --mask-iou 1     # Mask Scoring R-CNN: the MaskIoU head on the mask branch
+    python tools/bench_dcn.py --dcn-stages '' --ohem 1 --ohem-nms 0.7   # online hard example mining in the box head
 
-Prints one JSON line: {"dcn_stages", "modulated", "groups", "roi_pool", "mask", "mask_iou", "img_per_s", "step_ms", "losses"}.
+Prints one JSON line: {"dcn_stages", "modulated", "groups", "roi_pool", "mask", "mask_iou", "ohem", "img_per_s", "step_ms", "losses"}.
 """
 import argparse
 import json
@@ -36,6 +37,8 @@ def main():
     ap.add_argument("--mask", type=int, default=0, help="1 = Mask R-CNN (ground-truth masks: an ellipse in every box, as bench.py)")
     ap.add_argument("--mask-iou", type=int, default=0, help="1 = Mask Scoring R-CNN's MaskIoU head (needs --mask 1)")
     ap.add_argument("--mask-iou-weight", type=float, default=1.0)
+    ap.add_argument("--ohem", type=int, default=0, choices=(0, 1), help="1 = online hard example mining in the box head")
+    ap.add_argument("--ohem-nms", type=float, default=0.7, help="dedup IoU of --ohem 1, in (0, 1]; 1 = none")
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     args = ap.parse_args()
@@ -50,7 +53,7 @@ def main():
                        dcn_groups=args.groups, roi_pool=args.roi_pool, bbox_head=args.bbox_head,
                        head_norm=args.head_norm, gn_groups=args.gn_groups, with_mask=bool(args.mask),
                        reg_loss=args.reg_loss, reg_loss_weight=args.reg_loss_weight, mask_iou=bool(args.mask_iou),
-                       mask_iou_weight=args.mask_iou_weight)
+                       mask_iou_weight=args.mask_iou_weight, ohem=bool(args.ohem), ohem_nms=args.ohem_nms)
     model.enable_wgrad_stream()
     model.enable_branch_stream()
     model.enable_grouped_wgrad()
@@ -80,7 +83,7 @@ def main():
     dt = time.perf_counter() - t0
     vals = [float(v) for v in torch.cat(list(losses)).cpu().numpy()]
     print(json.dumps({"dcn_stages": list(stages), "modulated": bool(args.modulated), "groups": args.groups,
-                      "roi_pool": args.roi_pool, "mask": bool(args.mask), "mask_iou": bool(args.mask_iou), "bbox_head": args.bbox_head, "head_norm": args.head_norm,
+                      "roi_pool": args.roi_pool, "mask": bool(args.mask), "mask_iou": bool(args.mask_iou), "ohem": bool(args.ohem), "bbox_head": args.bbox_head, "head_norm": args.head_norm,
                       "reg_loss": args.reg_loss,
                       "img_per_s": round(BATCH_PER_GPU * args.steps / dt, 2),
                       "step_ms": round(1e3 * dt / args.steps, 3), "losses": vals}), flush=True)
