@@ -617,6 +617,39 @@ int mxdet_maskiou_loss(const uint16_t* pred, const int32_t* cls, const float* ta
 int mxdet_maskiou_score(const float* dets, const uint16_t* pred, int64_t R, int32_t ld, float* scores,
                         mxdet_stream_t stream);
 
+/* Keypoint R-CNN (He et al., ICCV 2017, section 5). logits bf16 [R,S_in,S_in,Kpad] (Kpad % 8 == 0, channels
+ * [K,Kpad) are padding). The map the loss and the decode see is the fixed x2 bilinear upsample U [S,S], S = 2*S_in, of a
+ * channel (half-pixel centres, edge replication, horizontal first; each product and sum one unfused fp32 operation):
+ *   h[i][2j+p] = 0.75f*in[i][j] + 0.25f*in[i][clamp(j-1+2p, 0, S_in-1)],  U[2i+q][X] = 0.75f*h[i][X] + 0.25f*h[clamp(i-1+2q)][X].
+ * It is formed in LDS / registers and never stored.
+ *
+ * Target, int32 [R,K] (-1 = not trained). rois [R,5] (batch index, x1,y1,x2,y2), matched_gt / labels [R], gt_keypoints fp32
+ * [N,G,K,3] = (x, y, v) in the frame of the network input, v > 0 = labelled. Rows with labels <= 0, matched_gt outside
+ * [0,G) or (int)rois[r,0] outside [0,N) give -1 and read no keypoint memory. Else, with rw = fmaxf(x2-x1, 1.0f):
+ *   bx = (kx == x2) ? S-1 : (int)floorf((kx - x1) * ((float)S / rw)), by alike in y;
+ *   target = by*S + bx when v > 0, 0 <= bx < S and 0 <= by < S, else -1. */
+int mxdet_keypoint_target(const float* rois, const int32_t* matched_gt, const int32_t* labels, const float* gt_keypoints,
+                          int64_t R, int32_t N, int32_t G, int32_t K, int32_t S_in, int32_t* targets, mxdet_stream_t stream);
+/* Heatmap loss. targets int32 [R,K] as above (values outside [0,S*S) count as -1). n_valid = number of valid targets,
+ * counted on the device; k = (loss_scale * weight) / (float)max(n_valid, 1);
+ *   loss_out[0] = k * sum over valid (r,j) of log(sum_i exp(U_i - max U)) - (U_target - max U)   (mxdet_expf / mxdet_logf;
+ *   fp32, fixed order: per roi over ascending channels, then over ascending rois);
+ *   grad bf16 [R,S_in,S_in,Kpad], fully written: ((softmax(U) - onehot) * k) through the adjoint of the upsample in gather
+ *   form -- d_in[i][j] = sum_t w_t * (sum_s w_s * Q[clamp(2i-1+s, 0, S-1)][clamp(2j-1+t, 0, S-1)]), w = (.25,.75,.75,.25),
+ *   s and t ascending --, zeros for invalid (r,j) and channels >= K.
+ * No atomics: bit-identical from run to run. One workgroup per roi holds the roi's block in LDS: S_in <= 32 and
+ * 16*S_in^2 + 2*K*S_in^2 + 12*K + 160 <= 65536 bytes (MXDET_ESHAPE otherwise). R = 0 writes loss_out[0] = 0. */
+size_t mxdet_keypoint_loss_workspace_bytes(int64_t R);
+int mxdet_keypoint_loss(const uint16_t* logits, const int32_t* targets, int64_t R, int32_t S_in, int32_t Kpad, int32_t K,
+                        float loss_scale, float weight, float* loss_out, uint16_t* grad, void* workspace,
+                        size_t workspace_bytes, mxdet_stream_t stream);
+/* Test time, out fp32 [R,K,3] = (x, y, score). dets [R,6] = (x1,y1,x2,y2,score,class) in the frame the keypoints are wanted
+ * in. Per channel j < K: the argmax of U (ties: the lowest linear index) = (by, bx);
+ *   x = x1 + ((float)bx + 0.5f) * (rw / (float)S), y alike, score = the maximal value of U.
+ * Rows with (int)class <= 0 (padding) give zeros and read no logits. 2*K*S_in^2 <= 65536 bytes of LDS. */
+int mxdet_keypoint_decode(const uint16_t* logits, const float* dets, int64_t R, int32_t S_in, int32_t Kpad, int32_t K,
+                          float* out, mxdet_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * backbones / necks / rpn_heads / bbox_heads / mask_heads (README.md:27-31) -- dense contractions.
  * MXNet roles: Convolution (+ BatchNorm(use_global_stats) + Activation + elemwise_add),

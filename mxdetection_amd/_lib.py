@@ -205,6 +205,10 @@ SIGNATURES = {
     "mxdet_maskiou_input_bwd": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
     "mxdet_maskiou_loss": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp]),
     "mxdet_maskiou_score": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
+    "mxdet_keypoint_target": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "mxdet_keypoint_loss_workspace_bytes": (c_sz, [c_i64]),
+    "mxdet_keypoint_loss": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_keypoint_decode": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mxdet_conv2d_fwd": (c_i32, [P(ConvDescT), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mxdet_conv2d_fwd_chain": (c_i32, [P(ConvDescT), c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
                                        c_i32, c_vp, c_vp]),

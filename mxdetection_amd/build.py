@@ -25,6 +25,8 @@ PER_FILE = {
     "mask.hip": ["-ffp-contract=off"],
     # the MaskIoU target / loss / score are compared bit for bit with a numpy-float32 restatement
     "mask_iou.hip": EXACT,
+    # the keypoint target and decode (the x2 bilinear upsample, one fp32 operation per step) are compared bit for bit
+    "keypoint.hip": EXACT,
     # the OHEM score is the box-head loss entries' per-roi loss bit for bit (one definition, loss_elem.h)
     "ohem.hip": EXACT,
     "wgrad.hip": [],

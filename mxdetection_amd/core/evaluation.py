@@ -121,13 +121,59 @@ def _iou_masks(dm, gm, crowd):
     return inter / np.maximum(union, 1e-12)
 
 
+# the per-keypoint standard deviations of the COCO person-keypoint benchmark (cocoapi, COCOeval.Params.kpt_oks_sigmas)
+COCO_KEYPOINT_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
+
+
+def _oks(dk, gk, gbox, garea, sigmas):
+    """Object keypoint similarity (cocoapi COCOeval.computeOks). dk [D,K,3], gk [G,K,3] = (x, y, v), gbox [G,4] xywh, garea
+    [G]. Over the labelled keypoints of the ground truth: mean of exp(-d^2 / (2 * area * (2*sigma)^2)); for a ground truth
+    without any (always ignored) the distance is measured to the doubled box, over all keypoints."""
+    D, Gn = dk.shape[0], gk.shape[0]
+    out = np.zeros((D, Gn))
+    var = (np.asarray(sigmas, np.float64) * 2.0) ** 2
+    for g in range(Gn):
+        xg, yg, vg = gk[g, :, 0], gk[g, :, 1], gk[g, :, 2]
+        k1 = int((vg > 0).sum())
+        x0, x1 = gbox[g, 0] - gbox[g, 2], gbox[g, 0] + 2.0 * gbox[g, 2]
+        y0, y1 = gbox[g, 1] - gbox[g, 3], gbox[g, 1] + 2.0 * gbox[g, 3]
+        for d in range(D):
+            xd, yd = dk[d, :, 0], dk[d, :, 1]
+            if k1 > 0:
+                dx, dy = xd - xg, yd - yg
+            else:
+                dx = np.maximum(0.0, x0 - xd) + np.maximum(0.0, xd - x1)
+                dy = np.maximum(0.0, y0 - yd) + np.maximum(0.0, yd - y1)
+            e = (dx ** 2 + dy ** 2) / var / (garea[g] + np.spacing(1)) / 2.0
+            if k1 > 0:
+                e = e[vg > 0]
+            out[d, g] = np.exp(-e).sum() / e.shape[0]
+    return out
+
+
+def coco_keypoint_eval(gts, dts, max_dets=(20,), sigmas=None):
+    """COCO keypoint AP / AR: the protocol of coco_bbox_eval (ten thresholds 0.50:0.05:0.95, 101 recall points, the same
+    matching) with OKS in the place of IoU.
+
+    gts: {image_id, category_id, keypoints [K,3] or flat [3K] = (x, y, v), bbox [x,y,w,h], area, iscrowd (optional)}; the
+    OKS scale is the ground truth's "area" (bbox area if absent). Ground truth without a labelled keypoint is ignored.
+    dts: {image_id, category_id, keypoints, score, area (optional, for the area-range test of unmatched detections; without
+    it the extent of the keypoints, as cocoapi's loadRes computes it)}.
+    sigmas: per-keypoint standard deviations, default the published COCO person values (K = 17).
+    Returns {"AP", "AP50", "AP75", "APm", "APl", "AR", "ARm", "ARl"} at max_dets[-1] detections per image (-1 where undefined)."""
+    sig = COCO_KEYPOINT_SIGMAS if sigmas is None else np.asarray(sigmas, np.float64)
+    r = coco_bbox_eval(gts, dts, max_dets, _kpt=sig)
+    return {"AP": r["AP"], "AP50": r["AP50"], "AP75": r["AP75"], "APm": r["APm"], "APl": r["APl"],
+            "AR": r["AR%d" % max_dets[-1]], "ARm": r["ARm"], "ARl": r["ARl"]}
+
+
 def coco_segm_eval(gts, dts, max_dets=(1, 10, 100)):
     """COCO mask AP / AR: same protocol as coco_bbox_eval with mask IoU. Every entry carries "mask" (binary [H,W] array in
     the image's frame); areas are mask areas unless the ground truth gives "area"."""
     return coco_bbox_eval(gts, dts, max_dets, _segm=True)
 
 
-def coco_bbox_eval(gts, dts, max_dets=(1, 10, 100), _segm=False):
+def coco_bbox_eval(gts, dts, max_dets=(1, 10, 100), _segm=False, _kpt=None):
     """COCO box AP / AR.
 
     gts: list of dicts {image_id, category_id, bbox [x,y,w,h], iscrowd (0/1, optional), area (optional)};
@@ -160,6 +206,9 @@ def coco_bbox_eval(gts, dts, max_dets=(1, 10, 100), _segm=False):
                     ga = np.array([x.get("area", x["bbox"][2] * x["bbox"][3]) for x in g], np.float64)
                 crowd = np.array([bool(x.get("iscrowd", 0)) for x in g], bool)
                 ig = crowd | (ga < rng[0]) | (ga > rng[1])
+                if _kpt is not None:
+                    gk = np.array([x["keypoints"] for x in g], np.float64).reshape(-1, len(_kpt), 3)
+                    ig = ig | ((gk[:, :, 2] > 0).sum(1) == 0)         # nothing labelled: ignored
                 go = np.argsort(ig, kind="mergesort")
                 gb, crowd, ig = gb[go], crowd[go], ig[go]
                 do = np.argsort([-x["score"] for x in d], kind="mergesort")[:max_dets[-1]]
@@ -168,6 +217,12 @@ def coco_bbox_eval(gts, dts, max_dets=(1, 10, 100), _segm=False):
                     db = np.array([np.asarray(d[i]["mask"]) > 0 for i in do], bool).reshape((-1,) + shp)
                     ious = _iou_masks(db, gb, crowd)
                     darea = db.reshape(db.shape[0], -1).sum(1).astype(np.float64) if db.shape[0] else np.zeros((0,))
+                elif _kpt is not None:
+                    db = np.array([d[i]["keypoints"] for i in do], np.float64).reshape(-1, len(_kpt), 3)
+                    ious = _oks(db, gk[go], gb, ga[go], _kpt)
+                    # as cocoapi's loadRes: without an "area" the extent of the keypoints
+                    ext = (np.ptp(db[:, :, 0], axis=1) * np.ptp(db[:, :, 1], axis=1)) if db.shape[0] else np.zeros((0,))
+                    darea = np.array([d[i].get("area", ext[j]) for j, i in enumerate(do)], np.float64)
                 else:
                     db = np.array([d[i]["bbox"] for i in do], np.float64).reshape(-1, 4)
                     ious, darea = _iou_xywh(db, gb, crowd), db[:, 2] * db[:, 3]
@@ -273,6 +328,24 @@ def voc_eval(gts, dts, iou_thresh=0.5, use_07_metric=False):
         prec = ctp / np.maximum(ctp + cfp, np.finfo(np.float64).eps)
         aps[c] = voc_ap(rec, prec, use_07_metric) if npos else 0.0
     return (float(np.mean(list(aps.values()))) if aps else 0.0), aps
+
+
+def detections_to_coco_keypoints(dets, num_dets, keypoints, image_ids, scales, class_to_cat=None):
+    """predict(with_keypoints=True) output -> COCO keypoint result dicts in ORIGINAL image coordinates: dets [N,M,6],
+    keypoints [N,M,K,3] = (x, y, heatmap score) at network-input scale. "keypoints" is the flat [x, y, 1] * K list of the
+    result format; "score" is the box score."""
+    keypoints = keypoints.detach().cpu().numpy() if hasattr(keypoints, "detach") else np.asarray(keypoints)
+    out = detections_to_coco(dets, num_dets, image_ids, scales, class_to_cat)
+    num = num_dets.detach().cpu().numpy() if hasattr(num_dets, "detach") else np.asarray(num_dets)
+    i = 0
+    for n in range(keypoints.shape[0]):
+        for k in range(int(num[n])):
+            kp = np.ones((keypoints.shape[2], 3), np.float64)
+            kp[:, :2] = keypoints[n, k, :, :2] / scales[n]
+            out[i]["keypoints"] = kp.reshape(-1).tolist()
+            out[i]["area"] = out[i]["bbox"][2] * out[i]["bbox"][3]
+            i += 1
+    return out
 
 
 def detections_to_coco(dets, num_dets, image_ids, scales, class_to_cat=None):

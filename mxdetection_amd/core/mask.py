@@ -103,6 +103,46 @@ def maskiou_score(dets, pred, out=None):
     return out
 
 
+def keypoint_target(rois, matched_gt, labels, gt_keypoints, size_in=28, out=None):
+    """Keypoint R-CNN's heatmap target (mxdet_keypoint_target): rois [R,5] f32, matched_gt / labels [R] i32, gt_keypoints
+    [N,G,K,3] f32 (x, y, v) -> int32 [R,K]: the linear index into the (2*size_in)^2 upsampled map, -1 = not trained."""
+    lib = _lib.load()
+    R = rois.shape[0]
+    N, G, K, _ = gt_keypoints.shape
+    if out is None:
+        out = torch.empty((R, K), dtype=torch.int32, device=rois.device)
+    check(lib.mxdet_keypoint_target(ptr(rois), ptr(matched_gt), ptr(labels), ptr(gt_keypoints), R, N, G, K, size_in, ptr(out),
+                                    stream_ptr()), "keypoint_target")
+    return out
+
+
+def keypoint_loss_workspace(R, device):
+    return torch.empty((_lib.load().mxdet_keypoint_loss_workspace_bytes(R),), dtype=torch.uint8, device=device)
+
+
+def keypoint_loss(logits, targets, loss_out, grad, workspace, loss_scale=1.0, weight=1.0, num_keypoints=None):
+    """logits / grad bf16 [R,S_in,S_in,Kpad]; targets int32 [R,K]; loss_out f32[1] (mxdet_keypoint_loss): softmax
+    cross-entropy over the x2 upsampled map of every valid (roi, keypoint), normalised by their number."""
+    lib = _lib.load()
+    R, S_in, _, Kpad = logits.shape
+    K = targets.shape[1] if num_keypoints is None else num_keypoints
+    check(lib.mxdet_keypoint_loss(ptr(logits), ptr(targets), R, S_in, Kpad, K, loss_scale, weight, ptr(loss_out), ptr(grad),
+                                  ptr(workspace), workspace.numel(), stream_ptr()), "keypoint_loss")
+    return loss_out
+
+
+def keypoint_decode(logits, dets, num_keypoints, out=None):
+    """logits bf16 [R,S_in,S_in,Kpad], dets [R,6] f32 (x1,y1,x2,y2,score,class) -> f32 [R,K,3] = (x, y, score): the argmax of
+    the x2 upsampled map of each keypoint channel, placed in the box (mxdet_keypoint_decode); zeros on padding rows."""
+    lib = _lib.load()
+    R, S_in, _, Kpad = logits.shape
+    if out is None:
+        out = torch.empty((R, num_keypoints, 3), dtype=torch.float32, device=logits.device)
+    check(lib.mxdet_keypoint_decode(ptr(logits), ptr(dets), R, S_in, Kpad, num_keypoints, ptr(out), stream_ptr()),
+          "keypoint_decode")
+    return out
+
+
 def mask_paste(logits, dets, H, W, thresh=0.5, out=None, workspace=None):
     """Inference paste-back: logits bf16 [R,S,S,Cpad], dets [R,6] f32 (x1,y1,x2,y2,score,class) in the output frame
     -> full-frame instance masks [R,H,W] u8 (mxdet_mask_paste)."""

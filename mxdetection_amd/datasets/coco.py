@@ -15,19 +15,27 @@ import os
 import numpy as np
 
 
-def load_coco_roidb(ann_file, image_dir="", keep_crowd=False, min_area=0.0):
+def load_coco_roidb(ann_file, image_dir="", keep_crowd=False, min_area=0.0, with_keypoints=False):
+    """with_keypoints: entries gain "keypoints" [G,K,3] f32 = (x, y, v) from the annotations' flat "keypoints" lists
+    (person-keypoint files; K from the first category that names its keypoints, else from the data; annotations without
+    the field, and v = 0 rows, give zeros). Every other key is what it is without the option."""
     with open(ann_file, "r") as f:
         ds = json.load(f)
     cat_ids = sorted(c["id"] for c in ds["categories"])
     cat_to_cls = {cid: i + 1 for i, cid in enumerate(cat_ids)}
     class_names = ["__background__"] + [next(c["name"] for c in ds["categories"] if c["id"] == cid) for cid in cat_ids]
+    num_kp = 0
+    if with_keypoints:
+        named = [len(c["keypoints"]) for c in ds["categories"] if c.get("keypoints")]
+        flat = [len(a["keypoints"]) // 3 for a in ds.get("annotations", []) if a.get("keypoints")]
+        num_kp = named[0] if named else (flat[0] if flat else 17)
     by_image = {}
     for a in ds.get("annotations", []):
         by_image.setdefault(a["image_id"], []).append(a)
     roidb = []
     for im in sorted(ds["images"], key=lambda r: r["id"]):
         w, h = int(im["width"]), int(im["height"])
-        boxes, classes, polys = [], [], []
+        boxes, classes, polys, kps = [], [], [], []
         for a in sorted(by_image.get(im["id"], []), key=lambda r: r["id"]):
             if a.get("iscrowd", 0) and not keep_crowd:
                 continue
@@ -42,6 +50,13 @@ def load_coco_roidb(ann_file, image_dir="", keep_crowd=False, min_area=0.0):
             classes.append(cat_to_cls[a["category_id"]])
             seg = a.get("segmentation", [])
             polys.append([list(map(float, p)) for p in seg if len(p) >= 6] if isinstance(seg, list) else [])
+            if with_keypoints:
+                k = np.zeros((num_kp, 3), np.float32)
+                flat = a.get("keypoints")
+                if flat is not None and len(flat) == 3 * num_kp:
+                    k[:] = np.asarray(flat, np.float32).reshape(num_kp, 3)
+                    k[k[:, 2] <= 0] = 0
+                kps.append(k)
         roidb.append({
             "image": os.path.join(image_dir, im["file_name"]) if image_dir else im["file_name"],
             "id": im["id"], "height": h, "width": w,
@@ -50,6 +65,8 @@ def load_coco_roidb(ann_file, image_dir="", keep_crowd=False, min_area=0.0):
             "polygons": polys,
             "flipped": False,
         })
+        if with_keypoints:
+            roidb[-1]["keypoints"] = np.asarray(kps, np.float32).reshape(-1, num_kp, 3)
     return roidb, class_names
 
 

@@ -49,18 +49,22 @@ def epoch_order(roidb, global_batch, epoch, seed=0, shuffle=True, aspect_groupin
 
 class HostBatch:
     """What the host side produces for one per-rank batch (numpy only; no device calls)."""
-    __slots__ = ("frames", "flips", "shapes", "scales", "resized", "pad", "gt", "im_info", "poly", "indices")
+    __slots__ = ("frames", "flips", "shapes", "scales", "resized", "pad", "gt", "im_info", "poly", "indices", "kp")
 
 
 class DetectionLoader:
     def __init__(self, roidb, batch_per_gpu=2, device="cuda", rank=0, world=1, reader=None, preprocessor=None,
-                 g_max=100, with_masks=False, shuffle=True, aspect_grouping=True, seed=0, num_workers=4, depth=2):
+                 g_max=100, with_masks=False, shuffle=True, aspect_grouping=True, seed=0, num_workers=4, depth=2,
+                 with_keypoints=False, num_keypoints=17):
+        """with_keypoints: batches also carry "gt_keypoints" fp32 [N, g_max, num_keypoints, 3] = (x, y, v) in the frame of
+        the network input (entries without a "keypoints" field, and padding instances, give zeros)."""
         from .synthetic import synthetic_reader
         self.roidb, self.b, self.device = roidb, batch_per_gpu, device
         self.rank, self.world = rank, world
         self.reader = reader or synthetic_reader
         self.pre = preprocessor or T.BatchPreprocessor(pad_to="orient")
         self.g_max, self.with_masks = g_max, with_masks
+        self.with_keypoints, self.num_keypoints = bool(with_keypoints), int(num_keypoints)
         self.shuffle, self.aspect_grouping, self.seed = shuffle, aspect_grouping, seed
         self.num_workers, self.depth = max(1, num_workers), max(2, depth)
         self.epoch = 0
@@ -93,6 +97,7 @@ class DetectionLoader:
         hb.gt = -np.ones((N, self.g_max, 5), np.float32)
         hb.im_info = np.zeros((N, 3), np.float32)
         polys = []
+        hb.kp = np.zeros((N, self.g_max, self.num_keypoints, 3), np.float32) if self.with_keypoints else None
         for n, e in enumerate(entries):
             G = min(int(e["boxes"].shape[0]), self.g_max)
             w = hb.shapes[n][1]
@@ -104,6 +109,8 @@ class DetectionLoader:
             hb.gt[n, :G, :4] = bx
             hb.gt[n, :G, 4] = e["gt_classes"][:G]
             hb.im_info[n] = (hb.resized[n][0], hb.resized[n][1], hb.scales[n])
+            if self.with_keypoints and G and e.get("keypoints") is not None:
+                hb.kp[n, :G] = T.transform_keypoints(e["keypoints"][:G], hb.scales[n], hb.flips[n], w)
             if self.with_masks:
                 polys.append([T.transform_polygons(p, hb.scales[n], hb.flips[n], w) for p in e.get("polygons", [])[:G]])
         hb.poly = T.pack_polygons(polys, N, self.g_max) if self.with_masks else None
@@ -119,6 +126,9 @@ class DetectionLoader:
         s["gt"] = torch.empty((self.b, self.g_max, 5), dtype=torch.float32, device=self.device)
         s["info_pin"] = torch.empty((self.b, 3), dtype=torch.float32, pin_memory=True)
         s["info"] = torch.empty((self.b, 3), dtype=torch.float32, device=self.device)
+        if self.with_keypoints:
+            s["kp_pin"] = torch.empty((self.b, self.g_max, self.num_keypoints, 3), dtype=torch.float32, pin_memory=True)
+            s["kp"] = torch.empty((self.b, self.g_max, self.num_keypoints, 3), dtype=torch.float32, device=self.device)
         s["img"] = None
         s["masks"] = None
         s["ready"] = torch.cuda.Event()
@@ -143,11 +153,15 @@ class DetectionLoader:
             o += f.size
         s["gt_pin"].numpy()[...] = hb.gt
         s["info_pin"].numpy()[...] = hb.im_info
+        if self.with_keypoints:
+            s["kp_pin"].numpy()[...] = hb.kp
         with torch.cuda.stream(self._copy_stream):
             self._copy_stream.wait_event(s["free"])            # the step that last read this slot has been enqueued
             s["raw"][:total].copy_(s["pinned"][:total], non_blocking=True)
             s["gt"].copy_(s["gt_pin"], non_blocking=True)
             s["info"].copy_(s["info_pin"], non_blocking=True)
+            if self.with_keypoints:
+                s["kp"].copy_(s["kp_pin"], non_blocking=True)
             frames = [s["raw"][offs[n]:offs[n] + f.size].view(f.shape[0], f.shape[1], 3) for n, f in enumerate(hb.frames)]
             hp, wp = hb.pad
             if s["img"] is None or tuple(s["img"].shape) != (len(frames), 3, hp, wp):
@@ -233,6 +247,8 @@ class DetectionLoader:
                 out = {"image": s["img"], "gt_boxes": s["gt"], "im_info": s["info"]}
                 if self.with_masks:
                     out["gt_masks"] = s["masks"]
+                if self.with_keypoints:
+                    out["gt_keypoints"] = s["kp"]
                 yield out
                 s["free"].record(cur)        # everything the consumer enqueued on this slot precedes the next upload
         finally:

@@ -20,6 +20,9 @@ def build_detector(cfg, device="cuda"):
         if net.mask_iou and net.type != "mask_rcnn":
             raise ValueError("network.mask_iou = %r: %s has no mask branch to score (the MaskIoU head is a mask_rcnn option)"
                              % (net.mask_iou, net.type))
+        if net.keypoints not in (0, 1, False, True):
+            raise ValueError("network.keypoints must be 0 or 1 (got %r)" % (net.keypoints,))
+        kpt = dict(with_keypoints=bool(net.keypoints), num_keypoints=net.num_keypoints, keypoint_weight=net.keypoint_weight)
         dpool = dict(roi_pool=str(net.roi_pool), dpool_trans_std=float(net.dpool_trans_std),
                      dpool_sample_per_part=int(net.dpool_sample_per_part), dpool_offset_fcs=int(net.dpool_offset_fcs))
         heads = dict(bbox_head=str(net.bbox_head), head_norm=str(net.head_norm), gn_groups=net.gn_groups)
@@ -27,11 +30,14 @@ def build_detector(cfg, device="cuda"):
                            rois_per_image=tr.batch_rois, pre_nms_top_n=tr.rpn_pre_nms_top_n,
                            post_nms_top_n=tr.rpn_post_nms_top_n, with_mask=(net.type == "mask_rcnn"), **dcn, **dpool, **heads,
                            **reg, mask_iou=bool(net.mask_iou), mask_iou_weight=net.mask_iou_weight, ohem=bool(net.ohem),
-                           ohem_nms=net.ohem_nms)
+                           ohem_nms=net.ohem_nms, **kpt)
     elif net.type == "retinanet":
         if net.ohem:
             raise ValueError("network.ohem = %r: retinanet has no box head to mine RoIs for (OHEM is a faster_rcnn / mask_rcnn "
                              "option)" % (net.ohem,))
+        if net.keypoints:
+            raise ValueError("network.keypoints = %r: retinanet has no RoI branch to put a keypoint head on (Keypoint R-CNN is "
+                             "a faster_rcnn / mask_rcnn option)" % (net.keypoints,))
         if net.mask_iou:
             raise ValueError("network.mask_iou = %r: retinanet has no mask branch to score (the MaskIoU head is a mask_rcnn "
                              "option)" % (net.mask_iou,))
@@ -53,17 +59,21 @@ def build_detector(cfg, device="cuda"):
 
 
 def build_loader(cfg, device="cuda", rank=0, world=1, train=True, with_masks=None):
-    """Config -> (roidb, class names, DetectionLoader)."""
+    """Config -> (roidb, class names, DetectionLoader). With network.keypoints the roidb carries keypoints and training
+    batches carry gt_keypoints."""
     import numpy as np
     from ..datasets import append_flipped, filter_roidb, load_coco_roidb, synthetic_roidb
     from ..datasets.loader import DetectionLoader
     from ..datasets.synthetic import synthetic_reader
     from ..process_data import BatchPreprocessor
     ds = cfg.dataset
+    kpt = bool(cfg.network.keypoints)
     if ds.type == "synthetic":
-        roidb, names, reader = synthetic_roidb(ds.num_images, seed=1, num_classes=cfg.network.num_classes - 1), None, synthetic_reader
+        roidb = synthetic_roidb(ds.num_images, seed=1, num_classes=cfg.network.num_classes - 1,
+                                num_keypoints=int(cfg.network.num_keypoints) if kpt else 0)
+        names, reader = None, synthetic_reader
     elif ds.type == "coco":
-        roidb, names = load_coco_roidb(ds.ann_file, ds.image_dir)
+        roidb, names = load_coco_roidb(ds.ann_file, ds.image_dir, with_keypoints=kpt)
         # frames are stored as uint8 [h,w,3] .npy arrays next to / instead of the JPEGs (no decoder in the image)
         reader = lambda e: np.load(e["image"] if e["image"].endswith(".npy") else e["image"].rsplit(".", 1)[0] + ".npy")  # noqa: E731
     elif ds.type == "voc":
@@ -83,5 +93,6 @@ def build_loader(cfg, device="cuda", rank=0, world=1, train=True, with_masks=Non
     loader = DetectionLoader(roidb, tr.batch_images if train else cfg.TEST.batch_images, device=device, rank=rank, world=world,
                              reader=reader, preprocessor=pre, g_max=ds.max_gt,
                              with_masks=(train and cfg.network.type == "mask_rcnn") if with_masks is None else with_masks,
-                             shuffle=train and tr.shuffle, aspect_grouping=train and tr.aspect_grouping, seed=tr.seed)
+                             shuffle=train and tr.shuffle, aspect_grouping=train and tr.aspect_grouping, seed=tr.seed,
+                             with_keypoints=train and kpt, num_keypoints=int(cfg.network.num_keypoints))
     return roidb, names, loader

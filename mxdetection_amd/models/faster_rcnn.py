@@ -12,7 +12,7 @@ from ..core.bbox import check_ohem
 from ..core.loss import check_reg_loss
 from .backbones import ResNet
 from .bbox_heads import BBoxHead, ConvFCBBoxHead
-from .mask_heads import FCNMaskHead, MaskIoUHead
+from .mask_heads import FCNMaskHead, KeypointHead, MaskIoUHead
 from .necks import FPN
 from .roi_extractors import DeformRoIExtractor, FPNRoIExtractor
 from .rpn_heads import RPNHead
@@ -40,7 +40,8 @@ class FasterRCNN(DetectorBase):
                  pre_nms_top_n=2000, post_nms_top_n=2000, with_mask=False, dcn_stages=(), dcn_modulated=True,
                  dcn_groups=1, roi_pool="roi_align", dpool_trans_std=0.1, dpool_sample_per_part=4, dpool_offset_fcs=3,
                  bbox_head="2fc", head_norm="none", gn_groups=32, reg_loss="smooth_l1", reg_loss_weight=1.0,
-                 mask_iou=False, mask_iou_weight=1.0, ohem=False, ohem_nms=0.7):
+                 mask_iou=False, mask_iou_weight=1.0, ohem=False, ohem_nms=0.7, with_keypoints=False, num_keypoints=17,
+                 keypoint_weight=1.0):
         """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
         roi_pool: the box branch's RoI pooling -- 'roi_align', or deformable RoI pooling with its offset head, 'dpool'
         (v1) / 'mdpool' (v2, modulated) (roi_extractors.DeformRoIExtractor, options dpool_*). The mask branch keeps its
@@ -56,13 +57,26 @@ class FasterRCNN(DetectorBase):
         starts exactly as in the model without it.
         ohem / ohem_nms: online hard example mining (Shrivastava et al. 2016) -- the box head trains on the rois_per_image
         highest-loss RoIs of a read-only pass over every candidate of the image (proposals and ground truth), deduplicated
-        by NMS at IoU ohem_nms in (0, 1] (1 = none), with no fg:bg quota (bbox_heads.BBoxHead.sample). It adds no parameter."""
+        by NMS at IoU ohem_nms in (0, 1] (1 = none), with no fg:bg quota (bbox_heads.BBoxHead.sample). It adds no parameter.
+        with_keypoints / num_keypoints / keypoint_weight: Keypoint R-CNN -- a keypoint head (mask_heads.KeypointHead) on a
+        14x14 RoIAlign of its own over the foreground rois, with or without the mask branch; its heatmap loss, times
+        keypoint_weight, is the LAST of the step's losses, training takes gt_keypoints [N,G,num_keypoints,3], and
+        predict(with_keypoints=True) returns the decoded keypoints. The head draws its initial weights from a generator of
+        its own, so every other parameter starts exactly as in the model without it."""
         check_head_options(bbox_head, head_norm, gn_groups, with_mask)
         if mask_iou and not with_mask:
             raise ValueError("mask_iou needs the mask branch (with_mask=True): the MaskIoU head scores the mask head's output")
         if mask_iou and not (isinstance(mask_iou_weight, (int, float)) and not isinstance(mask_iou_weight, bool)
                              and 0.0 < float(mask_iou_weight) < float("inf")):
             raise ValueError("mask_iou_weight must be a positive finite number (got %r)" % (mask_iou_weight,))
+        if not isinstance(with_keypoints, (bool, int)):
+            raise ValueError("with_keypoints must be a bool (got %r)" % (with_keypoints,))
+        if with_keypoints:
+            if not isinstance(num_keypoints, int) or isinstance(num_keypoints, bool) or not 1 <= num_keypoints <= 32:
+                raise ValueError("num_keypoints must be an integer in [1, 32] (got %r)" % (num_keypoints,))
+            if not (isinstance(keypoint_weight, (int, float)) and not isinstance(keypoint_weight, bool)
+                    and 0.0 < float(keypoint_weight) < float("inf")):
+                raise ValueError("keypoint_weight must be a positive finite number (got %r)" % (keypoint_weight,))
         check_reg_loss(reg_loss, reg_loss_weight)
         if not isinstance(ohem, (bool, int)):
             raise ValueError("ohem must be a bool (got %r)" % (ohem,))
@@ -78,7 +92,13 @@ class FasterRCNN(DetectorBase):
         # RoIAlign backward: deterministic gather form (no atomics, no fp32 accumulators, writes the bf16 maps directly);
         # False selects the fp32-atomic scatter form (310 us + zero-fill + finalize at the benchmark shape)
         self.roi_bwd_gather = True
-        self.mask_head = self.mask_iou_head = None
+        self.mask_head = self.mask_iou_head = self.keypoint_head = None
+        self.with_keypoints = bool(with_keypoints)
+        if self.with_keypoints:   # Keypoint R-CNN: the keypoint branch's backward runs before the mask branch's
+            self.keypoint_head = KeypointHead(256, self.arena, self.ws, device, torch.Generator().manual_seed(seed + 104729),
+                                              num_keypoints=num_keypoints, rois_per_image=max(1, rois_per_image // 4),
+                                              weight=keypoint_weight)
+            self.keypoint_roi_extractor = FPNRoIExtractor([4, 8, 16, 32], pooled=(14, 14), device=device)
         if with_mask:   # Mask R-CNN (BASELINE.json config 4): the mask branch's backward runs first
             if mask_iou:    # ... and within it the MaskIoU head's, which sits behind the mask head's output
                 self.mask_iou_head = MaskIoUHead(256, self.arena, self.ws, device, torch.Generator().manual_seed(seed + 7919),
@@ -123,6 +143,8 @@ class FasterRCNN(DetectorBase):
             if self.mask_iou_head is not None:
                 layers = self.mask_iou_head.layers() + layers
             norms = self.mask_head.norm_layers() + norms
+        if self.keypoint_head is not None:
+            layers = self.keypoint_head.layers() + layers
         self._finalize_params(layers, norm_layers=norms)
 
     def plan(self, N, H, W, g_max):
@@ -143,6 +165,8 @@ class FasterRCNN(DetectorBase):
             self.mask_head.plan(N)
             if self.mask_iou_head is not None:
                 self.mask_iou_head.plan(N, g_max)
+        if self.keypoint_head is not None:
+            self.keypoint_head.plan(N)
         self.ws.get()
         self.ws_rpn.get()
         # one flat bf16 buffer (levels are views, finest first): the RoI extractor finalizes P2..P5 with one launch
@@ -155,8 +179,10 @@ class FasterRCNN(DetectorBase):
         self.dC = [None] + [torch.empty(s, dtype=torch.bfloat16, device=dev) for s in c_shapes[1:]]
         self.planned = key
 
-    def forward_backward(self, image, gt_boxes, im_info, step=0, image_offset=0, step_dev=None, gt_masks=None):
-        """image NCHW [N,3,H,W]; gt_boxes [N,G,5] f32 (class < 0 padding); im_info [N,3] f32."""
+    def forward_backward(self, image, gt_boxes, im_info, step=0, image_offset=0, step_dev=None, gt_masks=None,
+                         gt_keypoints=None):
+        """image NCHW [N,3,H,W]; gt_boxes [N,G,5] f32 (class < 0 padding); im_info [N,3] f32; gt_masks [N,G,H,W] u8 (mask
+        branch); gt_keypoints [N,G,K,3] f32 = (x, y, v) (keypoint branch)."""
         N, _, H, W = image.shape
         self.plan(N, H, W, gt_boxes.shape[1])
         early = self.branch is not None
@@ -196,7 +222,17 @@ class FasterRCNN(DetectorBase):
                 iou_head.targets(self.mask_head, gt_boxes, gt_masks)
                 iou_head.forward(mpooled, self.mask_head.o, self.mask_head.cls)
                 maskiou_loss = iou_head.loss_and_grad()
+        kpt_head, kpt_loss = self.keypoint_head, None
+        if kpt_head is not None:
+            if gt_keypoints is None:
+                raise ValueError("a model with the keypoint head trains on gt_keypoints [N,G,%d,3]" % kpt_head.K)
+            krois = kpt_head.select_rois(self.bbox_head)
+            kpt_head.targets(gt_keypoints)
+            kpooled = self.keypoint_roi_extractor.forward(P, krois, prepare_gather=self.roi_bwd_gather)
+            kpt_head.forward(kpooled)
+            kpt_loss = kpt_head.loss_and_grad()
         # ---- backward ----
+        d_kpooled = kpt_head.backward() if kpt_head is not None else None
         if self.with_mask:
             # the MaskIoU head's backward completes first; its input gradient joins the mask head's at the RoI features
             # (the mask channel of its input is a constant: nothing flows into the mask logits)
@@ -217,6 +253,8 @@ class FasterRCNN(DetectorBase):
             self.roi_extractor.backward_gather(d_pooled.view(pooled.shape), self.dP[:4], accumulate=True)
             if self.with_mask:
                 self.mask_roi_extractor.backward_gather(d_mpooled, self.dP[:4], accumulate=True)
+            if kpt_head is not None:
+                self.keypoint_roi_extractor.backward_gather(d_kpooled, self.dP[:4], accumulate=True)
             if self._bucket_here(0):
                 self._reduce(0, self.mark_rpn, pre=self.ws_rpn if defer_rpn else None)
                 lo = self.mark_rpn
@@ -225,6 +263,8 @@ class FasterRCNN(DetectorBase):
             acc = self.roi_extractor.backward(d_pooled.view(pooled.shape), self.dP[:4], finalize=False)
             if self.with_mask:
                 self.mask_roi_extractor.backward(d_mpooled, self.dP[:4], shared_acc=acc, zero=False, finalize=False)
+            if kpt_head is not None:
+                self.keypoint_roi_extractor.backward(d_kpooled, self.dP[:4], shared_acc=acc, zero=False, finalize=False)
             self._join_branch()
             self.roi_extractor.finalize(self.dP[:4], accumulate=True)     # dP[l] = RPN part + RoI part
             self._reduce(0, self.mark_rpn)
@@ -234,20 +274,26 @@ class FasterRCNN(DetectorBase):
             self._reduce(lo, self.mark_fpn)
             lo = self.mark_fpn
         self._backbone_backward(lo)
-        if iou_head is not None:
-            return rpn_loss, rcnn_loss, mask_loss, maskiou_loss
+        losses = (rpn_loss, rcnn_loss)
         if self.with_mask:
-            return rpn_loss, rcnn_loss, mask_loss
-        return rpn_loss, rcnn_loss
+            losses += (mask_loss,)
+        if iou_head is not None:
+            losses += (maskiou_loss,)
+        if kpt_head is not None:
+            losses += (kpt_loss,)           # always the last
+        return losses
 
     def predict(self, image, im_info, score_thresh=0.05, nms_thresh=0.5, max_per_image=100, with_masks=False,
-                mask_thresh=0.5, nms_method="hard", soft_sigma=0.5):
+                mask_thresh=0.5, nms_method="hard", soft_sigma=0.5, with_keypoints=False):
         """Inference: forward, proposals, box head, then softmax / decode / per-class NMS / top-k on the GPU
         (core/evaluation, SURVEY.md section 8f rank 3); nms_method "linear" / "gaussian": Soft-NMS per class. Returns (dets [N,max_per_image,6] = x1,y1,x2,y2,score,class;
         num_dets [N]); with_masks (Mask R-CNN) adds the pasted-back instance masks [N,max_per_image,H,W] u8 in the
         frame of the network input: mask head on the detected boxes, sigmoid, bilinear resize into the box, threshold. A
         model with the MaskIoU head (mask_iou) returns a fourth value, the mask scores [N,max_per_image] f32: the
-        detection's score times the IoU the head predicts for its class (0 on padding rows); dets are unchanged."""
+        detection's score times the IoU the head predicts for its class (0 on padding rows); dets are unchanged.
+        with_keypoints (a model with the keypoint head) appends keypoints [N,max_per_image,K,3] f32 = (x, y, score) in the
+        frame of the network input as the LAST value: the keypoint head on the detected boxes, the argmax of each keypoint's
+        x2 upsampled heatmap placed in the box, the maximal logit as score; zeros on padding rows."""
         from ..core.evaluation import DetectionPostprocess
         N, _, H, W = image.shape
         g_max = self.planned[3] if self.planned is not None and self.planned[:3] == (N, H, W) else 100
@@ -264,19 +310,27 @@ class FasterRCNN(DetectorBase):
                                               stds=self.bbox_head.stds, nms_method=nms_method, soft_sigma=soft_sigma)
             self._post_key = key
         dets, num = self._post(o2[:, :self.bbox_head.nc], o2[:, self.bbox_head.nc:], rois.view(-1, 5), num_rois, im_info)
-        if not with_masks:
+        if not with_masks and not with_keypoints:
             return dets, num
-        assert self.with_mask, "with_masks needs a model built with the mask head"
+        assert self.with_mask or not with_masks, "with_masks needs a model built with the mask head"
+        assert self.keypoint_head is not None or not with_keypoints, "with_keypoints needs a model built with the keypoint head"
         M = dets.shape[1]
         flat = dets.view(N * M, 6)
         drois = torch.empty((N * M, 5), dtype=torch.float32, device=dets.device)
         drois[:, 0] = torch.arange(N, device=dets.device, dtype=torch.float32).repeat_interleave(M)
         drois[:, 1:] = flat[:, :4]            # padding rows are zero boxes with class -1: pasted as empty masks
+        kpts = ()
+        if with_keypoints:
+            kh = self.keypoint_head
+            klogits = kh.forward(self.keypoint_roi_extractor.forward(P, drois))
+            kpts = (M_.keypoint_decode(klogits, flat, kh.K).view(N, M, kh.K, 3),)
+        if not with_masks:
+            return (dets, num) + kpts
         mpooled = self.mask_roi_extractor.forward(P, drois)
         logits = self.mask_head.forward(mpooled)
         masks = M_.mask_paste(logits, flat, H, W, mask_thresh)
         if self.mask_iou_head is None:
-            return dets, num, masks.view(N, M, H, W)
+            return (dets, num, masks.view(N, M, H, W)) + kpts
         pred = self.mask_iou_head.forward(mpooled, logits, flat[:, 5].to(torch.int32))
         scores = M_.maskiou_score(flat, pred.view(N * M, -1))
-        return dets, num, masks.view(N, M, H, W), scores.view(N, M)
+        return (dets, num, masks.view(N, M, H, W), scores.view(N, M)) + kpts

@@ -253,7 +253,8 @@ class DetectorBase(CheckpointMixin):
         del snap
         torch.cuda.synchronize()
 
-    def capture(self, image, gt_boxes, im_info, lr, image_offset=0, warmup=2, gt_masks=None, momentum=0.9, wd=1e-4):
+    def capture(self, image, gt_boxes, im_info, lr, image_offset=0, warmup=2, gt_masks=None, momentum=0.9, wd=1e-4,
+                gt_keypoints=None):
         """Capture forward+backward+update into hipGraph segments (cut only at gradient all-reduces).
         The RNG step counter is read from device memory (step_dev), inputs from static buffers. momentum / wd are
         baked into the captured update kernels (lr is read from device memory: replay(lr=...)). The eager warm-up
@@ -263,13 +264,15 @@ class DetectorBase(CheckpointMixin):
         hyper = (float(momentum), float(wd))
         self.static_in = (image.clone(), gt_boxes.clone(), im_info.clone())
         self.static_masks = gt_masks.clone() if gt_masks is not None else None
+        self.static_keypoints = gt_keypoints.clone() if gt_keypoints is not None else None
+        kp = {} if gt_keypoints is None else {"gt_keypoints": self.static_keypoints}     # models without the head take none
         self.step_dev = torch.zeros((1,), dtype=torch.int32, device=dev)
         self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=dev)   # replay(lr=...) rewrites it
         self._lr_host = lr
 
         def eager_step(step):
             self.train_step(*self.static_in, step=step, image_offset=image_offset, lr=lr, gt_masks=self.static_masks,
-                            momentum=hyper[0], wd=hyper[1])
+                            momentum=hyper[0], wd=hyper[1], **kp)
         if warmup > 0:
             with self._weights_restored():
                 for i in range(warmup):     # eager warm-up: plans shapes and allocates every buffer
@@ -322,7 +325,7 @@ class DetectorBase(CheckpointMixin):
                 self._rec.seg_begin()
                 self._upd, self._upd_done = (((self.lr_dev,) + hyper) if self.dist is None else None), []
                 losses = self.forward_backward(*self.static_in, step=0, image_offset=image_offset, step_dev=self.step_dev,
-                                               gt_masks=self.static_masks)
+                                               gt_masks=self.static_masks, **kp)
                 self._upd = None
                 self.optimizer_step(self.lr_dev, hyper[0], hyper[1])
                 self._rec.finish(front, losses)        # detaches itself
@@ -397,7 +400,7 @@ class DetectorBase(CheckpointMixin):
         if self._rec is not None and self._rec.cap.tail_event is not None:
             self._rec.cap.tail_event.record_node()
 
-    def replay(self, image, gt_boxes, im_info, step, gt_masks=None, lr=None):
+    def replay(self, image, gt_boxes, im_info, step, gt_masks=None, lr=None, gt_keypoints=None):
         """One training step from the captured graphs; lr (if given) replaces the captured learning rate from here on."""
         si = self.static_in
         cap = self.captured
@@ -426,6 +429,8 @@ class DetectorBase(CheckpointMixin):
             si[2].copy_(im_info, non_blocking=True)
             if gt_masks is not None:
                 self.static_masks.copy_(gt_masks, non_blocking=True)
+            if gt_keypoints is not None:
+                self.static_keypoints.copy_(gt_keypoints, non_blocking=True)
         self.step_dev.fill_(step)
         scratch = ReplayScratch()
         for entry in captured.schedule:
@@ -452,14 +457,15 @@ class DetectorBase(CheckpointMixin):
         self.refresh_transposed()
 
     def train_step(self, image, gt_boxes, im_info, step=0, image_offset=0, lr=0.0025, gt_masks=None,
-                   momentum=0.9, wd=1e-4):
+                   momentum=0.9, wd=1e-4, gt_keypoints=None):
         self._upd, self._upd_done = ((lr, momentum, wd) if self.dist is None else None), []
         from ...ops import dense
         trace = not getattr(self, "_pf_wired", False) and self.prefetch != "0"
         if trace:
             dense.PF_TRACE = []
         try:
-            losses = self.forward_backward(image, gt_boxes, im_info, step, image_offset, gt_masks=gt_masks)
+            kp = {} if gt_keypoints is None else {"gt_keypoints": gt_keypoints}
+            losses = self.forward_backward(image, gt_boxes, im_info, step, image_offset, gt_masks=gt_masks, **kp)
         finally:
             self._upd = None
             if trace:

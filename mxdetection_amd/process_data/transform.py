@@ -69,6 +69,26 @@ def transform_polygons(polys, scale, flip, width):
     return out
 
 
+# COCO person keypoints: (left, right) index pairs that trade places under a horizontal flip
+COCO_KEYPOINT_FLIP_PAIRS = ((1, 2), (3, 4), (5, 6), (7, 8), (9, 10), (11, 12), (13, 14), (15, 16))
+
+
+def transform_keypoints(keypoints, scale, flip, width, flip_pairs=COCO_KEYPOINT_FLIP_PAIRS):
+    """Source-image keypoints [G,K,3] = (x, y, v) (pixel coordinates, as the boxes) -> network-input keypoints: flip in the
+    source frame (x' = width - 1 - x, then the left/right pairs trade places), then scale. Rows with v = 0 (not
+    labelled) stay all zero. Pairs that name an index past K are skipped (a K other than COCO's 17)."""
+    k = np.array(keypoints, dtype=np.float32, copy=True)
+    if k.size:
+        if flip:
+            k[..., 0] = np.float32(width - 1) - k[..., 0]
+            for a, b in flip_pairs:
+                if a < k.shape[1] and b < k.shape[1]:
+                    k[:, [a, b]] = k[:, [b, a]]
+        k[..., :2] *= np.float32(scale)
+        k[k[..., 2] <= 0] = 0
+    return k
+
+
 def pack_polygons(per_instance_polys, N, G):
     """per_instance_polys[n][g] = list of [V,2] arrays -> (verts [V,2] f32, poly_start [P+1] i32, inst_first [N*G+1] i32)."""
     verts, poly_start, inst_first = [], [0], [0]

@@ -64,6 +64,9 @@ DEFAULTS = {
         "mask_iou_weight": 1.0,           # weight of the MaskIoU head's L2 loss
         "ohem": False,                    # faster_rcnn / mask_rcnn: online hard example mining (Shrivastava et al. 2016) -- the box head trains on the batch_rois highest-loss RoIs of a read-only pass over every candidate, no fg:bg quota
         "ohem_nms": 0.7,                  # IoU above which a higher-loss RoI suppresses a lower-loss one before the choice, in (0, 1]; 1 = no dedup
+        "keypoints": 0,                   # faster_rcnn / mask_rcnn: 1 = Keypoint R-CNN's keypoint head (He et al. 2017); training then reads the roidb's keypoints
+        "keypoint_weight": 1.0,           # weight of the keypoint heatmap loss
+        "num_keypoints": 17,              # keypoints per instance (COCO person: 17)
     },
     "dataset": {
         "type": "synthetic",              # synthetic | coco | voc (ann_file = Annotations directory)

@@ -10,8 +10,9 @@ padded to 1344, weight gradients grouped on a side stream, RPN branch on its own
     python tools/bench_dcn.py --dcn-stages '' --reg-loss giou --reg-loss-weight 10     # GIoU loss on the decoded box in the box head
     python tools/bench_dcn.py --dcn-stages '' --mask 1 --mask-iou 1     # Mask Scoring R-CNN: the MaskIoU head on the mask branch
     python tools/bench_dcn.py --dcn-stages '' --ohem 1 --ohem-nms 0.7   # online hard example mining in the box head
+    python tools/bench_dcn.py --dcn-stages '' --keypoints 1             # Keypoint R-CNN: the keypoint head beside the box head
 
-Prints one JSON line: {"dcn_stages", "modulated", "groups", "roi_pool", "mask", "mask_iou", "ohem", "img_per_s", "step_ms", "losses"}.
+Prints one JSON line: {"dcn_stages", "modulated", "groups", "roi_pool", "mask", "mask_iou", "ohem", "keypoints", "img_per_s", "step_ms", "losses"}.
 """
 import argparse
 import json
@@ -39,6 +40,8 @@ def main():
     ap.add_argument("--mask-iou-weight", type=float, default=1.0)
     ap.add_argument("--ohem", type=int, default=0, choices=(0, 1), help="1 = online hard example mining in the box head")
     ap.add_argument("--ohem-nms", type=float, default=0.7, help="dedup IoU of --ohem 1, in (0, 1]; 1 = none")
+    ap.add_argument("--keypoints", type=int, default=0, choices=(0, 1),
+                    help="1 = Keypoint R-CNN's keypoint head (ground-truth keypoints: 17 points inside every box)")
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     args = ap.parse_args()
@@ -53,7 +56,8 @@ def main():
                        dcn_groups=args.groups, roi_pool=args.roi_pool, bbox_head=args.bbox_head,
                        head_norm=args.head_norm, gn_groups=args.gn_groups, with_mask=bool(args.mask),
                        reg_loss=args.reg_loss, reg_loss_weight=args.reg_loss_weight, mask_iou=bool(args.mask_iou),
-                       mask_iou_weight=args.mask_iou_weight, ohem=bool(args.ohem), ohem_nms=args.ohem_nms)
+                       mask_iou_weight=args.mask_iou_weight, ohem=bool(args.ohem), ohem_nms=args.ohem_nms,
+                       with_keypoints=bool(args.keypoints))
     model.enable_wgrad_stream()
     model.enable_branch_stream()
     model.enable_grouped_wgrad()
@@ -70,20 +74,32 @@ def main():
             m = (((xx - cx[..., None, None]) / rx[..., None, None]) ** 2 +
                  ((yy - cy[..., None, None]) / ry[..., None, None]) ** 2) <= 1.0
             masks[k] = (m & (b[..., 4] >= 0)[..., None, None]).to(torch.uint8).contiguous()
-    model.capture(*batches[0], lr=lr, image_offset=0, gt_masks=masks[0])
+    kps = [{}] * len(batches)
+    if args.keypoints:   # 17 labelled points inside every GT box (GT rows 0..15 are the valid ones), zeros on padding rows
+        gen = torch.Generator().manual_seed(17)
+        kps = []
+        for _, gt, _ in batches:
+            b = gt[:, :16]
+            u = torch.rand((b.shape[0], 16, 17, 2), generator=gen).to(device) * 0.8 + 0.1
+            kp = torch.ones((b.shape[0], 16, 17, 3), device=device)
+            kp[..., 0] = b[..., None, 0] + u[..., 0] * (b[..., None, 2] - b[..., None, 0])
+            kp[..., 1] = b[..., None, 1] + u[..., 1] * (b[..., None, 3] - b[..., None, 1])
+            kps.append({"gt_keypoints": (kp * (b[..., 4] >= 0)[..., None, None]).contiguous()})
+    model.capture(*batches[0], lr=lr, image_offset=0, gt_masks=masks[0], **kps[0])
     for i in range(args.warmup):
         img, gt, info = batches[i % len(batches)]
-        model.replay(img, gt, info, i, gt_masks=masks[i % len(batches)])
+        model.replay(img, gt, info, i, gt_masks=masks[i % len(batches)], **kps[i % len(batches)])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
         img, gt, info = batches[(args.warmup + i) % len(batches)]
-        losses = model.replay(img, gt, info, args.warmup + i, gt_masks=masks[(args.warmup + i) % len(batches)])
+        losses = model.replay(img, gt, info, args.warmup + i, gt_masks=masks[(args.warmup + i) % len(batches)],
+                              **kps[(args.warmup + i) % len(batches)])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     vals = [float(v) for v in torch.cat(list(losses)).cpu().numpy()]
     print(json.dumps({"dcn_stages": list(stages), "modulated": bool(args.modulated), "groups": args.groups,
-                      "roi_pool": args.roi_pool, "mask": bool(args.mask), "mask_iou": bool(args.mask_iou), "ohem": bool(args.ohem), "bbox_head": args.bbox_head, "head_norm": args.head_norm,
+                      "roi_pool": args.roi_pool, "mask": bool(args.mask), "mask_iou": bool(args.mask_iou), "ohem": bool(args.ohem), "keypoints": bool(args.keypoints), "bbox_head": args.bbox_head, "head_norm": args.head_norm,
                       "reg_loss": args.reg_loss,
                       "img_per_s": round(BATCH_PER_GPU * args.steps / dt, 2),
                       "step_ms": round(1e3 * dt / args.steps, 3), "losses": vals}), flush=True)

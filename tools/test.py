@@ -1,4 +1,5 @@
-"""Evaluation driver: checkpoint -> detections -> COCO box AP (the lineage's `test.py` role).
+"""Evaluation driver: checkpoint -> detections -> COCO box AP (the lineage's `test.py` role); mask AP for mask_rcnn and
+keypoint AP (OKS) for a model with the keypoint head (network.keypoints).
 
     python tools/test.py --cfg configs/faster_rcnn_r50_fpn.yaml --params output/faster_rcnn_r50_fpn-0012.params
 """
@@ -20,7 +21,8 @@ def main():
     ap.add_argument("overrides", nargs="*")
     args = ap.parse_args()
     import torch
-    from mxdetection_amd.core.evaluation import coco_bbox_eval, coco_segm_eval, detections_to_coco
+    from mxdetection_amd.core.evaluation import (coco_bbox_eval, coco_keypoint_eval, coco_segm_eval, detections_to_coco,
+                                                 detections_to_coco_keypoints)
     from mxdetection_amd.models.builder import build_detector, build_loader
     from mxdetection_amd.utils import load_config
     cfg = load_config(args.cfg, list(args.overrides) + ["TRAIN.flip=false"])
@@ -30,6 +32,9 @@ def main():
     elif not args.random_init:
         sys.exit("tools/test.py: no --params given (use --random-init to evaluate untrained weights on purpose)")
     segm = cfg.network.type == "mask_rcnn"
+    kpt = getattr(model, "keypoint_head", None) is not None
+    kgts, kdts = [], []          # keypoint evaluation, in original image coordinates
+    kw = {"with_keypoints": True} if kpt else {}
     roidb, _, loader = build_loader(cfg, train=False, with_masks=segm)
     te = cfg.TEST
     order = loader.rank_batches()
@@ -38,19 +43,23 @@ def main():
     for k, batch in enumerate(loader):
         if segm:
             out = model.predict(batch["image"], batch["im_info"], te.score_thresh, te.nms, te.max_per_image,
-                                with_masks=True, nms_method=te.nms_method, soft_sigma=te.soft_sigma)
+                                with_masks=True, nms_method=te.nms_method, soft_sigma=te.soft_sigma, **kw)
             dets, num, masks = out[:3]
             # Mask Scoring R-CNN (network.mask_iou): segm detections are ranked by box score x predicted mask IoU
-            mask_scores = out[3].cpu().numpy() if len(out) > 3 else None
+            mask_scores = out[3].cpu().numpy() if len(out) - kpt > 3 else None
         else:
-            dets, num = model.predict(batch["image"], batch["im_info"], te.score_thresh, te.nms, te.max_per_image,
-                                      nms_method=te.nms_method, soft_sigma=te.soft_sigma)
+            out = model.predict(batch["image"], batch["im_info"], te.score_thresh, te.nms, te.max_per_image,
+                                nms_method=te.nms_method, soft_sigma=te.soft_sigma, **kw)
+            dets, num = out[:2]
         ids = [int(i) for i in order[k]]
         fresh = [n for n, i in enumerate(ids) if i not in seen]          # the last batch wraps around
         scales = batch["im_info"][:, 2].cpu().numpy().tolist()
         res = detections_to_coco(dets, num, [roidb[i]["id"] for i in ids], scales)
         keep_ids = {roidb[ids[n]]["id"] for n in fresh}
         dts += [r for r in res if r["image_id"] in keep_ids]
+        if kpt:        # the keypoints are the last value predict returns
+            kres = detections_to_coco_keypoints(dets, num, out[-1], [roidb[i]["id"] for i in ids], scales)
+            kdts += [r for r in kres if r["image_id"] in keep_ids]
         if segm:
             dn, nn, mk, gm = dets.cpu().numpy(), num.cpu().numpy(), masks.cpu().numpy(), batch["gt_masks"].cpu().numpy()
             for n in fresh:
@@ -66,12 +75,18 @@ def main():
             for b, c in zip(e["boxes"], e["gt_classes"]):
                 gts.append({"image_id": e["id"], "category_id": int(c), "bbox": [float(b[0]), float(b[1]), float(b[2] - b[0] + 1),
                                                                                float(b[3] - b[1] + 1)]})
+            if kpt and e.get("keypoints") is not None:
+                for g, k in zip(gts[len(gts) - len(e["boxes"]):], e["keypoints"]):
+                    kgts.append(dict(g, keypoints=k.tolist(), area=g["bbox"][2] * g["bbox"][3]))
         if args.max_images and len(seen) >= args.max_images:
             break
     torch.cuda.synchronize()
     out = {"images": len(seen), "detections": len(dts), **coco_bbox_eval(gts, dts)}
     if segm:
         out["segm"] = coco_segm_eval(sgts, sdts)
+    if kpt:
+        sig = None if model.keypoint_head.K == 17 else [0.05] * model.keypoint_head.K      # COCO's sigmas are for its 17
+        out["keypoints"] = coco_keypoint_eval(kgts, kdts, sigmas=sig)
     print(json.dumps(out))
 
 

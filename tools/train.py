@@ -57,18 +57,20 @@ def main():
         for batch in loader:
             lr = sched(it)
             img, gt, info, mk = batch["image"], batch["gt_boxes"], batch["im_info"], batch.get("gt_masks")
+            kp = {"gt_keypoints": batch["gt_keypoints"]} if "gt_keypoints" in batch else {}     # network.keypoints
             if use_graph and not captured:
-                model.capture(img, gt, info, lr=lr, image_offset=off, gt_masks=mk, momentum=tr.momentum, wd=tr.wd)
+                model.capture(img, gt, info, lr=lr, image_offset=off, gt_masks=mk, momentum=tr.momentum, wd=tr.wd, **kp)
                 captured = True
             if use_graph:
-                losses = model.replay(img, gt, info, it, gt_masks=mk, lr=lr)
+                losses = model.replay(img, gt, info, it, gt_masks=mk, lr=lr, **kp)
             else:
                 losses = model.train_step(img, gt, info, step=it, image_offset=off, lr=lr, gt_masks=mk,
-                                          momentum=tr.momentum, wd=tr.wd)
+                                          momentum=tr.momentum, wd=tr.wd, **kp)
             it += 1
             seen += tr.batch_images * world
             if rank == 0 and tr.log_period and it % tr.log_period == 0:
-                # rpn (cls, box), rcnn (cls, box), then the mask loss (mask_rcnn) and the MaskIoU loss (network.mask_iou)
+                # rpn (cls, box), rcnn (cls, box), then the mask loss (mask_rcnn), the MaskIoU loss (network.mask_iou) and,
+                # always last, the keypoint loss (network.keypoints)
                 vals = [float(v) for v in torch.cat(list(losses)).cpu().numpy()]
                 dt = time.perf_counter() - t0
                 print("epoch %d iter %d lr %.5f losses %s  %.1f img/s" % (epoch, it, lr, ["%.4f" % v for v in vals], seen / dt),
