@@ -8,17 +8,16 @@ ConvFCBBoxHead (4conv1fc, the GN head recipe of Detectron / mmdetection): 4 x (c
 on [R,7,7,256] -> FC 12544 -> 1024 + ReLU -> the same fused output layer. It shares sampling, loss, the padded output
 layer, checkpoint layout and the layers() ordering with BBoxHead.
 """
-import os
-
 import torch
 
 from ...core import bbox as B_
 from ...core import loss as L_
-from ...ops import dense
-from ..utils.layers import ConvLayer, GroupNormLayer, cached_buf
+from ..utils.layers import LayerChain, buf_cache
 
 
 class BBoxHead:
+    num_fcs, num_convs, conv_dim, norm, gn_groups = 2, 0, 256, "none", 32      # the 2fc head: no tower
+
     def __init__(self, in_features, arena, ws, device, gen, num_classes=81, fc_dim=1024, rois_per_image=512,
                  fg_fraction=0.25, fg_thresh=0.5, bg_hi=0.5, bg_lo=0.0, stds=(0.1, 0.1, 0.2, 0.2), sigma=1.0,
                  seed=99, reg_loss="smooth_l1", reg_loss_weight=1.0, ohem=False, ohem_nms=0.7):
@@ -35,39 +34,41 @@ class BBoxHead:
         self.nc = num_classes
         self.reg_dim = 4 * num_classes
         self.ld = (num_classes + self.reg_dim + 63) // 64 * 64
-        self.fc_out = ConvLayer("bbox.fc_out", fc_dim, self.ld, 1, init_std=0.01, cout_real=num_classes + self.reg_dim, **kw)
-        self._build_trunk(in_features, fc_dim, kw)
-        self.fc_out.fc_in_hwc = ()
-        self.R, self.fg_fraction, self.fg_thresh, self.bg_hi, self.bg_lo = rois_per_image, fg_fraction, fg_thresh, bg_hi, bg_lo
-        self.stds, self.sigma, self.seed, self.device = stds, sigma, seed, device
-        self.in_features, self.fc_dim = in_features, fc_dim
-        self.fc1_ksplit = int(os.environ.get("MXDET_TUNE_FC1_KSPLIT", "4"))
-        self.bufs = {}
-
-    def _build_trunk(self, in_features, fc_dim, kw):
-        """The layers in front of fc_out, registered in backward completion order."""
-        self.fc2 = ConvLayer("bbox.fc2", fc_dim, fc_dim, 1, **kw)
-        self.fc1 = ConvLayer("bbox.fc1", in_features, fc_dim, 1, **kw)
+        # registration = backward completion order: the FC trunk (fc_out first), then the tower
+        fcs = [dict(name="bbox.fc%d" % (i + 1), cin=fc_dim if i else in_features, cout=fc_dim, k=1, split=i == 0)
+               for i in range(self.num_fcs)]
+        fcs.append(dict(name="bbox.fc_out", cin=fc_dim, cout=self.ld, k=1, init_std=0.01,
+                        cout_real=num_classes + self.reg_dim, relu=False))
+        self.fcs = LayerChain(fcs, **kw)
+        C = self.conv_dim
+        self.tower = LayerChain([dict(name="bbox.conv%d" % i, cin=C, cout=C, k=3) for i in range(self.num_convs)],
+                                norm=self.norm, gn_groups=self.gn_groups, **kw)
+        self.tower_in = (7, 7, C) if self.num_convs else (1, 1, in_features)
+        self.convs, self.norms = self.tower.convs, self.tower.norms
+        self.fc1, self.fc_out = self.fcs.convs[0], self.fcs.convs[-1]
+        if self.num_fcs == 2:
+            self.fc2 = self.fcs.convs[1]
         # checkpoint layout (CheckpointMixin._to_mx): fully connected layers are stored 2-D; fc1's input is the pooled
         # [7,7,C] block flattened (H, W, C) here and (C, H, W) in an MXNet FullyConnected after a Flatten of NCHW
         pooled = 7
         self.fc1.fc_in_hwc = (pooled, pooled, in_features // (pooled * pooled)) if in_features % (pooled * pooled) == 0 else ()
-        self.fc2.fc_in_hwc = ()
+        for l in self.fcs.convs[1:]:
+            l.fc_in_hwc = ()
+        self.R, self.fg_fraction, self.fg_thresh, self.bg_hi, self.bg_lo = rois_per_image, fg_fraction, fg_thresh, bg_hi, bg_lo
+        self.stds, self.sigma, self.seed, self.device = stds, sigma, seed, device
+        self.in_features, self.fc_dim = in_features, fc_dim
+        self.bufs, self._buf = buf_cache(device)
 
     def layers(self):
-        return [self.fc_out, self.fc2, self.fc1]
+        return self.fcs.layers() + self.tower.layers()
 
     def norm_layers(self):
-        return []
-
-    def _buf(self, key, shape, dtype=torch.bfloat16, zero=False):
-        return cached_buf(self.bufs, key, shape, dtype, self.device, zero)
+        return self.tower.norm_layers()
 
     def plan(self, N):
         R = N * self.R
-        self.fc1.plan((R, 1, 1, self.in_features))
-        self.fc2.plan((R, 1, 1, self.fc_dim))
-        self.fc_out.plan((R, 1, 1, self.fc_dim))
+        self.tower.plan((R,) + self.tower_in)
+        self.fcs.plan((R, 1, 1, self.in_features))
         self.loss = torch.zeros((2,), dtype=torch.float32, device=self.device)
         self.loss_ws = L_.loss_workspace(R, self.device)
 
@@ -122,19 +123,9 @@ class BBoxHead:
 
     def forward(self, pooled):
         R = pooled.shape[0]
-        self.x = pooled.view(R, 1, 1, -1)
-        # fc1 is 196 K-steps on 16 x 16 tiles of 64 x 64: one latency-bound wave per SIMD on its own (118 us in the step
-        # while nothing else runs). Split four ways the grid fills the chip; the fold is deterministic (split order).
-        ks = self.fc1_ksplit if (R * self.fc_dim) % (64 * 64 * 8) == 0 and R % 64 == 0 else 1
-        if ks > 1:
-            need = 4 * ks * R * self.fc_dim
-            ws = self._buf("fc1_ws", (need,), dtype=torch.uint8)
-            self.h1 = dense.conv2d_forward_splitk(self.x, self.fc1.w_bf16, self.fc1.bias_f32, None, True, ks,
-                                                  self._buf("h1", (R, 1, 1, self.fc_dim)), ws)
-        else:
-            self.h1 = self.fc1.forward(self.x, relu=True, out=self._buf("h1", (R, 1, 1, self.fc_dim)))
-        self.h2 = self.fc2.forward(self.h1, relu=True, out=self._buf("h2", (R, 1, 1, self.fc_dim)))
-        self.o = self.fc_out.forward(self.h2, out=self._buf("o", (R, 1, 1, self.ld)))
+        self.x = self.tower.forward(pooled.view((R,) + self.tower_in), self._buf).view(R, 1, 1, -1)
+        self.o = self.fcs.forward(self.x, self._buf)
+        self.acts, self.h1 = self.tower.acts, self.fcs.acts[1]
         return self.o
 
     def loss_and_grad(self, loss_scale=1.0):
@@ -152,90 +143,18 @@ class BBoxHead:
         return self.loss
 
     def backward(self):
-        R = self.o.shape[0]
-        self.fc_out.backward_weight(self.h2, self.go)
-        d_h2 = self.fc_out.backward_data(self.go, self.h2.shape, relu_mask=self.h2, out=self._buf("dh2", self.h2.shape))
-        self.fc2.backward_weight(self.h1, d_h2)
-        d_h1 = self.fc2.backward_data(d_h2, self.h1.shape, relu_mask=self.h1, out=self._buf("dh1", self.h1.shape))
-        self.fc1.backward_weight(self.x, d_h1)
-        d_x = self.fc1.backward_data(d_h1, self.x.shape, out=self._buf("dx", self.x.shape))
-        return d_x
+        """Returns d(loss)/d(pooled), in the tower's input shape."""
+        m = self.tower.out_mask           # fc1's data gradient applies the last conv's ReLU
+        g = self.fcs.backward(self.go, self._buf, first_mask=None if m is None else m.view(self.x.shape))
+        return self.tower.backward(g.view(self.tower.acts[-1].shape), self._buf)
 
 
 class ConvFCBBoxHead(BBoxHead):
     """4conv1fc. norm = "gn": every conv is bias-free and followed by GroupNorm with the ReLU fused into the GN kernel, so
     the conv's data gradient takes no ReLU mask (the GN backward applies it)."""
+    num_fcs = 1
 
     def __init__(self, in_features, arena, ws, device, gen, num_convs=4, conv_dim=256, norm="none", gn_groups=32, **kw):
         self.num_convs, self.conv_dim, self.norm, self.gn_groups = num_convs, conv_dim, norm, gn_groups
         assert in_features == 7 * 7 * conv_dim
         super().__init__(in_features, arena, ws, device, gen, **kw)
-
-    def _build_trunk(self, in_features, fc_dim, kw):
-        C = self.conv_dim
-        self.fc1 = ConvLayer("bbox.fc1", in_features, fc_dim, 1, **kw)
-        self.fc1.fc_in_hwc = (7, 7, C)
-        gn = self.norm == "gn"
-        self.convs, self.norms = [None] * self.num_convs, [None] * self.num_convs
-        for i in reversed(range(self.num_convs)):     # backward completion order: GN i, then conv i
-            if gn:
-                self.norms[i] = GroupNormLayer("bbox.conv%d_gn" % i, C, self.gn_groups, kw["arena"], kw["device"])
-            self.convs[i] = ConvLayer("bbox.conv%d" % i, C, C, 3, bias=not gn, **kw)
-
-    def layers(self):
-        return [self.fc_out, self.fc1] + list(reversed(self.convs))
-
-    def norm_layers(self):
-        return [n for n in reversed(self.norms) if n is not None]
-
-    def plan(self, N):
-        R = N * self.R
-        shp = (R, 7, 7, self.conv_dim)
-        for c, n in zip(self.convs, self.norms):
-            c.plan(shp)
-            if n is not None:
-                n.plan(shp)
-        self.fc1.plan((R, 1, 1, self.in_features))
-        self.fc_out.plan((R, 1, 1, self.fc_dim))
-        self.loss = torch.zeros((2,), dtype=torch.float32, device=self.device)
-        self.loss_ws = L_.loss_workspace(R, self.device)
-
-    def forward(self, pooled):
-        R = pooled.shape[0]
-        x = pooled.view(R, 7, 7, self.conv_dim)
-        self.acts = [x]
-        for i, (c, n) in enumerate(zip(self.convs, self.norms)):
-            if n is None:
-                x = c.forward(x, relu=True, out=self._buf("a%d" % i, x.shape))
-            else:
-                x = n.forward(c.forward(x, out=self._buf("c%d" % i, x.shape)), relu=True, out=self._buf("a%d" % i, x.shape))
-            self.acts.append(x)
-        self.x = x.view(R, 1, 1, -1)
-        ks = self.fc1_ksplit if (R * self.fc_dim) % (64 * 64 * 8) == 0 and R % 64 == 0 else 1
-        if ks > 1:
-            ws = self._buf("fc1_ws", (4 * ks * R * self.fc_dim,), dtype=torch.uint8)
-            self.h1 = dense.conv2d_forward_splitk(self.x, self.fc1.w_bf16, self.fc1.bias_f32, None, True, ks,
-                                                  self._buf("h1", (R, 1, 1, self.fc_dim)), ws)
-        else:
-            self.h1 = self.fc1.forward(self.x, relu=True, out=self._buf("h1", (R, 1, 1, self.fc_dim)))
-        self.o = self.fc_out.forward(self.h1, out=self._buf("o", (R, 1, 1, self.ld)))
-        return self.o
-
-    def backward(self):
-        """Returns d(loss)/d(pooled) [R,7,7,C]."""
-        self.fc_out.backward_weight(self.h1, self.go)
-        d_h1 = self.fc_out.backward_data(self.go, self.h1.shape, relu_mask=self.h1, out=self._buf("dh1", self.h1.shape))
-        self.fc1.backward_weight(self.x, d_h1)
-        last = self.acts[-1]
-        gn = self.norm == "gn"
-        # without GN the last conv's ReLU is applied here; with GN the GN backward applies it
-        g = self.fc1.backward_data(d_h1, self.x.shape, relu_mask=None if gn else last.view(self.x.shape),
-                                   out=self._buf("dx", self.x.shape)).view(last.shape)
-        for i in reversed(range(self.num_convs)):
-            xin = self.acts[i]
-            if gn:
-                g = self.norms[i].backward(g, out=self._buf("dc%d" % i, xin.shape))
-            self.convs[i].backward_weight(xin, g)
-            g = self.convs[i].backward_data(g, xin.shape, relu_mask=xin if (i > 0 and not gn) else None,
-                                            out=self._buf("g%d" % i, xin.shape))
-        return g

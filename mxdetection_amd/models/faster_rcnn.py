@@ -35,6 +35,12 @@ def check_head_options(bbox_head, head_norm, gn_groups, with_mask):
             raise ValueError("gn_groups = %r does not divide 256 channels into groups of a multiple of 8" % (g,))
 
 
+def check_loss_weight(name, w):
+    """A branch's loss weight: a positive finite number, not a bool."""
+    if not (isinstance(w, (int, float)) and not isinstance(w, bool) and 0.0 < float(w) < float("inf")):
+        raise ValueError("%s must be a positive finite number (got %r)" % (name, w))
+
+
 class FasterRCNN(DetectorBase):
     def __init__(self, device="cuda", depth=50, num_classes=81, seed=7, rpn_seed=99, rois_per_image=512,
                  pre_nms_top_n=2000, post_nms_top_n=2000, with_mask=False, dcn_stages=(), dcn_modulated=True,
@@ -66,17 +72,14 @@ class FasterRCNN(DetectorBase):
         check_head_options(bbox_head, head_norm, gn_groups, with_mask)
         if mask_iou and not with_mask:
             raise ValueError("mask_iou needs the mask branch (with_mask=True): the MaskIoU head scores the mask head's output")
-        if mask_iou and not (isinstance(mask_iou_weight, (int, float)) and not isinstance(mask_iou_weight, bool)
-                             and 0.0 < float(mask_iou_weight) < float("inf")):
-            raise ValueError("mask_iou_weight must be a positive finite number (got %r)" % (mask_iou_weight,))
+        if mask_iou:
+            check_loss_weight("mask_iou_weight", mask_iou_weight)
         if not isinstance(with_keypoints, (bool, int)):
             raise ValueError("with_keypoints must be a bool (got %r)" % (with_keypoints,))
         if with_keypoints:
             if not isinstance(num_keypoints, int) or isinstance(num_keypoints, bool) or not 1 <= num_keypoints <= 32:
                 raise ValueError("num_keypoints must be an integer in [1, 32] (got %r)" % (num_keypoints,))
-            if not (isinstance(keypoint_weight, (int, float)) and not isinstance(keypoint_weight, bool)
-                    and 0.0 < float(keypoint_weight) < float("inf")):
-                raise ValueError("keypoint_weight must be a positive finite number (got %r)" % (keypoint_weight,))
+            check_loss_weight("keypoint_weight", keypoint_weight)
         check_reg_loss(reg_loss, reg_loss_weight)
         if not isinstance(ohem, (bool, int)):
             raise ValueError("ohem must be a bool (got %r)" % (ohem,))

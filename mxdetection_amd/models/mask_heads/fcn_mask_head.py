@@ -9,10 +9,24 @@ import torch
 
 from ...core import mask as M_
 from ...ops import dense
-from ..utils.layers import ConvLayer, GroupNormLayer, cached_buf
+from ..utils.layers import ConvLayer, LayerChain, buf_cache
+
+
+def select_rois(head, bbox_head):
+    """The rois a mask-branch head (mask, keypoint) trains on. The box head writes its sampled rois foreground first, so
+    the first `Rimg` slots of every image hold all foreground rois (<= 25% of 512 = 128) followed by background /
+    padding, which the targets mark as ignored."""
+    N = bbox_head.rois.shape[0]
+    k = head.Rimg
+    head.rois = bbox_head.rois[:, :k].reshape(N * k, 5).contiguous()
+    head.matched = bbox_head.matched[:, :k].reshape(-1).contiguous()
+    head.roi_labels = bbox_head.labels[:, :k].reshape(-1).contiguous()
+    return head.rois
 
 
 class FCNMaskHead:
+    select_rois = select_rois
+
     def __init__(self, channels, arena, ws, device, gen, num_classes=81, num_convs=4, size=28, rois_per_image=128,
                  norm="none", gn_groups=32):
         """norm = "gn": every conv is bias-free and followed by GroupNorm + ReLU (fused in the GN kernel); deconv and
@@ -24,44 +38,24 @@ class FCNMaskHead:
         # registration = backward completion order
         self.logits = ConvLayer("mask.logits", channels, self.cpad, 1, init_std=0.001, cout_real=num_classes - 1, **kw)
         self.deconv = ConvLayer("mask.deconv", channels, 4 * channels, 1, **kw)   # 2x2/2 deconv as 1x1 conv + shuffle
-        gn = norm == "gn"
-        self.convs, self.norms = [None] * num_convs, [None] * num_convs
-        for i in reversed(range(num_convs)):
-            if gn:
-                self.norms[i] = GroupNormLayer("mask.conv%d_gn" % i, channels, gn_groups, arena, device)
-            self.convs[i] = ConvLayer("mask.conv%d" % i, channels, channels, 3, bias=not gn, **kw)
-        self.bufs = {}
+        self.tower = LayerChain([dict(name="mask.conv%d" % i, cin=channels, cout=channels, k=3) for i in range(num_convs)],
+                                norm=norm, gn_groups=gn_groups, **kw)
+        self.convs, self.norms = self.tower.convs, self.tower.norms
+        self.bufs, self._buf = buf_cache(device)
 
     def layers(self):
-        return [self.logits, self.deconv] + list(reversed(self.convs))
+        return [self.logits, self.deconv] + self.tower.layers()
 
     def norm_layers(self):
-        return [n for n in reversed(self.norms) if n is not None]
-
-    def _buf(self, key, shape, dtype=torch.bfloat16, zero=False):
-        return cached_buf(self.bufs, key, shape, dtype, self.device, zero)
+        return self.tower.norm_layers()
 
     def plan(self, N):
         R = N * self.Rimg
         h = self.S // 2
-        for c, n in zip(self.convs, self.norms):
-            c.plan((R, h, h, self.C))
-            if n is not None:
-                n.plan((R, h, h, self.C))
-        self.deconv.plan((R, h, h, self.C))
+        self.deconv.plan(self.tower.plan((R, h, h, self.C)))
         self.logits.plan((R, self.S, self.S, self.C))
         self.loss = torch.zeros((1,), dtype=torch.float32, device=self.device)
         self.loss_ws = M_.mask_loss_workspace(R, self.S, self.device)
-
-    def select_rois(self, bbox_head):
-        """The box head writes its sampled rois foreground first, so the first `Rimg` slots of every image hold all
-        foreground rois (<= 25% of 512 = 128) followed by background / padding, which the targets mark as ignored."""
-        N = bbox_head.rois.shape[0]
-        k = self.Rimg
-        self.rois = bbox_head.rois[:, :k].reshape(N * k, 5).contiguous()
-        self.matched = bbox_head.matched[:, :k].reshape(-1).contiguous()
-        self.roi_labels = bbox_head.labels[:, :k].reshape(-1).contiguous()
-        return self.rois
 
     def targets(self, gt_masks):
         R = self.rois.shape[0]
@@ -70,14 +64,8 @@ class FCNMaskHead:
 
     def forward(self, pooled):
         """pooled bf16 [R,14,14,C]"""
-        x = pooled
-        self.acts = [x]
-        for i, (c, n) in enumerate(zip(self.convs, self.norms)):
-            if n is None:
-                x = c.forward(x, relu=True, out=self._buf("a%d" % i, x.shape))
-            else:
-                x = n.forward(c.forward(x, out=self._buf("c%d" % i, x.shape)), relu=True, out=self._buf("a%d" % i, x.shape))
-            self.acts.append(x)
+        x = self.tower.forward(pooled, self._buf)
+        self.acts = self.tower.acts
         R, h, w, _ = x.shape
         self.d4 = self.deconv.forward(x, relu=True, out=self._buf("d4", (R, h, w, 4 * self.C)))
         self.up = dense.pixel_shuffle2(self.d4, self._buf("up", (R, 2 * h, 2 * w, self.C)))
@@ -96,13 +84,5 @@ class FCNMaskHead:
         d_d4 = dense.pixel_shuffle2_inv_relu(d_up, self.d4, self._buf("d_d4", self.d4.shape))
         x = self.acts[-1]
         self.deconv.backward_weight(x, d_d4)
-        gn = self.norm == "gn"       # the GN backward applies its fused ReLU's mask itself
-        g = self.deconv.backward_data(d_d4, x.shape, relu_mask=None if gn else x, out=self._buf("g%d" % len(self.convs), x.shape))
-        for i in reversed(range(len(self.convs))):
-            xin = self.acts[i]
-            if gn:
-                g = self.norms[i].backward(g, out=self._buf("dc%d" % i, xin.shape))
-            self.convs[i].backward_weight(xin, g)
-            g = self.convs[i].backward_data(g, xin.shape, relu_mask=xin if (i > 0 and not gn) else None,
-                                            out=self._buf("g%d" % i, xin.shape))
-        return g
+        g = self.deconv.backward_data(d_d4, x.shape, relu_mask=self.tower.out_mask, out=self._buf("d_tower", x.shape))
+        return self.tower.backward(g, self._buf)

@@ -12,10 +12,13 @@ import torch
 
 from ...core import mask as M_
 from ...ops import dense
-from ..utils.layers import ConvLayer, cached_buf
+from ..utils.layers import ConvLayer, LayerChain, buf_cache
+from .fcn_mask_head import select_rois
 
 
 class KeypointHead:
+    select_rois = select_rois      # the mask head's rule: background / padding rows are marked as not trained
+
     def __init__(self, channels, arena, ws, device, gen, num_keypoints=17, num_convs=8, conv_channels=512, size=28,
                  rois_per_image=128, weight=1.0):
         kw = dict(arena=arena, ws=ws, device=device, gen=gen)
@@ -28,38 +31,23 @@ class KeypointHead:
         # output channel (dy*2+dx)*Kpad + c: the alignment channels c >= K start at zero and, with zero gradients from the
         # loss kernel, stay there
         self.deconv._w0.view(4, self.kpad, -1)[:, self.K:] = 0
-        self.convs = [None] * num_convs
-        for i in reversed(range(num_convs)):
-            self.convs[i] = ConvLayer("kpt.conv%d" % i, channels if i == 0 else conv_channels, conv_channels, 3, **kw)
-        self.bufs = {}
+        self.tower = LayerChain([dict(name="kpt.conv%d" % i, cin=conv_channels if i else channels, cout=conv_channels, k=3)
+                                 for i in range(num_convs)], **kw)
+        self.convs = self.tower.convs
+        self.bufs, self._buf = buf_cache(device)
 
     def layers(self):
-        return [self.deconv] + list(reversed(self.convs))
+        return [self.deconv] + self.tower.layers()
 
     def norm_layers(self):
         return []
 
-    def _buf(self, key, shape, dtype=torch.bfloat16, zero=False):
-        return cached_buf(self.bufs, key, shape, dtype, self.device, zero)
-
     def plan(self, N):
         R = N * self.Rimg
         h = self.S // 2
-        for i, c in enumerate(self.convs):
-            c.plan((R, h, h, self.C if i == 0 else self.Cc))
-        self.deconv.plan((R, h, h, self.Cc))
+        self.deconv.plan(self.tower.plan((R, h, h, self.C)))
         self.loss = torch.zeros((1,), dtype=torch.float32, device=self.device)
         self.loss_ws = M_.keypoint_loss_workspace(R, self.device)
-
-    def select_rois(self, bbox_head):
-        """The mask head's rule: the box head writes its sampled rois foreground first, so the first `Rimg` slots of every
-        image hold all foreground rois followed by background / padding, which the targets mark as not trained."""
-        N = bbox_head.rois.shape[0]
-        k = self.Rimg
-        self.rois = bbox_head.rois[:, :k].reshape(N * k, 5).contiguous()
-        self.matched = bbox_head.matched[:, :k].reshape(-1).contiguous()
-        self.roi_labels = bbox_head.labels[:, :k].reshape(-1).contiguous()
-        return self.rois
 
     def targets(self, gt_keypoints):
         """gt_keypoints f32 [N,G,K,3] -> the heatmap targets int32 [R,K] of the selected rois."""
@@ -71,11 +59,8 @@ class KeypointHead:
 
     def forward(self, pooled):
         """pooled bf16 [R,14,14,C] -> logits bf16 [R,28,28,Kpad]"""
-        x = pooled
-        self.acts = [x]
-        for i, c in enumerate(self.convs):
-            x = c.forward(x, relu=True, out=self._buf("a%d" % i, c.out_shape(x.shape)))
-            self.acts.append(x)
+        x = self.tower.forward(pooled, self._buf)
+        self.acts = self.tower.acts
         R, h, w, _ = x.shape
         self.d4 = self.deconv.forward(x, out=self._buf("d4", (R, h, w, 4 * self.kpad)))
         self.o = dense.pixel_shuffle2(self.d4, self._buf("o", (R, 2 * h, 2 * w, self.kpad)))
@@ -91,10 +76,5 @@ class KeypointHead:
         d_d4 = dense.pixel_shuffle2(self.go, self._buf("d_d4", self.d4.shape), inverse=True)      # no ReLU behind the deconv
         x = self.acts[-1]
         self.deconv.backward_weight(x, d_d4)
-        g = self.deconv.backward_data(d_d4, x.shape, relu_mask=x, out=self._buf("g%d" % len(self.convs), x.shape))
-        for i in reversed(range(len(self.convs))):
-            xin = self.acts[i]
-            self.convs[i].backward_weight(xin, g)
-            g = self.convs[i].backward_data(g, xin.shape, relu_mask=xin if i > 0 else None,
-                                            out=self._buf("g%d" % i, xin.shape))
-        return g
+        g = self.deconv.backward_data(d_d4, x.shape, relu_mask=self.tower.out_mask, out=self._buf("d_tower", x.shape))
+        return self.tower.backward(g, self._buf)

@@ -8,13 +8,10 @@ FC 1024 + ReLU -> FC num_classes-1 (padded to 128 columns); bias everywhere, no 
 the rows with a positive target (core.mask.maskiou_target / maskiou_loss). The mask channel is a constant in the
 backward pass: the head's gradient reaches the mask RoI features only.
 """
-import os
-
 import torch
 
 from ...core import mask as M_
-from ...ops import dense
-from ..utils.layers import ConvLayer, cached_buf
+from ..utils.layers import LayerChain, buf_cache
 
 
 class MaskIoUHead:
@@ -32,41 +29,33 @@ class MaskIoUHead:
         # the output layer starts as small as mask.logits does: the loss is an unbounded L2, and a prediction far from
         # [0, 1] at the start sends a large gradient through the shared RoI features into the FPN (with std 0.01 on a
         # randomly initialised backbone the whole step diverged within three iterations at lr 0.002)
-        self.fc_out = ConvLayer("maskiou.fc_out", fc_dim, self.ld, 1, init_std=0.001, cout_real=num_classes - 1, **kw)
-        self.fc2 = ConvLayer("maskiou.fc2", fc_dim, fc_dim, 1, **kw)
-        self.fc1 = ConvLayer("maskiou.fc1", self.in_features, fc_dim, 1, **kw)
+        fcs = [dict(name="maskiou.fc1", cin=self.in_features, cout=fc_dim, k=1, split=True),    # the box heads' split rule
+               dict(name="maskiou.fc2", cin=fc_dim, cout=fc_dim, k=1),
+               dict(name="maskiou.fc_out", cin=fc_dim, cout=self.ld, k=1, init_std=0.001, cout_real=num_classes - 1,
+                    relu=False)]
+        self.fcs = LayerChain(fcs, **kw)
+        self.fc1, self.fc2, self.fc_out = self.fcs.convs
         self.fc1.fc_in_hwc = (h, h, channels)       # checkpoint layout, as bbox.fc1
         self.fc2.fc_in_hwc = ()
         self.fc_out.fc_in_hwc = ()
-        self.convs = [None] * num_convs
-        for i in reversed(range(num_convs)):
-            last = i == num_convs - 1
-            self.convs[i] = ConvLayer("maskiou.conv%d" % i, self.cin if i == 0 else channels, channels, 3,
-                                      stride=2 if last else 1, **kw)
+        self.tower = LayerChain([dict(name="maskiou.conv%d" % i, cin=channels if i else self.cin, cout=channels, k=3,
+                                      stride=2 if i == num_convs - 1 else 1) for i in range(num_convs)], **kw)
+        self.convs = self.tower.convs
         # the alignment channels behind the mask channel see zero activations: zero filter entries stay zero
         self.convs[0]._w0[..., channels + 1:] = 0
-        self.fc1_ksplit = int(os.environ.get("MXDET_TUNE_FC1_KSPLIT", "4"))
-        self.bufs = {}
+        self.bufs, self._buf = buf_cache(device)
 
     def layers(self):
-        return [self.fc_out, self.fc2, self.fc1] + list(reversed(self.convs))
+        return self.fcs.layers() + self.tower.layers()
 
     def norm_layers(self):
         return []
 
-    def _buf(self, key, shape, dtype=torch.bfloat16, zero=False):
-        return cached_buf(self.bufs, key, shape, dtype, self.device, zero)
-
     def plan(self, N, g_max=None):
         R = N * self.Rimg
         h = self.S // 2
-        shp = (R, h, h, self.cin)
-        for c in self.convs:
-            c.plan(shp)
-            shp = c.out_shape(shp)
-        self.fc1.plan((R, 1, 1, self.in_features))
-        self.fc2.plan((R, 1, 1, self.fc_dim))
-        self.fc_out.plan((R, 1, 1, self.fc_dim))
+        self.tower.plan((R, h, h, self.cin))
+        self.fcs.plan((R, 1, 1, self.in_features))
         self.loss = torch.zeros((1,), dtype=torch.float32, device=self.device)
         if g_max is not None:      # the masks hold at most as many instances per image as the boxes
             self._target_ws(N, g_max)
@@ -86,21 +75,9 @@ class MaskIoUHead:
         R, h = mpooled.shape[0], mpooled.shape[1]
         x = M_.maskiou_input(mpooled, mask_logits, cls, out=self._buf("x", (R, h, h, self.cin)))
         self.cls = cls
-        self.acts = [x]
-        for i, c in enumerate(self.convs):
-            x = c.forward(x, relu=True, out=self._buf("a%d" % i, c.out_shape(x.shape)))
-            self.acts.append(x)
-        self.x = x.view(R, 1, 1, -1)
-        # fc1 under the box head's split-K rule (BBoxHead.forward)
-        ks = self.fc1_ksplit if (R * self.fc_dim) % (64 * 64 * 8) == 0 and R % 64 == 0 else 1
-        if ks > 1:
-            ws = self._buf("fc1_ws", (4 * ks * R * self.fc_dim,), dtype=torch.uint8)
-            self.h1 = dense.conv2d_forward_splitk(self.x, self.fc1.w_bf16, self.fc1.bias_f32, None, True, ks,
-                                                  self._buf("h1", (R, 1, 1, self.fc_dim)), ws)
-        else:
-            self.h1 = self.fc1.forward(self.x, relu=True, out=self._buf("h1", (R, 1, 1, self.fc_dim)))
-        self.h2 = self.fc2.forward(self.h1, relu=True, out=self._buf("h2", (R, 1, 1, self.fc_dim)))
-        self.o = self.fc_out.forward(self.h2, out=self._buf("o", (R, 1, 1, self.ld)))
+        self.x = self.tower.forward(x, self._buf).view(R, 1, 1, -1)
+        self.o = self.fcs.forward(self.x, self._buf)
+        self.acts, self.h1 = self.tower.acts, self.fcs.acts[1]
         return self.o
 
     def targets(self, mask_head, gt_boxes, gt_masks):
@@ -122,17 +99,5 @@ class MaskIoUHead:
     def backward(self):
         """Returns d(loss)/d(head input) bf16 [R,14,14,320]; channels [0,C) belong to the mask RoI features
         (core.mask.maskiou_input_bwd), the rest (mask channel, alignment padding) is dropped by the caller."""
-        self.fc_out.backward_weight(self.h2, self.go)
-        d_h2 = self.fc_out.backward_data(self.go, self.h2.shape, relu_mask=self.h2, out=self._buf("dh2", self.h2.shape))
-        self.fc2.backward_weight(self.h1, d_h2)
-        d_h1 = self.fc2.backward_data(d_h2, self.h1.shape, relu_mask=self.h1, out=self._buf("dh1", self.h1.shape))
-        self.fc1.backward_weight(self.x, d_h1)
-        last = self.acts[-1]
-        g = self.fc1.backward_data(d_h1, self.x.shape, relu_mask=last.view(self.x.shape),
-                                   out=self._buf("dx", self.x.shape)).view(last.shape)
-        for i in reversed(range(len(self.convs))):
-            xin = self.acts[i]
-            self.convs[i].backward_weight(xin, g)
-            g = self.convs[i].backward_data(g, xin.shape, relu_mask=xin if i > 0 else None,
-                                            out=self._buf("g%d" % i, xin.shape))
-        return g
+        g = self.fcs.backward(self.go, self._buf, first_mask=self.tower.out_mask.view(self.x.shape))
+        return self.tower.backward(g.view(self.acts[-1].shape), self._buf)

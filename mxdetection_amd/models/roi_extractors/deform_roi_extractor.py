@@ -16,7 +16,7 @@ import torch
 from ...ops.deform_roi_pool import (dpool_backward_feat, dpool_backward_feat_workspace, dpool_backward_trans,
                                     dpool_forward)
 from ...ops.roi_align import fpn_level_map
-from ..utils.layers import ConvLayer, cached_buf
+from ..utils.layers import LayerChain, buf_cache
 
 
 class DeformRoIExtractor:
@@ -32,30 +32,26 @@ class DeformRoIExtractor:
         self.in_features = nb * channels
         # hidden FCs draw from a generator of their own: every parameter of the plain model keeps its random draw
         kw = dict(arena=arena, ws=ws, device=device, gen=torch.Generator().manual_seed(seed))
+
+        def branch(name, n, nreal):
+            """n FCs: fc_dim hidden with ReLU; the last has nreal outputs (padded to 64s), starts at zero, no ReLU."""
+            specs = [dict(name="bbox.%s%d" % (name, i + 1), cin=fc_dim if i else self.in_features, cout=fc_dim, k=1)
+                     for i in range(n)]
+            specs[-1].update(cout=(nreal + 63) // 64 * 64, cout_real=nreal, zero_init=True, relu=False)
+            return LayerChain(specs, **kw)
         # registration order == backward completion order: the last FCs' weight gradients are issued first
-        dims = [self.in_features] + [fc_dim] * (offset_fcs - 1)
-        self.offset_fc = []
-        for i in reversed(range(offset_fcs)):
-            last = i == offset_fcs - 1
-            cout = (2 * nb + 63) // 64 * 64 if last else fc_dim
-            self.offset_fc.insert(0, ConvLayer("bbox.offset_fc%d" % (i + 1), dims[i], cout, 1, zero_init=last,
-                                               cout_real=2 * nb if last else None, **kw))
-        self.mask_fc = []
-        if self.modulated:
-            self.mask_fc = [None, ConvLayer("bbox.mask_fc2", fc_dim, (nb + 63) // 64 * 64, 1, zero_init=True,
-                                            cout_real=nb, **kw)]
-            self.mask_fc[0] = ConvLayer("bbox.mask_fc1", self.in_features, fc_dim, 1, **kw)
+        self.offset_chain = branch("offset_fc", offset_fcs, 2 * nb)
+        self.mask_chain = branch("mask_fc", 2, nb) if self.modulated else None
+        self.offset_fc = self.offset_chain.convs
+        self.mask_fc = self.mask_chain.convs if self.modulated else []
         # checkpoint layout (CheckpointMixin._to_mx): 2-D FC weights, the pooled-input ones reordered from (H, W, C) to (C, H, W)
         for l in self.layers():
             l.fc_in_hwc = (self.pooled[0], self.pooled[1], channels) if l.cin == self.in_features else ()
-        self.bufs = {}
+        self.bufs, self._buf = buf_cache(device)
 
     def layers(self):
         """In registration (= backward completion) order."""
-        return list(reversed(self.offset_fc)) + list(reversed(self.mask_fc))
-
-    def _buf(self, key, shape, dtype=torch.bfloat16, zero=False):
-        return cached_buf(self.bufs, key, shape, dtype, self.device, zero)
+        return self.offset_chain.layers() + (self.mask_chain.layers() if self.modulated else [])
 
     def plan(self, R):
         for l in self.layers():
@@ -71,18 +67,8 @@ class DeformRoIExtractor:
         a = dict(pooled=self.pooled, sample_per_part=self.spp, trans_std=self.trans_std, lvl_min=self.lvl_min)
         self.x0 = dpool_forward(self.feats, self.scales, rois, self.levels, out=self._buf("x0", (R, PH, PW, Cc)), **a)
         h = self.x0.view(R, 1, 1, -1)
-        self.h_off = [h]
-        for i, l in enumerate(self.offset_fc):
-            last = i == len(self.offset_fc) - 1
-            h = l.forward(h, relu=not last, out=self._buf("off%d" % i, (R, 1, 1, l.cout)))
-            self.h_off.append(h)
-        self.trans = h.view(R, -1)
-        self.mask = None
-        if self.modulated:
-            self.h_mask = self.mask_fc[0].forward(self.x0.view(R, 1, 1, -1), relu=True,
-                                                  out=self._buf("mh", (R, 1, 1, self.mask_fc[0].cout)))
-            self.mask = self.mask_fc[1].forward(self.h_mask, out=self._buf("mlogit", (R, 1, 1, self.mask_fc[1].cout))
-                                                ).view(R, -1)
+        self.trans = self.offset_chain.forward(h, self._buf).view(R, -1)
+        self.mask = self.mask_chain.forward(h, self._buf).view(R, -1) if self.modulated else None
         return dpool_forward(self.feats, self.scales, rois, self.levels, trans=self.trans, mask=self.mask,
                              out=self._buf("x1", (R, PH, PW, Cc)), **a)
 
@@ -102,19 +88,9 @@ class DeformRoIExtractor:
         dpool_backward_feat(dP, self.scales, self.rois, self.levels, grad_out, self.trans, self.mask,
                             accumulate=accumulate, workspace=ws, **a)
         # 2. offset head backward -> d_x0
-        dy = d_trans.view(R, 1, 1, -1)
-        for i in reversed(range(len(self.offset_fc))):
-            l, x = self.offset_fc[i], self.h_off[i]
-            l.backward_weight(x, dy)
-            dy = l.backward_data(dy, x.shape, relu_mask=x if i > 0 else None, out=self._buf("doff%d" % i, x.shape))
-        d_x0 = dy
-        if self.modulated:
-            m1, m2 = self.mask_fc
-            dm = d_mask.view(R, 1, 1, -1)
-            m2.backward_weight(self.h_mask, dm)
-            dh = m2.backward_data(dm, self.h_mask.shape, relu_mask=self.h_mask, out=self._buf("dmh", self.h_mask.shape))
-            m1.backward_weight(self.h_off[0], dh)
-            m1.backward_data(dh, d_x0.shape, accumulate=True, out=d_x0)
+        d_x0 = self.offset_chain.backward(d_trans.view(R, 1, 1, -1), self._buf)
+        if self.modulated:      # the second branch on x0 adds its gradient
+            self.mask_chain.backward(d_mask.view(R, 1, 1, -1), self._buf, add_to=d_x0)
         # 3. pass-0 adjoint
         dpool_backward_feat(dP, self.scales, self.rois, self.levels, d_x0.view(self.x0.shape), accumulate=True,
                             workspace=ws, **a)

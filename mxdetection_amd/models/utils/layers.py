@@ -11,23 +11,31 @@ Design (MI355X-first, not MXNet's per-NDArray executor):
     construction; frozen layers (stem, C2) keep bf16 filters only.
 """
 import contextlib
+import functools
 import math
+import os
 
 import torch
 
 from ...ops import dense
 
 
-def cached_buf(bufs, key, shape, dtype, device, zero=False):
+def cached_buf(bufs, key, shape, dtype=torch.bfloat16, device=None, zero=False):
     """Activation / gradient buffer cache of a model part, keyed by (name, shape, dtype): a call at another shape
     (inference with 1000 rois per image after training with 512) gets buffers of its own and never frees the ones a
-    captured hipGraph holds by address."""
+    captured hipGraph holds by address. A head's `_buf` is this function bound to its `bufs` and device (buf_cache)."""
     k = (key, tuple(shape), dtype)
     b = bufs.get(k)
     if b is None:
         b = (torch.zeros if zero else torch.empty)(tuple(shape), dtype=dtype, device=device)
         bufs[k] = b
     return b
+
+
+def buf_cache(device):
+    """(bufs, _buf) of a model part: _buf(key, shape, dtype=bf16, zero=False) is cached_buf on `bufs`."""
+    bufs = {}
+    return bufs, functools.partial(cached_buf, bufs, device=device)
 
 
 class Workspace:
@@ -302,6 +310,108 @@ class GroupNormLayer:
                                       out=out, workspace=self.plan(self.x.shape)[3])
 
 
+def fc_ksplit():
+    """MXDET_TUNE_FC1_KSPLIT (read when a head is built, never in a step): the split of fc_forward, 1 = never split."""
+    return int(os.environ.get("MXDET_TUNE_FC1_KSPLIT", "4"))
+
+
+def fc_forward(fc, x, ksplit, buf, relu=True, out=None):
+    """Forward of an FC (1x1 ConvLayer on [R,1,1,C]) whose reduction may be split `ksplit` ways.
+
+    The fc1 of a box head is 196 K-steps on 16 x 16 tiles of 64 x 64: one latency-bound wave per SIMD on its own (118 us
+    in the step while nothing else runs). Split four ways the grid fills the chip; the fold is deterministic (split
+    order). The split kernel takes whole 64-row tiles only; every other shape runs the plain kernel."""
+    R = x.shape[0]
+    if ksplit > 1 and (R * fc.cout) % (64 * 64 * 8) == 0 and R % 64 == 0:
+        ws = buf(("splitk", fc.name), (4 * ksplit * R * fc.cout,), dtype=torch.uint8)
+        return dense.conv2d_forward_splitk(x, fc.w_bf16, fc.bias_f32, None, relu, ksplit, out, ws)
+    return fc.forward(x, relu=relu, out=out)
+
+
+class LayerChain:
+    """A sequence of ConvLayers, each followed by an optional GroupNorm and an optional ReLU: the conv towers and FC trunks
+    of the RoI heads (an FC is a 1x1 conv on [R,1,1,C]; the `view` between a tower and an FC stays with the head).
+
+    `specs`: one dict per layer in forward order -- ConvLayer's name, cin, cout, k and optionally stride, init_std,
+    cout_real, zero_init, plus two keys of the chain: `relu` (default True) and `split` (default False: True sends the
+    layer's forward through fc_forward). norm = "gn": every conv is bias-free and followed by GroupNorm `<name>_gn`, into
+    whose kernel the ReLU is fused.
+
+    The chain fixes the two orders that nothing downstream can check:
+      * registration = backward completion order: for i descending, GN i, then conv i -- so are the generator's draws;
+      * backward, per layer from last to first: GN backward, weight gradient, data gradient. The data gradient of layer
+        i applies the ReLU that produced its input acts[i], i.e. layer i-1's; with GN none does (the GN backward applies its
+        own); layer 0's input belongs to the caller, who names its mask (`first_mask`), as `out_mask` names this chain's
+        for whoever computes the gradient of its output.
+    Buffers come from the owner's `_buf`, keyed by layer name."""
+
+    def __init__(self, specs, arena, ws, device, gen, norm="none", gn_groups=32):
+        n = len(specs)
+        self.gn = norm == "gn"
+        self.relu = [s.get("relu", True) for s in specs]
+        self.split = [s.get("split", False) for s in specs]
+        self.ksplit = fc_ksplit() if any(self.split) else 1
+        self.convs, self.norms = [None] * n, [None] * n
+        for i in reversed(range(n)):
+            s = {k: v for k, v in specs[i].items() if k not in ("relu", "split")}
+            if self.gn:
+                self.norms[i] = GroupNormLayer(s["name"] + "_gn", s["cout"], gn_groups, arena, device)
+            self.convs[i] = ConvLayer(bias=not self.gn, arena=arena, ws=ws, device=device, gen=gen, **s)
+        self.acts = None
+
+    def layers(self):
+        return list(reversed(self.convs))
+
+    def norm_layers(self):
+        return [n for n in reversed(self.norms) if n is not None]
+
+    def plan(self, x_shape):
+        for c, n in zip(self.convs, self.norms):
+            c.plan(x_shape)
+            x_shape = c.out_shape(x_shape)
+            if n is not None:
+                n.plan(x_shape)
+        return x_shape
+
+    def forward(self, x, buf):
+        """Keeps acts = [x, output of layer 0, ...]; returns the last."""
+        self.acts = [x]
+        for c, n, relu, split in zip(self.convs, self.norms, self.relu, self.split):
+            out = buf(("a", c.name), c.out_shape(x.shape))
+            if n is not None:
+                x = n.forward(c.forward(x, out=buf(("c", c.name), out.shape)), relu=relu, out=out)
+            elif split:
+                x = fc_forward(c, x, self.ksplit, buf, relu=relu, out=out)
+            else:
+                x = c.forward(x, relu=relu, out=out)
+            self.acts.append(x)
+        return x
+
+    def _mask(self, i):
+        return self.acts[i] if i > 0 and self.relu[i - 1] and not self.gn else None
+
+    @property
+    def out_mask(self):
+        """The ReLU mask that the data gradient arriving at this chain's output has to apply (None: no ReLU there, or GN's
+        backward applies it)."""
+        return self._mask(len(self.convs))
+
+    def backward(self, g, buf, first_mask=None, add_to=None):
+        """g: the gradient of the output, already masked by out_mask. Returns the gradient of the input -- added into
+        `add_to` if given (a second branch on the same input), else in a buffer of the chain's."""
+        for i in reversed(range(len(self.convs))):
+            c, n, x = self.convs[i], self.norms[i], self.acts[i]
+            if n is not None:
+                g = n.backward(g, out=buf(("dn", c.name), g.shape))
+            c.backward_weight(x, g)
+            mask = self._mask(i) if i > 0 else first_mask
+            if i == 0 and add_to is not None:
+                g = c.backward_data(g, x.shape, relu_mask=mask, accumulate=True, out=add_to)
+            else:
+                g = c.backward_data(g, x.shape, relu_mask=mask, out=buf(("g", c.name), x.shape))
+        return g
+
+
 class DeformConvLayer:
     """3x3 deformable convolution (DCN v1, or v2 with `modulated`), MXNet role contrib.DeformableConvolution; the
     drop-in for a bottleneck's conv2 ("Deformable convolution").
@@ -332,15 +442,12 @@ class DeformConvLayer:
                                 device=device, gen=gen, zero_init=True, cout_real=nreal)
         self.ws = ws
         self.device = device
-        self.bufs = {}
+        self.bufs, self._buf = buf_cache(device)
         self.x = self.off = self.col = None
 
     def layers(self):
         """Registration (= backward completion) order: the deformable filter's gradient is final first."""
         return [self.conv, self.offset]
-
-    def _buf(self, key, shape, dtype=torch.bfloat16):
-        return cached_buf(self.bufs, key, shape, dtype, self.device)
 
     def out_shape(self, x_shape):
         return self.offset.out_shape(x_shape)[:3] + (self.cout,)

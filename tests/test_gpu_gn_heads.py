@@ -1,4 +1,5 @@
-"""GroupNorm heads: the 4conv1fc box head and the GN mask head against a torch-CPU fp64 autograd restatement, and the
+"""GroupNorm heads: the 4conv1fc box head and the GN mask head (and, for the layer chain without GN, the MaskIoU head's
+tower and FC trunk) against a torch-CPU fp64 autograd restatement, and the
 assembled models (step, gradients, eager / grouped / replayed agreement, checkpoints, predict, defaults). Small images,
 as tests/test_gpu_dpool_model.py.
 
@@ -187,6 +188,63 @@ def test_gn_mask_head_matches_fp64_autograd(hip):
         return res
     ref, emu = run(lambda t: t), run(_round_fn())
     assert set(got) == set(ref)
+    _compare(sorted(ref), got, ref, emu)
+
+
+@pytest.mark.parametrize("R,fc_dim", [(8, 64), (64, None)])
+def test_maskiou_tower_and_fcs_match_fp64_autograd(hip, R, fc_dim):
+    """The chain without GN in the MaskIoU head's shape: a wider layer 0 (320 -> C), a strided last conv, biases, then the
+    FC trunk through a `view`, with fc1's ReLU mask taken from the tower's last activation. 64 channels are the fewest the
+    dense kernels take (forward Cin % 64, data gradient Cout % 64), fc_dim 64 likewise. R = 8 runs fc1's plain kernel,
+    R = 64 at the default fc_dim its split-K route. The graph starts at the head's assembled input (core.mask.maskiou_input
+    has tests of its own); the input gradient is compared on the feature channels [0, C), all the caller reads.
+    Measured on an MI355X: outputs, emulation 1.8e-3, kernels 1.8e-3; gradients, emulation 1.8e-3 .. 1.0e-1, kernels within
+    1.07x of the emulation on every tensor (bound: 2x)."""
+    import torch
+    from mxdetection_amd.models.mask_heads import MaskIoUHead
+    torch.set_num_threads(16)
+    C = 64
+    head, arena, ws = _standalone(MaskIoUHead, channels=C, rois_per_image=R, **({} if fc_dim is None else {"fc_dim": fc_dim}))
+    head.plan(1)
+    ws.get()
+    g = torch.Generator().manual_seed(7)
+    mpooled = torch.randn((R, 14, 14, C), generator=g).to(torch.bfloat16)
+    logits = torch.randn((R, 28, 28, 128), generator=g).to(torch.bfloat16)
+    cls = torch.randint(1, head.nc, (R,), generator=g).to(torch.int32)
+    go = torch.randn((R, 1, 1, head.ld), generator=g).to(torch.bfloat16)
+    go[..., head.nc - 1:] = 0
+    o = head.forward(mpooled.cuda(), logits.cuda(), cls.cuda())
+    head.go = go.cuda()
+    d_in = head.backward()
+    torch.cuda.synchronize()
+    x_in = head.acts[0].cpu()
+    assert tuple(x_in.shape) == (R, 14, 14, head.cin) and tuple(d_in.shape) == tuple(x_in.shape)
+    assert torch.equal(x_in[..., :C], mpooled) and not x_in[..., C + 1:].any()
+    got = {"out": o.float().cpu().numpy().reshape(R, -1), "d_in": d_in[..., :C].float().cpu().numpy()}
+    for l in head.layers():
+        got[l.name + ".weight"] = arena.view(l.wi, "g").cpu().numpy()
+        got[l.name + ".bias"] = arena.view(l.bi, "g").cpu().numpy()
+
+    def run(rnd):
+        F = torch.nn.functional
+        x = x_in.double().permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+        params = {l.name: (_w(arena, l), _b(arena, l)) for l in head.layers()}
+        t = x
+        for c in head.convs:
+            w, b = params[c.name]
+            t = rnd(torch.relu(F.conv2d(t, w, b, stride=c.stride, padding=1)))
+        t = t.permute(0, 2, 3, 1).reshape(R, -1)           # the head's view: (H, W, C) flattened
+        for fc, relu in ((head.fc1, True), (head.fc2, True), (head.fc_out, False)):
+            w, b = params[fc.name]
+            t = t @ w.reshape(w.shape[0], -1).t() + b
+            t = rnd(torch.relu(t) if relu else t)
+        t.backward(go.double().reshape(R, -1))
+        res = {"out": t.detach().numpy(), "d_in": rnd(x.grad).permute(0, 2, 3, 1)[..., :C].numpy()}
+        for name, (w, b) in params.items():
+            res[name + ".weight"], res[name + ".bias"] = w.grad.permute(0, 2, 3, 1).numpy(), b.grad.numpy()
+        return res
+    ref, emu = run(lambda t: t), run(_round_fn())
+    assert set(got) == set(ref) and len(ref) == 2 + 2 * 7
     _compare(sorted(ref), got, ref, emu)
 
 
