@@ -238,6 +238,25 @@ int mxdet_proposal_target(const float* rois, const int32_t* num_rois, int32_t ro
                           uint32_t image_offset, float* out_rois, int32_t* labels,
                           float* bbox_targets, float* bbox_weights, int32_t* matched_gt,
                           int32_t* num_fg, mxdet_stream_t stream);
+/* IoU-balanced negative sampling (Libra R-CNN, Pang et al., CVPR 2019): mxdet_proposal_target with the
+ * background quota spread over num_bins = K (1..MXDET_SAMPLER_MAX_BINS) IoU bins. Foreground selection, candidate set,
+ * Philox streams (2 = fg, 3 = bg) and output layout are those of mxdet_proposal_target. A background candidate
+ * (bg_lo <= iou < bg_hi) belongs to bin k = the number of edges e_j, j = 1..K-1, with iou >= e_j, where
+ * e_j = bg_lo + (bg_hi - bg_lo) * ((float)j / (float)K), each operation one fp32 operation (the edges are FIXED; they do
+ * not depend on the largest background IoU as mmdetection's do). With want = rois_per_image - nfg and per = want / K
+ * (integer division), bin k gives its min(per, count_k) candidates of smallest (key, index); the shortfall
+ * want - sum(taken) is filled with the smallest (key, index) among the background candidates not yet chosen, from any
+ * bin; fewer candidates than want leaves padding. K = 1 is mxdet_proposal_target bit for bit. No host synchronisation,
+ * no allocation, no float atomics; capturable; a pure function of its inputs. Bad num_bins: MXDET_EINVAL, no launch. */
+#define MXDET_SAMPLER_MAX_BINS 8
+int mxdet_proposal_target_balanced(const float* rois, const int32_t* num_rois, int32_t rois_stride,
+                                   const float* gt_boxes, int32_t N, int32_t G_max, int32_t rois_per_image,
+                                   float fg_fraction, float fg_thresh, float bg_hi, float bg_lo, int32_t num_classes,
+                                   int32_t class_agnostic, const float* means /* HOST [4] */,
+                                   const float* stds /* HOST [4] */, uint32_t seed, uint32_t step,
+                                   const uint32_t* step_dev, uint32_t image_offset, int32_t num_bins, float* out_rois,
+                                   int32_t* labels, float* bbox_targets, float* bbox_weights, int32_t* matched_gt,
+                                   int32_t* num_fg, mxdet_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * core/bbox -- online hard example mining for the box head (Shrivastava et al., CVPR 2016).
@@ -425,6 +444,20 @@ int mxdet_rcnn_loss(const void* cls_logits, const void* bbox_pred, int32_t dtype
                     const float* bbox_weights, int64_t R, int32_t num_classes, int32_t reg_dim,
                     float sigma, float norm, float loss_scale, float* loss_out, void* grad_cls,
                     void* grad_reg, void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
+/* mxdet_rcnn_loss with Balanced L1 (Libra R-CNN, Pang et al., CVPR 2019) in place of smooth-L1: same row
+ * walk, targets and weights convention, columns left untouched alike; loss_out[0] and grad_cls are bit-identical to
+ * mxdet_rcnn_loss. Per column with weight w != 0 of a row with label > 0: d = (pred - target) * w, a = |d|,
+ *   a < beta:  L = (alpha / b) * (b*a + 1) * log(b*a/beta + 1) - alpha*a,  dL/dd = sign(d) * alpha * log(b*a/beta + 1)
+ *   else:      L = gamma*a + gamma/b - alpha*beta,                           dL/dd = sign(d) * gamma
+ * (log = mxdet_logf; fp32 operation order: DESIGN.md section 3). b is the caller's float32(exp(gamma/alpha) - 1): the
+ * kernel never evaluates it. The closed-form gradient is the paper's: the derivative of L exactly when beta = 1 (the
+ * published setting); value and gradient are continuous at a = beta for every beta. loss_out[1] = sum_r (reg_weight * sum_c L) * norm; grad_reg = dL/dd * reg_weight * w * norm *
+ * loss_scale. alpha, gamma, beta, b, reg_weight > 0, else MXDET_EINVAL. */
+int mxdet_rcnn_loss_balanced(const void* cls_logits, const void* bbox_pred, int32_t dtype, int32_t ld_cls, int32_t ld_reg,
+                             const int32_t* labels, const float* bbox_targets, const float* bbox_weights, int64_t R,
+                             int32_t num_classes, int32_t reg_dim, float alpha, float gamma, float beta, float b,
+                             float reg_weight, float norm, float loss_scale, float* loss_out, void* grad_cls,
+                             void* grad_reg, void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
 
 /* IoU-family box losses on the DECODED box. Per element: a box b (roi / anchor), a ground-truth box g and
  * four raw deltas d; the prediction is b decoded by d * stds ("+1" convention, means 0, dw / dh clamped at
@@ -945,6 +978,46 @@ int mxdet_subsample2_bwd(const uint16_t* dy, int32_t N, int32_t H, int32_t W, in
 /* adjoint of the nearest-neighbour 2x upsample: dcoarse[N,Hc,Wc,C] (+)= sum of the 2x2 fine cells */
 int mxdet_upsample2_bwd(const uint16_t* dfine, int32_t N, int32_t Hf, int32_t Wf, int32_t C,
                         int32_t accumulate, uint16_t* dcoarse, mxdet_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * models/necks -- Balanced Feature Pyramid (Libra R-CNN, Pang et al., CVPR 2019): the gather and scatter
+ * stages around the refine step, which is the caller's (a 3x3 convolution, or none).
+ * Levels l = 0..L-1, finest first, bf16 [N,H[l],W[l],C] channels-last; refine level r; (h, w) = (H[r], W[r]).
+ *   gather:   g_l = adaptive max pool of P_l to (h, w) for l < r, P_r itself, the nearest resize of P_l for l > r;
+ *             B = bf16((((g_0 + g_1) + ...) + g_{L-1}) / (float)L): fp32 sum in level order, one division, one rounding.
+ *   scatter:  Q_l = bf16(f32(P_l) + f32(s_l)); s_l = the nearest resize of Rf to (H[l], W[l]) for l < r, Rf itself for
+ *             l = r, the adaptive max pool of Rf for l > r.
+ * Index rules along an axis (those of torch's interpolate(mode="nearest") and adaptive_max_pool2d at integer ratios and
+ * at the shapes of tests/test_libra_cpu.py): nearest src = (dst * in) / out in integers; pool window of output o =
+ * [floor(o * in / out), ceil((o + 1) * in / out)) -- windows overlap when in is no multiple of out; the maximum's ties go
+ * to the first element in row-major window order. A window may span at most 16 elements per axis (MXDET_ESHAPE).
+ * The forward entries store every pooled element's arg-maximum (u8: 16 * dy + dx inside the window) in the workspace:
+ * the backward entries read no activation.
+ *   scatter_bwd: dRf = bf16(sum_l adj(s_l)(dQ_l)): one fp32 sum over the levels in order and, within a level, over
+ *             the contributing pixels in row-major order.
+ *   gather_bwd:  dP_l = bf16(f32(dQ_l) + adj(g_l)(f32(dB) / (float)L)): each term is divided first, the terms are
+ *             summed in fp32 in row-major order of the contributing pixels, and the sum is added to f32(dQ_l).
+ * Gather form, no float atomics: bit-identical run to run. out[l] may equal feat[l] (gather_bwd in place over dQ).
+ * Every entry: one launch for all levels; host checks before it (2 <= L <= MXDET_BFP_MAX_LEVELS, 0 <= r < L, N, H, W
+ * positive, C % 8 == 0: MXDET_ESHAPE; null pointers: MXDET_EINVAL; workspace: MXDET_EWORKSPACE); no allocation, no
+ * host synchronisation; capturable. */
+#define MXDET_BFP_MAX_LEVELS 6
+typedef struct {
+  int32_t num_levels, refine_level, N, C;
+  int32_t H[8], W[8];
+  void* feat[8]; /* per level: P (gather_fwd, scatter_fwd), dQ (scatter_bwd, gather_bwd) */
+  void* out[8];  /* per level: Q (scatter_fwd), dP (gather_bwd); not read by the other two */
+} mxdet_bfp_desc_t;
+size_t mxdet_bfp_workspace_bytes(const mxdet_bfp_desc_t* d);
+int mxdet_bfp_gather_fwd(const mxdet_bfp_desc_t* d, uint16_t* B, void* workspace, size_t workspace_bytes,
+                         mxdet_stream_t stream);
+int mxdet_bfp_scatter_fwd(const mxdet_bfp_desc_t* d, const uint16_t* Rf, void* workspace, size_t workspace_bytes,
+                          mxdet_stream_t stream);
+int mxdet_bfp_scatter_bwd(const mxdet_bfp_desc_t* d, uint16_t* dRf, const void* workspace, size_t workspace_bytes,
+                          mxdet_stream_t stream);
+int mxdet_bfp_gather_bwd(const mxdet_bfp_desc_t* d, const uint16_t* dB, const void* workspace, size_t workspace_bytes,
+                         mxdet_stream_t stream);
+
 /* One-stage (RetinaNet) test-time detection, MXNet-lineage role: per level top-k of sigmoid scores over (anchor, class),
  * decode, concatenate levels, per-class NMS, max_per_image -- a host loop in the lineage.
  * p describes the head outputs with p->classes = C foreground classes and p->A = anchors_per_cell * C:

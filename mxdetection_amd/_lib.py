@@ -82,6 +82,12 @@ class GnDescT(C.Structure):
                 ("accumulate", c_i32)]
 
 
+class BfpDescT(C.Structure):
+    """mxdet_bfp_desc_t (include/mxdet.h)."""
+    _fields_ = [("num_levels", c_i32), ("refine_level", c_i32), ("N", c_i32), ("C", c_i32), ("H", c_i32 * 8), ("W", c_i32 * 8),
+                ("feat", c_vp * 8), ("out", c_vp * 8)]
+
+
 class RpnOrderedItemT(C.Structure):
     """mxdet_rpn_ordered_item_t (include/mxdet.h)."""
     _fields_ = [("kind", c_i32), ("H", c_i32), ("W", c_i32), ("halves_per_slab", c_i32), ("slab0", c_i32),
@@ -143,6 +149,9 @@ SIGNATURES = {
     "mxdet_proposal_target": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32,
                                       c_i32, c_i32, P(c_f32), P(c_f32), c_u32, c_u32, c_vp, c_u32, c_vp, c_vp, c_vp,
                                       c_vp, c_vp, c_vp, c_vp]),
+    "mxdet_proposal_target_balanced": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32,
+                                               c_i32, c_i32, P(c_f32), P(c_f32), c_u32, c_u32, c_vp, c_u32, c_i32, c_vp, c_vp,
+                                               c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mxdet_ohem_roi_score": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i64,
                                      c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp]),
     "mxdet_ohem_select_workspace_bytes": (c_sz, [c_i32, c_i32]),
@@ -176,6 +185,8 @@ SIGNATURES = {
     "mxdet_loss_finalize": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     "mxdet_rcnn_loss": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32,
                                 c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_rcnn_loss_balanced": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32, c_f32,
+                                         c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mxdet_box_iou_loss": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_i32, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp,
                                    c_vp, c_vp]),
     "mxdet_rcnn_loss_iou": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_i32,
@@ -251,6 +262,11 @@ SIGNATURES = {
     "mxdet_subsample2": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mxdet_subsample2_bwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mxdet_upsample2_bwd": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "mxdet_bfp_workspace_bytes": (c_sz, [P(BfpDescT)]),
+    "mxdet_bfp_gather_fwd": (c_i32, [P(BfpDescT), c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_bfp_scatter_fwd": (c_i32, [P(BfpDescT), c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_bfp_scatter_bwd": (c_i32, [P(BfpDescT), c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_bfp_gather_bwd": (c_i32, [P(BfpDescT), c_vp, c_vp, c_sz, c_vp]),
     "mxdet_add_bf16": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "mxdet_relu_bwd_bf16": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "mxdet_f32_to_bf16": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
@@ -289,6 +305,9 @@ CLS_LOSS_KINDS = {"qfl": 1, "vfl": 2}
 # `cls_kind` of mxdet_retina_loss_level_dfl: the above and MXDET_CLS_LOSS_FOCAL; reg_max's bound (MXDET_REG_MAX_LIMIT)
 CLS_LOSS_KINDS_DFL = {"focal": 0, "qfl": 1, "vfl": 2}
 REG_MAX_LIMIT = 31
+# bounds of the Libra R-CNN entries (MXDET_SAMPLER_MAX_BINS, MXDET_BFP_MAX_LEVELS)
+SAMPLER_MAX_BINS = 8
+BFP_MAX_LEVELS = 6
 
 _lib = None
 

@@ -28,12 +28,16 @@ def bbox_overlaps(boxes, query_boxes):
 
 def sample_rois(rois, num_rois, gt_boxes, rois_per_image=512, fg_fraction=0.25, fg_thresh=0.5, bg_thresh_hi=0.5,
                 bg_thresh_lo=0.0, num_classes=81, class_agnostic=False, bbox_means=(0.0, 0.0, 0.0, 0.0),
-                bbox_stds=(0.1, 0.1, 0.2, 0.2), seed=0, step=0, image_offset=0, step_dev=None):
-    """proposal-target. rois [N,S,5], num_rois [N] int32, gt_boxes [N,G,5] (class < 0 = padding).
+                bbox_stds=(0.1, 0.1, 0.2, 0.2), seed=0, step=0, image_offset=0, step_dev=None, num_bins=None):
+    """proposal-target. rois [N,S,5], num_rois [N] int32, gt_boxes [N,G,5] (class < 0 = padding). num_bins: None = uniform
+    background sampling; 1..SAMPLER_MAX_BINS = IoU-balanced background sampling over that many fixed IoU bins
+    (mxdet_proposal_target_balanced; 1 bin gives the uniform sampler's bits).
 
     Returns (rois [N,R,5], labels [N,R] i32, bbox_targets [N,R,D], bbox_weights [N,R,D], matched_gt [N,R] i32,
     num_fg [N] i32); D = 4 (class agnostic) or 4*num_classes.
     """
+    if num_bins is not None:
+        check_sampler("iou_balanced", num_bins)
     lib = _lib.load()
     _f32c(rois), _f32c(gt_boxes)
     N, S = rois.shape[0], rois.shape[1]
@@ -49,11 +53,31 @@ def sample_rois(rois, num_rois, gt_boxes, rois_per_image=512, fg_fraction=0.25, 
     num_fg = torch.empty((N,), dtype=torch.int32, device=dev)
     means = (C.c_float * 4)(*bbox_means)
     stds = (C.c_float * 4)(*bbox_stds)
-    check(lib.mxdet_proposal_target(ptr(rois), ptr(num_rois), S, ptr(gt_boxes), N, G, R, fg_fraction, fg_thresh,
-                                    bg_thresh_hi, bg_thresh_lo, num_classes, int(class_agnostic), means, stds,
-                                    seed, step, ptr(step_dev), image_offset, ptr(out_rois), ptr(labels), ptr(tgt), ptr(wgt),
-                                    ptr(matched), ptr(num_fg), stream_ptr()), "proposal_target")
+    head = (ptr(rois), ptr(num_rois), S, ptr(gt_boxes), N, G, R, fg_fraction, fg_thresh, bg_thresh_hi, bg_thresh_lo, num_classes,
+            int(class_agnostic), means, stds, seed, step, ptr(step_dev), image_offset)
+    outs = (ptr(out_rois), ptr(labels), ptr(tgt), ptr(wgt), ptr(matched), ptr(num_fg), stream_ptr())
+    if num_bins is None:
+        check(lib.mxdet_proposal_target(*head, *outs), "proposal_target")
+    else:
+        check(lib.mxdet_proposal_target_balanced(*head, num_bins, *outs), "proposal_target_balanced")
     return out_rois, labels, tgt, wgt, matched, num_fg
+
+
+# ---- IoU-balanced negative sampling (Libra R-CNN; include/mxdet.h) ----
+SAMPLERS = ("random", "iou_balanced")
+SAMPLER_MAX_BINS = _lib.SAMPLER_MAX_BINS
+
+
+def check_sampler(sampler, sampler_bins=3, ohem=False):
+    """The RoI sampler options of the box head, checked before anything is allocated."""
+    if sampler not in SAMPLERS:
+        raise ValueError("sampler must be one of %s (got %r)" % (", ".join(SAMPLERS), sampler))
+    k = sampler_bins
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= SAMPLER_MAX_BINS:
+        raise ValueError("sampler_bins must be an integer in 1..%d (got %r)" % (SAMPLER_MAX_BINS, k))
+    if sampler == "iou_balanced" and ohem:
+        raise ValueError("sampler = 'iou_balanced' cannot be combined with ohem: OHEM keeps no fg:bg quota for the IoU bins to "
+                         "balance")
 
 
 # ---- online hard example mining for the box head (include/mxdet.h; DESIGN.md 5o) ----

@@ -95,17 +95,53 @@ def retina_loss_level(cls, reg, A, C, cls_labels, bbox_targets, level_offset, al
 # ---- IoU / GIoU / DIoU losses on the decoded box (include/mxdet.h) ----
 IOU_LOSS_KINDS = _lib.IOU_LOSS_KINDS
 REG_LOSSES = ("smooth_l1",) + tuple(IOU_LOSS_KINDS)
+BOX_HEAD_REG_LOSSES = REG_LOSSES + ("balanced_l1",)       # Balanced L1 (Libra R-CNN) is the box head's alone
 
 
-def check_reg_loss(reg_loss, reg_loss_weight):
-    """The regression-loss options of the box heads and the RetinaNet head, checked before anything is allocated."""
-    if reg_loss not in REG_LOSSES:
-        raise ValueError("reg_loss must be one of %s (got %r)" % (", ".join(REG_LOSSES), reg_loss))
+def check_reg_loss(reg_loss, reg_loss_weight, box_head=False):
+    """The regression-loss options of the box heads (box_head: 'balanced_l1' too) and the RetinaNet head, checked before
+    anything is allocated."""
+    if reg_loss == "balanced_l1" and not box_head:
+        raise ValueError("reg_loss = 'balanced_l1' is an option of the R-CNN box head only (the RetinaNet head keeps %s)"
+                         % ", ".join(REG_LOSSES))
+    allowed = BOX_HEAD_REG_LOSSES if box_head else REG_LOSSES
+    if reg_loss not in allowed:
+        raise ValueError("reg_loss must be one of %s (got %r)" % (", ".join(allowed), reg_loss))
     w = reg_loss_weight
     if isinstance(w, bool) or not isinstance(w, (int, float)) or not w > 0:
         raise ValueError("reg_loss_weight must be a positive number (got %r)" % (w,))
     if reg_loss == "smooth_l1" and w != 1:
         raise ValueError("reg_loss_weight = %r needs an IoU-family reg_loss: smooth_l1 takes no weight" % (w,))
+
+
+# ---- Balanced L1 of the box head (Libra R-CNN, Pang et al. 2019; include/mxdet.h; DESIGN.md 5r) ----
+BL1_DEFAULTS = (0.5, 1.5, 1.0)          # alpha, gamma, beta as published
+
+
+def check_balanced_l1(alpha=0.5, gamma=1.5, beta=1.0):
+    """alpha, gamma, beta of Balanced L1: positive finite numbers. Returns them as floats."""
+    for name, v in (("bl1_alpha", alpha), ("bl1_gamma", gamma), ("bl1_beta", beta)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 < float(v) < float("inf"):
+            raise ValueError("%s must be a positive finite number (got %r)" % (name, v))
+    return float(alpha), float(gamma), float(beta)
+
+
+def balanced_l1_b(alpha, gamma):
+    """b = float32(exp(gamma / alpha) - 1), evaluated in double: the constant that joins Balanced L1's two branches."""
+    import math
+    return float(torch.tensor(math.exp(float(gamma) / float(alpha)) - 1.0, dtype=torch.float64).to(torch.float32))
+
+
+def rcnn_loss_balanced(cls_logits, bbox_pred, labels, bbox_targets, bbox_weights, num_classes, reg_dim, ld_cls, ld_reg, alpha,
+                       gamma, beta, reg_weight, norm, loss_scale, grad_cls, grad_reg, loss_out, workspace):
+    """rcnn_loss with Balanced L1(alpha, gamma, beta) times reg_weight in place of smooth-L1."""
+    lib = _lib.load()
+    alpha, gamma, beta = check_balanced_l1(alpha, gamma, beta)
+    R = labels.numel()
+    check(lib.mxdet_rcnn_loss_balanced(ptr(cls_logits), ptr(bbox_pred), _DT[cls_logits.dtype], ld_cls, ld_reg, ptr(labels),
+                                       ptr(bbox_targets), ptr(bbox_weights), R, num_classes, reg_dim, alpha, gamma, beta,
+                                       balanced_l1_b(alpha, gamma), reg_weight, norm, loss_scale, ptr(loss_out), ptr(grad_cls),
+                                       ptr(grad_reg), ptr(workspace), workspace.numel(), stream_ptr()), "rcnn_loss_balanced")
 
 
 def box_iou_loss(boxes, gt, deltas, kind="giou", stds=(1.0, 1.0, 1.0, 1.0), weight=None, grad_scale=1.0, loss=None,

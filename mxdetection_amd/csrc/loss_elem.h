@@ -340,27 +340,82 @@ __device__ __forceinline__ float rcnn_softmax_ce(const void* __restrict__ cls, i
   return lcls;
 }
 
-// smooth-L1 of roi r's reg_dim columns against its targets / weights; kGrad: writes columns [0, reg_dim) of the grad_reg
-// row. Every lane returns the row's loss.
-template <bool kGrad>
-__device__ __forceinline__ float rcnn_reg_smooth_l1(const void* __restrict__ reg, int dtype, int ld_reg, long long r, int lab,
-                                                    int lane, const float* __restrict__ tgt, const float* __restrict__ wgt,
-                                                    int reg_dim, float sigma2, float norm, float loss_scale,
-                                                    void* __restrict__ greg) {
+// Balanced L1 (Pang et al., CVPR 2019) of one weighted difference d, a = |d|:
+//   a < beta:  L = (alpha / b) * (b * a + 1) * log(b * a / beta + 1) - alpha * a,   dL/dd = sign(d) * alpha * log(b * a / beta + 1)
+//   else:      L = gamma * a + gamma / b - alpha * beta,                            dL/dd = sign(d) * gamma
+// b = exp(gamma / alpha) - 1 comes from the host (the two branches then meet at a = beta). One fp32 operation per
+// statement, in this order; the log is mxdet_logf.
+__device__ __forceinline__ float balanced_l1_log(float a, float beta, float b) {
+  float t = b * a;
+  t = t / beta;
+  t = t + 1.0f;
+  return mxdet_logf(t);
+}
+__device__ __forceinline__ float balanced_l1(float d, float alpha, float gamma, float beta, float b) {
+  const float a = d < 0.0f ? -d : d;
+  if (a < beta) {
+    const float lg = balanced_l1_log(a, beta, b);
+    float p = b * a;
+    p = p + 1.0f;
+    float q = alpha / b;
+    q = q * p;
+    q = q * lg;
+    const float s = alpha * a;
+    return q - s;
+  }
+  float L = gamma * a;
+  const float c0 = gamma / b;
+  L = L + c0;
+  const float c1 = alpha * beta;
+  return L - c1;
+}
+__device__ __forceinline__ float balanced_l1_grad(float d, float alpha, float gamma, float beta, float b) {
+  const float a = d < 0.0f ? -d : d;
+  const float m = a < beta ? alpha * balanced_l1_log(a, beta, b) : gamma;
+  return d > 0.0f ? m : (d < 0.0f ? -m : 0.0f);
+}
+
+// The regression elements as rcnn_reg_elem takes them: loss(d) and grad(d) = dL/dd of one weighted difference.
+struct SmoothL1Elem {
+  float sigma2;
+  __device__ __forceinline__ float loss(float d) const { return mxdet_smooth_l1(d, sigma2); }
+  __device__ __forceinline__ float grad(float d) const { return mxdet_smooth_l1_grad(d, sigma2); }
+};
+struct BalancedL1Elem {      // reg_weight scales the gradient here and the row's loss in the kernel
+  float alpha, gamma, beta, b, reg_weight;
+  __device__ __forceinline__ float loss(float d) const { return balanced_l1(d, alpha, gamma, beta, b); }
+  __device__ __forceinline__ float grad(float d) const { return balanced_l1_grad(d, alpha, gamma, beta, b) * reg_weight; }
+};
+
+// An element-wise regression loss of roi r's reg_dim columns against its targets / weights; kGrad: writes columns
+// [0, reg_dim) of the grad_reg row. Every lane returns the row's loss.
+template <bool kGrad, class Elem>
+__device__ __forceinline__ float rcnn_reg_elem(const void* __restrict__ reg, int dtype, int ld_reg, long long r, int lab,
+                                               int lane, const float* __restrict__ tgt, const float* __restrict__ wgt,
+                                               int reg_dim, const Elem elem, float norm, float loss_scale,
+                                               void* __restrict__ greg) {
   float lreg = 0.0f;
   for (int c = lane; c < reg_dim; c += 64) {
     float w = wgt[r * reg_dim + c];
     float g = 0.0f;
     if (w != 0.0f && lab > 0) {
       float d = (load_as_f32(reg, r * ld_reg + c, dtype) - tgt[r * reg_dim + c]) * w;
-      lreg += mxdet_smooth_l1(d, sigma2);
-      if (kGrad) g = mxdet_smooth_l1_grad(d, sigma2) * w * norm * loss_scale;
+      lreg += elem.loss(d);
+      if (kGrad) g = elem.grad(d) * w * norm * loss_scale;
     }
     if (kGrad) store_from_f32(greg, r * ld_reg + c, dtype, g);
   }
   // fixed xor tree: every lane ends with the same value
   for (int off = 32; off > 0; off >>= 1) lreg += __shfl_xor(lreg, off);
   return lreg;
+}
+// smooth-L1 (the name ohem.hip scores rows with)
+template <bool kGrad>
+__device__ __forceinline__ float rcnn_reg_smooth_l1(const void* __restrict__ reg, int dtype, int ld_reg, long long r, int lab,
+                                                    int lane, const float* __restrict__ tgt, const float* __restrict__ wgt,
+                                                    int reg_dim, float sigma2, float norm, float loss_scale,
+                                                    void* __restrict__ greg) {
+  return rcnn_reg_elem<kGrad>(reg, dtype, ld_reg, r, lab, lane, tgt, wgt, reg_dim, SmoothL1Elem{sigma2}, norm, loss_scale, greg);
 }
 
 // The IoU-family term of roi r: every lane evaluates the roi's one box (wave-uniform); kGrad: the lanes share the row's

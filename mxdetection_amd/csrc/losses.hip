@@ -131,19 +131,21 @@ rpn_loss_kernel(const uint16_t* __restrict__ head, int N, int H, int W, int A, i
 // ---------------------------------------------------------------------------------------------
 // (rcnn_softmax_ce / rcnn_reg_smooth_l1 / rcnn_reg_iou, the per-roi walks of the two kernels below, live in loss_elem.h:
 // ohem.hip scores rows with the same code.)
-// Box-head losses: one wave per roi.
+// Box-head losses: one wave per roi. Elem: the regression element (SmoothL1Elem: reg_weight is 1, an exact factor;
+// BalancedL1Elem).
+template <class Elem>
 __global__ void __launch_bounds__(256)
 rcnn_loss_kernel(const void* __restrict__ cls, const void* __restrict__ reg, int dtype, int ld_cls,
                  int ld_reg, const int32_t* __restrict__ labels, const float* __restrict__ tgt,
                  const float* __restrict__ wgt, long long R, int num_classes, int reg_dim,
-                 float sigma2, float norm, float loss_scale, void* __restrict__ gcls,
+                 const Elem elem, float reg_weight, float norm, float loss_scale, void* __restrict__ gcls,
                  void* __restrict__ greg, float* __restrict__ partial) {
   long long r = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (r >= R) return;
   const int lane = lane_id();
   int lab = labels[r];
   const float lcls = rcnn_softmax_ce<true>(cls, dtype, ld_cls, r, lab, lane, num_classes, norm, loss_scale, gcls);
-  const float lreg = rcnn_reg_smooth_l1<true>(reg, dtype, ld_reg, r, lab, lane, tgt, wgt, reg_dim, sigma2, norm, loss_scale, greg);
+  const float lreg = reg_weight * rcnn_reg_elem<true>(reg, dtype, ld_reg, r, lab, lane, tgt, wgt, reg_dim, elem, norm, loss_scale, greg);
   if (lane == 0) {
     partial[2 * r + 0] = lcls * norm;
     partial[2 * r + 1] = lreg * norm;
@@ -331,6 +333,31 @@ extern "C" int mxdet_loss_finalize(const float* partial, int32_t count, int32_t 
   return check_launch("loss_finalize");
 }
 
+// the shared checks and the two launches of mxdet_rcnn_loss / mxdet_rcnn_loss_balanced
+template <class Elem>
+static int rcnn_loss_launch(const char* entry, const void* cls_logits, const void* bbox_pred, int32_t dtype, int32_t ld_cls,
+                            int32_t ld_reg, const int32_t* labels, const float* bbox_targets, const float* bbox_weights,
+                            int64_t R, int32_t num_classes, int32_t reg_dim, const Elem elem, float reg_weight, float norm,
+                            float loss_scale, float* loss_out, void* grad_cls, void* grad_reg, void* workspace,
+                            size_t workspace_bytes, mxdet_stream_t stream) {
+  MXDET_REQUIRE(R > 0 && num_classes > 0 && reg_dim > 0 && ld_cls >= num_classes && ld_reg >= reg_dim,
+                MXDET_ESHAPE, "%s: bad shape", entry);
+  MXDET_REQUIRE(dtype == MXDET_DTYPE_F32 || dtype == MXDET_DTYPE_BF16, MXDET_EINVAL, "%s: dtype", entry);
+  MXDET_REQUIRE(cls_logits && bbox_pred && labels && bbox_targets && bbox_weights && loss_out &&
+                    grad_cls && grad_reg,
+                MXDET_EINVAL, "%s: null pointer", entry);
+  MXDET_REQUIRE(workspace && workspace_bytes >= mxdet_loss_workspace_bytes(R), MXDET_EWORKSPACE,
+                "%s: workspace too small", entry);
+  float* partial = (float*)((char*)workspace + 256);
+  hipStream_t s = as_stream(stream);
+  hipLaunchKernelGGL(rcnn_loss_kernel<Elem>, dim3((unsigned)ceil_div<int64_t>(R, 4)), dim3(256), 0, s,
+                     cls_logits, bbox_pred, dtype, ld_cls, ld_reg, labels, bbox_targets, bbox_weights,
+                     (long long)R, num_classes, reg_dim, elem, reg_weight, norm, loss_scale, grad_cls,
+                     grad_reg, partial);
+  hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, partial, (int)R, 2, loss_out);
+  return check_launch(entry);
+}
+
 extern "C" int mxdet_rcnn_loss(const void* cls_logits, const void* bbox_pred, int32_t dtype,
                                int32_t ld_cls, int32_t ld_reg, const int32_t* labels,
                                const float* bbox_targets, const float* bbox_weights, int64_t R,
@@ -338,22 +365,23 @@ extern "C" int mxdet_rcnn_loss(const void* cls_logits, const void* bbox_pred, in
                                float loss_scale, float* loss_out, void* grad_cls, void* grad_reg,
                                void* workspace, size_t workspace_bytes, mxdet_stream_t stream) {
   clear_error();
-  MXDET_REQUIRE(R > 0 && num_classes > 0 && reg_dim > 0 && ld_cls >= num_classes && ld_reg >= reg_dim,
-                MXDET_ESHAPE, "rcnn_loss: bad shape");
-  MXDET_REQUIRE(dtype == MXDET_DTYPE_F32 || dtype == MXDET_DTYPE_BF16, MXDET_EINVAL, "rcnn_loss: dtype");
-  MXDET_REQUIRE(cls_logits && bbox_pred && labels && bbox_targets && bbox_weights && loss_out &&
-                    grad_cls && grad_reg,
-                MXDET_EINVAL, "rcnn_loss: null pointer");
-  MXDET_REQUIRE(workspace && workspace_bytes >= mxdet_loss_workspace_bytes(R), MXDET_EWORKSPACE,
-                "rcnn_loss: workspace too small");
-  float* partial = (float*)((char*)workspace + 256);
-  hipStream_t s = as_stream(stream);
-  hipLaunchKernelGGL(rcnn_loss_kernel, dim3((unsigned)ceil_div<int64_t>(R, 4)), dim3(256), 0, s,
-                     cls_logits, bbox_pred, dtype, ld_cls, ld_reg, labels, bbox_targets, bbox_weights,
-                     (long long)R, num_classes, reg_dim, sigma * sigma, norm, loss_scale, grad_cls,
-                     grad_reg, partial);
-  hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, partial, (int)R, 2, loss_out);
-  return check_launch("rcnn_loss");
+  return rcnn_loss_launch("rcnn_loss", cls_logits, bbox_pred, dtype, ld_cls, ld_reg, labels, bbox_targets, bbox_weights, R,
+                          num_classes, reg_dim, SmoothL1Elem{sigma * sigma}, 1.0f, norm, loss_scale, loss_out, grad_cls,
+                          grad_reg, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mxdet_rcnn_loss_balanced(const void* cls_logits, const void* bbox_pred, int32_t dtype, int32_t ld_cls,
+                                        int32_t ld_reg, const int32_t* labels, const float* bbox_targets,
+                                        const float* bbox_weights, int64_t R, int32_t num_classes, int32_t reg_dim,
+                                        float alpha, float gamma, float beta, float b, float reg_weight, float norm,
+                                        float loss_scale, float* loss_out, void* grad_cls, void* grad_reg, void* workspace,
+                                        size_t workspace_bytes, mxdet_stream_t stream) {
+  clear_error();
+  MXDET_REQUIRE(alpha > 0.0f && gamma > 0.0f && beta > 0.0f && b > 0.0f && reg_weight > 0.0f, MXDET_EINVAL,
+                "rcnn_loss_balanced: alpha, gamma, beta, b and reg_weight must be positive");
+  return rcnn_loss_launch("rcnn_loss_balanced", cls_logits, bbox_pred, dtype, ld_cls, ld_reg, labels, bbox_targets,
+                          bbox_weights, R, num_classes, reg_dim, BalancedL1Elem{alpha, gamma, beta, b, reg_weight}, reg_weight,
+                          norm, loss_scale, loss_out, grad_cls, grad_reg, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mxdet_box_iou_loss(const float* boxes, const float* gt, const void* deltas, int32_t dtype, int32_t ld,

@@ -256,19 +256,24 @@ anchor_encode_kernel(const float4* __restrict__ anchors, long long A_total, cons
 }
 
 // ---------------------------------------------------------------------------------------------
-// proposal target: one workgroup per image.
+// proposal target: one workgroup per image. kBalanced: IoU-balanced background sampling (Pang et al., CVPR 2019; DESIGN.md
+// section 3): the background candidates fall into num_bins IoU bins with FIXED edges e_j = bg_lo + (bg_hi - bg_lo) * (j / K);
+// each bin gives its (R - nfg) / K smallest (key, index), and what the bins could not give is topped up with the smallest
+// (key, index) among the background candidates left over, from any bin. A background candidate of bin k carries state
+// 8 + k until it is chosen (plain sampling: state 2, one selection).
+template <bool kBalanced>
 __global__ void __launch_bounds__(1024)
 proposal_target_kernel(const float* __restrict__ rois, const int32_t* __restrict__ num_rois,
                        int rois_stride, const float* __restrict__ gt, int G_max, int R, int max_fg,
                        float fg_thresh, float bg_hi, float bg_lo, int num_classes, int class_agnostic,
                        float4 means, float4 stds, unsigned seed, unsigned step,
-                       const unsigned* __restrict__ step_dev, unsigned image_offset,
+                       const unsigned* __restrict__ step_dev, unsigned image_offset, int num_bins,
                        float* __restrict__ out_rois, int32_t* __restrict__ labels,
                        float* __restrict__ bbox_targets, float* __restrict__ bbox_weights,
                        int32_t* __restrict__ matched_gt, int32_t* __restrict__ num_fg_out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   // layout: gt[G_max*5] f32 | valid_gt[G_max] i32 | cstate[ncap] i8 (0 none,1 fg cand,2 bg cand,
-  //         3 fg chosen, 4 bg chosen) | cgt[ncap] i16
+  //         3 fg chosen, 4 bg chosen, 8 + k bg cand of IoU bin k) | cgt[ncap] i16
   const int ncap = rois_stride + G_max;
   float* sg = (float*)smem_raw;
   int* vg = (int*)(sg + G_max * 5);
@@ -316,7 +321,20 @@ proposal_target_kernel(const float* __restrict__ rois, const int32_t* __restrict
     if (nv == 0) best = 0.0f;
     signed char st = 0;
     if (best >= fg_thresh && bi >= 0) st = 1;
-    else if (best < bg_hi && best >= bg_lo) st = 2;
+    else if (best < bg_hi && best >= bg_lo) {
+      st = 2;
+      if (kBalanced) {
+        int k = 0;
+        const float span = bg_hi - bg_lo;
+        for (int j = 1; j < num_bins; ++j) {
+          float e = (float)j / (float)num_bins;
+          e = span * e;
+          e = bg_lo + e;
+          if (best >= e) ++k;
+        }
+        st = (signed char)(8 + k);
+      }
+    }
     cstate[i] = st;
     cgt[i] = (short)bi;
   }
@@ -331,13 +349,42 @@ proposal_target_kernel(const float* __restrict__ rois, const int32_t* __restrict
   };
   SelectResult sel_f = block_select_threshold(nc, max_fg, 32, kfg, sm);
   const int nfg = sel_f.n_cand < max_fg ? sel_f.n_cand : max_fg;
-  SelectResult sel_b = block_select_threshold(nc, R - nfg, 32, kbg, sm);
   const int want_bg = (R - nfg) > 0 ? (R - nfg) : 0;
-  if (threadIdx.x == 0) cnt_bg = sel_b.n_cand < want_bg ? sel_b.n_cand : want_bg;
-  for (int i = threadIdx.x; i < nc; i += blockDim.x) {
-    unsigned kv;
-    if (cstate[i] == 1) { kfg(i, kv); if (sel_f.chosen(kv, (unsigned)i)) cstate[i] = 3; }
-    else if (cstate[i] == 2) { kbg(i, kv); if (sel_b.chosen(kv, (unsigned)i)) cstate[i] = 4; }
+  if (!kBalanced) {
+    SelectResult sel_b = block_select_threshold(nc, R - nfg, 32, kbg, sm);
+    if (threadIdx.x == 0) cnt_bg = sel_b.n_cand < want_bg ? sel_b.n_cand : want_bg;
+    for (int i = threadIdx.x; i < nc; i += blockDim.x) {
+      unsigned kv;
+      if (cstate[i] == 1) { kfg(i, kv); if (sel_f.chosen(kv, (unsigned)i)) cstate[i] = 3; }
+      else if (cstate[i] == 2) { kbg(i, kv); if (sel_b.chosen(kv, (unsigned)i)) cstate[i] = 4; }
+    }
+  } else {
+    for (int i = threadIdx.x; i < nc; i += blockDim.x) {
+      unsigned kv;
+      if (cstate[i] == 1) { kfg(i, kv); if (sel_f.chosen(kv, (unsigned)i)) cstate[i] = 3; }
+    }
+    // every quantity below is the same in all threads: the branches around the selections are workgroup-uniform
+    const int per = want_bg / num_bins;
+    int taken = 0;
+    for (int k = 0; k <= num_bins; ++k) {
+      // k < num_bins: bin k's quota; k == num_bins: the top-up from whatever the bins left behind
+      const bool top_up = k == num_bins;
+      const int quota = top_up ? want_bg - taken : per;
+      if (quota <= 0) continue;
+      __syncthreads();                                 // the states the last round wrote
+      auto kbin = [&](int i, unsigned& kv) -> bool {
+        kv = mxdet_sample_key(seed, step, image, 3u, (unsigned)i);
+        return top_up ? cstate[i] >= 8 : cstate[i] == 8 + k;
+      };
+      SelectResult sel_k = block_select_threshold(nc, quota, 32, kbin, sm);
+      const int got = sel_k.n_cand < quota ? sel_k.n_cand : quota;
+      taken += got;
+      for (int i = threadIdx.x; i < nc; i += blockDim.x) {
+        unsigned kv;
+        if (kbin(i, kv) && sel_k.chosen(kv, (unsigned)i)) cstate[i] = 4;
+      }
+    }
+    if (threadIdx.x == 0) cnt_bg = taken;
   }
   __syncthreads();
   const int nbg = cnt_bg;
@@ -481,6 +528,43 @@ extern "C" int mxdet_anchor_target(const float* anchors, int64_t A_total, const 
   return check_launch("anchor_target");
 }
 
+// the checks and launches of mxdet_proposal_target (num_bins = 0) and mxdet_proposal_target_balanced (num_bins >= 1)
+static int proposal_target_launch(const char* entry, const float* rois, const int32_t* num_rois, int32_t rois_stride,
+                                  const float* gt_boxes, int32_t N, int32_t G_max, int32_t rois_per_image,
+                                  float fg_fraction, float fg_thresh, float bg_hi, float bg_lo, int32_t num_classes,
+                                  int32_t class_agnostic, const float* means, const float* stds, uint32_t seed,
+                                  uint32_t step, const uint32_t* step_dev, uint32_t image_offset, int32_t num_bins,
+                                  float* out_rois, int32_t* labels, float* bbox_targets, float* bbox_weights,
+                                  int32_t* matched_gt, int32_t* num_fg, mxdet_stream_t stream) {
+  MXDET_REQUIRE(N > 0 && rois_stride > 0 && G_max > 0 && rois_per_image > 0 && num_classes > 0,
+                MXDET_ESHAPE, "%s: bad sizes", entry);
+  MXDET_REQUIRE(rois && num_rois && gt_boxes && means && stds && out_rois && labels && bbox_targets &&
+                    bbox_weights && matched_gt && num_fg,
+                MXDET_EINVAL, "%s: null pointer", entry);
+  MXDET_REQUIRE(G_max <= 1024 && rois_stride <= 16384, MXDET_ESHAPE, "%s: too large", entry);
+  int ncap = rois_stride + G_max;
+  size_t lds = (size_t)G_max * 5 * 4 + (size_t)G_max * 4 + (size_t)((ncap + 7) & ~7) * 2 +
+               (size_t)((ncap + 15) & ~15);
+  MXDET_REQUIRE(lds <= 120 * 1024, MXDET_ESHAPE, "%s: LDS budget exceeded", entry);
+  int max_fg = (int)(fg_fraction * (float)rois_per_image);
+  // means/stds are tiny host arrays by contract (passed by value into the kernel)
+  float4 m = make_float4(means[0], means[1], means[2], means[3]);
+  float4 sd = make_float4(stds[0], stds[1], stds[2], stds[3]);
+  {
+    const size_t reg_dim = class_agnostic ? 4 : 4 * (size_t)num_classes;
+    const size_t bytes = (size_t)N * rois_per_image * reg_dim * sizeof(float);
+    hipError_t e = zero_async(bbox_targets, bytes, as_stream(stream));
+    if (e == hipSuccess) e = zero_async(bbox_weights, bytes, as_stream(stream));
+    MXDET_REQUIRE(e == hipSuccess, MXDET_EHIP, "%s: zero fill failed", entry);
+  }
+  auto kernel = num_bins > 0 ? proposal_target_kernel<true> : proposal_target_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(N), dim3(1024), lds, as_stream(stream), rois,
+                     num_rois, rois_stride, gt_boxes, G_max, rois_per_image, max_fg, fg_thresh, bg_hi,
+                     bg_lo, num_classes, class_agnostic, m, sd, seed, step, step_dev, image_offset, (int)num_bins,
+                     out_rois, labels, bbox_targets, bbox_weights, matched_gt, num_fg);
+  return check_launch(entry);
+}
+
 extern "C" int mxdet_proposal_target(const float* rois, const int32_t* num_rois, int32_t rois_stride,
                                      const float* gt_boxes, int32_t N, int32_t G_max,
                                      int32_t rois_per_image, float fg_fraction, float fg_thresh,
@@ -492,30 +576,25 @@ extern "C" int mxdet_proposal_target(const float* rois, const int32_t* num_rois,
                                      float* bbox_weights, int32_t* matched_gt, int32_t* num_fg,
                                      mxdet_stream_t stream) {
   clear_error();
-  MXDET_REQUIRE(N > 0 && rois_stride > 0 && G_max > 0 && rois_per_image > 0 && num_classes > 0,
-                MXDET_ESHAPE, "proposal_target: bad sizes");
-  MXDET_REQUIRE(rois && num_rois && gt_boxes && means && stds && out_rois && labels && bbox_targets &&
-                    bbox_weights && matched_gt && num_fg,
-                MXDET_EINVAL, "proposal_target: null pointer");
-  MXDET_REQUIRE(G_max <= 1024 && rois_stride <= 16384, MXDET_ESHAPE, "proposal_target: too large");
-  int ncap = rois_stride + G_max;
-  size_t lds = (size_t)G_max * 5 * 4 + (size_t)G_max * 4 + (size_t)((ncap + 7) & ~7) * 2 +
-               (size_t)((ncap + 15) & ~15);
-  MXDET_REQUIRE(lds <= 120 * 1024, MXDET_ESHAPE, "proposal_target: LDS budget exceeded");
-  int max_fg = (int)(fg_fraction * (float)rois_per_image);
-  // means/stds are tiny host arrays by contract (passed by value into the kernel)
-  float4 m = make_float4(means[0], means[1], means[2], means[3]);
-  float4 sd = make_float4(stds[0], stds[1], stds[2], stds[3]);
-  {
-    const size_t reg_dim = class_agnostic ? 4 : 4 * (size_t)num_classes;
-    const size_t bytes = (size_t)N * rois_per_image * reg_dim * sizeof(float);
-    hipError_t e = zero_async(bbox_targets, bytes, as_stream(stream));
-    if (e == hipSuccess) e = zero_async(bbox_weights, bytes, as_stream(stream));
-    MXDET_REQUIRE(e == hipSuccess, MXDET_EHIP, "proposal_target: zero fill failed");
-  }
-  hipLaunchKernelGGL(proposal_target_kernel, dim3(N), dim3(1024), lds, as_stream(stream), rois,
-                     num_rois, rois_stride, gt_boxes, G_max, rois_per_image, max_fg, fg_thresh, bg_hi,
-                     bg_lo, num_classes, class_agnostic, m, sd, seed, step, step_dev, image_offset, out_rois,
-                     labels, bbox_targets, bbox_weights, matched_gt, num_fg);
-  return check_launch("proposal_target");
+  return proposal_target_launch("proposal_target", rois, num_rois, rois_stride, gt_boxes, N, G_max, rois_per_image,
+                                fg_fraction, fg_thresh, bg_hi, bg_lo, num_classes, class_agnostic, means, stds, seed, step,
+                                step_dev, image_offset, 0, out_rois, labels, bbox_targets, bbox_weights, matched_gt, num_fg,
+                                stream);
+}
+
+extern "C" int mxdet_proposal_target_balanced(const float* rois, const int32_t* num_rois, int32_t rois_stride,
+                                              const float* gt_boxes, int32_t N, int32_t G_max, int32_t rois_per_image,
+                                              float fg_fraction, float fg_thresh, float bg_hi, float bg_lo,
+                                              int32_t num_classes, int32_t class_agnostic, const float* means,
+                                              const float* stds, uint32_t seed, uint32_t step, const uint32_t* step_dev,
+                                              uint32_t image_offset, int32_t num_bins, float* out_rois, int32_t* labels,
+                                              float* bbox_targets, float* bbox_weights, int32_t* matched_gt,
+                                              int32_t* num_fg, mxdet_stream_t stream) {
+  clear_error();
+  MXDET_REQUIRE(num_bins >= 1 && num_bins <= MXDET_SAMPLER_MAX_BINS, MXDET_EINVAL,
+                "proposal_target_balanced: num_bins %d not in 1..%d", num_bins, MXDET_SAMPLER_MAX_BINS);
+  return proposal_target_launch("proposal_target_balanced", rois, num_rois, rois_stride, gt_boxes, N, G_max,
+                                rois_per_image, fg_fraction, fg_thresh, bg_hi, bg_lo, num_classes, class_agnostic, means,
+                                stds, seed, step, step_dev, image_offset, num_bins, out_rois, labels, bbox_targets,
+                                bbox_weights, matched_gt, num_fg, stream);
 }

@@ -20,13 +20,24 @@ class BBoxHead:
 
     def __init__(self, in_features, arena, ws, device, gen, num_classes=81, fc_dim=1024, rois_per_image=512,
                  fg_fraction=0.25, fg_thresh=0.5, bg_hi=0.5, bg_lo=0.0, stds=(0.1, 0.1, 0.2, 0.2), sigma=1.0,
-                 seed=99, reg_loss="smooth_l1", reg_loss_weight=1.0, ohem=False, ohem_nms=0.7):
-        """reg_loss: 'smooth_l1' on the encoded deltas (core.loss.rcnn_loss), or 'iou' / 'giou' / 'diou' on the decoded
-        box times reg_loss_weight (core.loss.rcnn_loss_iou; the head still predicts deltas, inference is the same).
+                 seed=99, reg_loss="smooth_l1", reg_loss_weight=1.0, ohem=False, ohem_nms=0.7, sampler="random",
+                 sampler_bins=3, bl1_alpha=0.5, bl1_gamma=1.5, bl1_beta=1.0):
+        """reg_loss: 'smooth_l1' on the encoded deltas (core.loss.rcnn_loss), 'iou' / 'giou' / 'diou' on the decoded
+        box times reg_loss_weight (core.loss.rcnn_loss_iou; the head still predicts deltas, inference is the same), or
+        'balanced_l1' on the encoded deltas -- Balanced L1(bl1_alpha, bl1_gamma, bl1_beta) times reg_loss_weight
+        (core.loss.rcnn_loss_balanced).
         ohem / ohem_nms: online hard example mining (sample): the training RoIs are the rois_per_image highest-loss
-        candidates of a read-only pass, deduplicated by NMS at ohem_nms (1 = none); fg_fraction is not used."""
-        L_.check_reg_loss(reg_loss, reg_loss_weight)
+        candidates of a read-only pass, deduplicated by NMS at ohem_nms (1 = none); fg_fraction is not used.
+        sampler / sampler_bins: 'random' draws the background RoIs uniformly; 'iou_balanced' spreads their quota over
+        sampler_bins fixed IoU bins (core.bbox.sample_rois(num_bins=)). Not with ohem, which keeps no quota."""
+        L_.check_reg_loss(reg_loss, reg_loss_weight, box_head=True)
         B_.check_ohem(ohem_nms)
+        B_.check_sampler(sampler, sampler_bins, ohem=bool(ohem))
+        self.bl1 = L_.check_balanced_l1(bl1_alpha, bl1_gamma, bl1_beta)
+        if reg_loss == "balanced_l1" and ohem:
+            raise ValueError("reg_loss = 'balanced_l1' cannot be combined with ohem: the per-RoI score "
+                             "(mxdet_ohem_roi_score) has no Balanced L1 term")
+        self.sampler, self.sampler_bins = sampler, sampler_bins
         self.ohem, self.ohem_nms = bool(ohem), float(ohem_nms)
         self.ohem_extractor = None        # the detector's box RoI extractor (set by the detector that owns both)
         self.reg_loss, self.reg_loss_weight = reg_loss, float(reg_loss_weight)
@@ -78,7 +89,8 @@ class BBoxHead:
         if self.ohem:
             return self._sample_ohem(rois, num_rois, gt_boxes, step, image_offset, step_dev, feats)
         out = B_.sample_rois(rois, num_rois, gt_boxes, self.R, self.fg_fraction, self.fg_thresh, self.bg_hi, self.bg_lo,
-                             self.nc, False, (0.0, 0.0, 0.0, 0.0), self.stds, self.seed, step, image_offset, step_dev)
+                             self.nc, False, (0.0, 0.0, 0.0, 0.0), self.stds, self.seed, step, image_offset, step_dev,
+                             num_bins=self.sampler_bins if self.sampler == "iou_balanced" else None)
         self.rois, self.labels, self.tgt, self.wgt, self.matched, self.num_fg = out
         self.gt_boxes = gt_boxes
         return self.rois.view(-1, 5)
@@ -136,6 +148,10 @@ class BBoxHead:
         if self.reg_loss == "smooth_l1":
             L_.rcnn_loss(o2, o2[:, self.nc:], self.labels, self.tgt, self.wgt, self.nc, self.reg_dim, self.ld, self.ld,
                          self.sigma, 1.0 / R, loss_scale, g2, g2[:, self.nc:], self.loss, self.loss_ws)
+        elif self.reg_loss == "balanced_l1":
+            L_.rcnn_loss_balanced(o2, o2[:, self.nc:], self.labels, self.tgt, self.wgt, self.nc, self.reg_dim, self.ld, self.ld,
+                                  *self.bl1, self.reg_loss_weight, 1.0 / R, loss_scale, g2, g2[:, self.nc:], self.loss,
+                                  self.loss_ws)
         else:
             L_.rcnn_loss_iou(o2, o2[:, self.nc:], self.labels, self.rois, self.matched, self.gt_boxes, self.nc, self.reg_dim,
                              self.ld, self.ld, self.reg_loss, self.stds, self.reg_loss_weight, 1.0 / R, loss_scale, g2,

@@ -26,11 +26,13 @@ def build_detector(cfg, device="cuda"):
         dpool = dict(roi_pool=str(net.roi_pool), dpool_trans_std=float(net.dpool_trans_std),
                      dpool_sample_per_part=int(net.dpool_sample_per_part), dpool_offset_fcs=int(net.dpool_offset_fcs))
         heads = dict(bbox_head=str(net.bbox_head), head_norm=str(net.head_norm), gn_groups=net.gn_groups)
+        libra = dict(neck=str(net.neck), bfp_refine=str(net.bfp_refine), sampler=str(net.sampler), sampler_bins=net.sampler_bins,
+                     bl1_alpha=net.bl1_alpha, bl1_gamma=net.bl1_gamma, bl1_beta=net.bl1_beta)
         model = FasterRCNN(device, depth=net.backbone_depth, num_classes=net.num_classes, seed=net.seed,
                            rois_per_image=tr.batch_rois, pre_nms_top_n=tr.rpn_pre_nms_top_n,
                            post_nms_top_n=tr.rpn_post_nms_top_n, with_mask=(net.type == "mask_rcnn"), **dcn, **dpool, **heads,
                            **reg, mask_iou=bool(net.mask_iou), mask_iou_weight=net.mask_iou_weight, ohem=bool(net.ohem),
-                           ohem_nms=net.ohem_nms, **kpt)
+                           ohem_nms=net.ohem_nms, **kpt, **libra)
     elif net.type == "retinanet":
         if net.ohem:
             raise ValueError("network.ohem = %r: retinanet has no box head to mine RoIs for (OHEM is a faster_rcnn / mask_rcnn "
@@ -43,6 +45,15 @@ def build_detector(cfg, device="cuda"):
                              "option)" % (net.mask_iou,))
         if net.roi_pool != "roi_align":
             raise ValueError("network.roi_pool = %r: retinanet has no RoI branch" % (net.roi_pool,))
+        if net.neck != "fpn":
+            raise ValueError("network.neck = %r: retinanet keeps its own pyramid (the Balanced Feature Pyramid is a "
+                             "faster_rcnn / mask_rcnn option)" % (net.neck,))
+        if net.sampler != "random":
+            raise ValueError("network.sampler = %r: retinanet has no RoI sampler (iou_balanced is a faster_rcnn / mask_rcnn "
+                             "option)" % (net.sampler,))
+        if net.reg_loss == "balanced_l1":
+            raise ValueError("network.reg_loss = 'balanced_l1': Balanced L1 is the R-CNN box head's loss (retinanet keeps "
+                             "smooth_l1 | iou | giou | diou)")
         if net.bbox_head != "2fc" or net.head_norm != "none":
             raise ValueError("network.bbox_head / network.head_norm: retinanet has no RoI heads")
         model = RetinaNet(device, depth=net.backbone_depth, num_classes=net.num_classes - 1, seed=net.seed, **dcn, **reg,

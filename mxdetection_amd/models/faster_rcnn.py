@@ -8,12 +8,12 @@ itself is not declared anywhere in the reference tree; thi
 import torch
 
 from ..core import mask as M_
-from ..core.bbox import check_ohem
-from ..core.loss import check_reg_loss
+from ..core.bbox import check_ohem, check_sampler
+from ..core.loss import check_balanced_l1, check_reg_loss
 from .backbones import ResNet
 from .bbox_heads import BBoxHead, ConvFCBBoxHead
 from .mask_heads import FCNMaskHead, KeypointHead, MaskIoUHead
-from .necks import FPN
+from .necks import BFP, FPN, check_neck
 from .roi_extractors import DeformRoIExtractor, FPNRoIExtractor
 from .rpn_heads import RPNHead
 from .utils.detector import DetectorBase
@@ -47,7 +47,8 @@ class FasterRCNN(DetectorBase):
                  dcn_groups=1, roi_pool="roi_align", dpool_trans_std=0.1, dpool_sample_per_part=4, dpool_offset_fcs=3,
                  bbox_head="2fc", head_norm="none", gn_groups=32, reg_loss="smooth_l1", reg_loss_weight=1.0,
                  mask_iou=False, mask_iou_weight=1.0, ohem=False, ohem_nms=0.7, with_keypoints=False, num_keypoints=17,
-                 keypoint_weight=1.0):
+                 keypoint_weight=1.0, neck="fpn", bfp_refine="conv", sampler="random", sampler_bins=3, bl1_alpha=0.5,
+                 bl1_gamma=1.5, bl1_beta=1.0):
         """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
         roi_pool: the box branch's RoI pooling -- 'roi_align', or deformable RoI pooling with its offset head, 'dpool'
         (v1) / 'mdpool' (v2, modulated) (roi_extractors.DeformRoIExtractor, options dpool_*). The mask branch keeps its
@@ -68,7 +69,13 @@ class FasterRCNN(DetectorBase):
         14x14 RoIAlign of its own over the foreground rois, with or without the mask branch; its heatmap loss, times
         keypoint_weight, is the LAST of the step's losses, training takes gt_keypoints [N,G,num_keypoints,3], and
         predict(with_keypoints=True) returns the decoded keypoints. The head draws its initial weights from a generator of
-        its own, so every other parameter starts exactly as in the model without it."""
+        its own, so every other parameter starts exactly as in the model without it.
+        Libra R-CNN (Pang et al. 2019), three independent parts: neck = 'bfp' / bfp_refine -- the Balanced Feature Pyramid
+        behind the FPN (necks.BFP; refine 'conv' = one 3x3 convolution, 'none'); every head, the RPN and predict then read
+        the balanced levels, and the refine convolution draws from a generator of its own. sampler = 'iou_balanced' /
+        sampler_bins -- the box head's background RoIs keep a quota per IoU bin (not with ohem). reg_loss = 'balanced_l1' /
+        bl1_alpha, bl1_gamma, bl1_beta -- Balanced L1 on the encoded deltas, times reg_loss_weight (not with ohem)."""
+        check_neck(neck, bfp_refine)
         check_head_options(bbox_head, head_norm, gn_groups, with_mask)
         if mask_iou and not with_mask:
             raise ValueError("mask_iou needs the mask branch (with_mask=True): the MaskIoU head scores the mask head's output")
@@ -80,10 +87,15 @@ class FasterRCNN(DetectorBase):
             if not isinstance(num_keypoints, int) or isinstance(num_keypoints, bool) or not 1 <= num_keypoints <= 32:
                 raise ValueError("num_keypoints must be an integer in [1, 32] (got %r)" % (num_keypoints,))
             check_loss_weight("keypoint_weight", keypoint_weight)
-        check_reg_loss(reg_loss, reg_loss_weight)
+        check_reg_loss(reg_loss, reg_loss_weight, box_head=True)
         if not isinstance(ohem, (bool, int)):
             raise ValueError("ohem must be a bool (got %r)" % (ohem,))
         check_ohem(ohem_nms)
+        check_sampler(sampler, sampler_bins, ohem=bool(ohem))
+        check_balanced_l1(bl1_alpha, bl1_gamma, bl1_beta)
+        if reg_loss == "balanced_l1" and ohem:
+            raise ValueError("reg_loss = 'balanced_l1' cannot be combined with ohem: the per-RoI score "
+                             "(mxdet_ohem_roi_score) has no Balanced L1 term")
         if roi_pool not in ("roi_align", "dpool", "mdpool"):
             raise ValueError("roi_pool must be 'roi_align', 'dpool' or 'mdpool' (got %r)" % (roi_pool,))
         self.roi_pool = roi_pool
@@ -111,14 +123,16 @@ class FasterRCNN(DetectorBase):
                                          rois_per_image=max(1, rois_per_image // 4), norm=head_norm, gn_groups=gn_groups)
             self.mask_roi_extractor = FPNRoIExtractor([4, 8, 16, 32], pooled=(14, 14), device=device)
         self.mark_mask = self.arena.size
+        libra = dict(sampler=sampler, sampler_bins=sampler_bins, bl1_alpha=bl1_alpha, bl1_gamma=bl1_gamma, bl1_beta=bl1_beta)
         if bbox_head == "4conv1fc":
             self.bbox_head = ConvFCBBoxHead(7 * 7 * 256, self.arena, self.ws, device, gen, norm=head_norm, gn_groups=gn_groups,
                                             num_classes=num_classes, rois_per_image=rois_per_image, seed=rpn_seed,
-                                            reg_loss=reg_loss, reg_loss_weight=reg_loss_weight, ohem=ohem, ohem_nms=ohem_nms)
+                                            reg_loss=reg_loss, reg_loss_weight=reg_loss_weight, ohem=ohem, ohem_nms=ohem_nms,
+                                            **libra)
         else:
             self.bbox_head = BBoxHead(7 * 7 * 256, self.arena, self.ws, device, gen, num_classes=num_classes,
                                       rois_per_image=rois_per_image, seed=rpn_seed, reg_loss=reg_loss,
-                                      reg_loss_weight=reg_loss_weight, ohem=ohem, ohem_nms=ohem_nms)
+                                      reg_loss_weight=reg_loss_weight, ohem=ohem, ohem_nms=ohem_nms, **libra)
         self.dpool = None
         if roi_pool != "roi_align":
             # the offset head belongs to the head bucket: its backward runs in the slot of the RoI extractor's
@@ -132,6 +146,10 @@ class FasterRCNN(DetectorBase):
         self.rpn_head = RPNHead(256, self.strides, self.arena, self.ws_rpn, device, gen, pre_nms_top_n=pre_nms_top_n,
                                 post_nms_top_n=post_nms_top_n, seed=rpn_seed)
         self.mark_rpn = self.arena.size
+        # Balanced Feature Pyramid: its refine convolution's backward completes before the FPN's, so it is registered first
+        # among the neck's layers (inside the FPN bucket)
+        self.bfp = BFP(256, self.arena, self.ws, device, torch.Generator().manual_seed(seed + 15485863),
+                       refine=bfp_refine) if neck == "bfp" else None
         self.neck = FPN([256, 512, 1024, 2048], 256, self.arena, self.ws, device, gen)
         self.mark_fpn = self.arena.size
         self.backbone = ResNet(depth, self.arena, self.ws, device, gen, dcn_stages=dcn_stages,
@@ -139,7 +157,8 @@ class FasterRCNN(DetectorBase):
         self.roi_extractor = self.dpool if self.dpool is not None else FPNRoIExtractor(self.strides[:4], device=device)
         self.bbox_head.ohem_extractor = self.roi_extractor
         layers = self.bbox_head.layers() + (self.dpool.layers() if self.dpool is not None else [])
-        layers += self.rpn_head.layers() + self.neck.layers() + self.backbone.layers()
+        layers += self.rpn_head.layers() + (self.bfp.layers() if self.bfp is not None else [])
+        layers += self.neck.layers() + self.backbone.layers()
         norms = self.bbox_head.norm_layers()
         if with_mask:
             layers = self.mask_head.layers() + layers
@@ -160,6 +179,8 @@ class FasterRCNN(DetectorBase):
         self.neck.plan(c_shapes)
         p_shapes = [(s[0], s[1], s[2], 256) for s in c_shapes]
         p_shapes.append((N, (p_shapes[-1][1] + 1) // 2, (p_shapes[-1][2] + 1) // 2, 256))
+        if self.bfp is not None:
+            self.bfp.plan(p_shapes)
         self.rpn_head.plan(p_shapes, g_max)
         self.bbox_head.plan(N)
         if self.dpool is not None:
@@ -196,7 +217,7 @@ class FasterRCNN(DetectorBase):
             with self._branch_ctx():
                 self.rpn_head.assign_targets(gt_boxes, im_info, step, image_offset, step_dev)
         C = self.backbone.forward(image)
-        P = self.neck.forward(C)
+        P = self._neck_forward(C)
         self.rpn_head.forward(P)
         # The RPN training branch (anchor targets, RPN losses, RPN head backward: MFMA-heavy) depends only on the
         # head outputs; the proposal -> RoI -> box-head chain (long, low-occupancy selection/NMS kernels) does not
@@ -272,6 +293,8 @@ class FasterRCNN(DetectorBase):
             self.roi_extractor.finalize(self.dP[:4], accumulate=True)     # dP[l] = RPN part + RoI part
             self._reduce(0, self.mark_rpn)
             lo = self.mark_rpn
+        if self.bfp is not None:
+            self.bfp.backward(self.dP)          # d/dQ -> d/dP in place: the FPN's backward runs unchanged behind it
         self.neck.backward(self.dP, self.dC, [False, True, True, True])
         if self._bucket_here(1):
             self._reduce(lo, self.mark_fpn)
@@ -285,6 +308,11 @@ class FasterRCNN(DetectorBase):
         if kpt_head is not None:
             losses += (kpt_loss,)           # always the last
         return losses
+
+    def _neck_forward(self, C):
+        """The pyramid every consumer reads: the FPN's levels, balanced by the BFP if the model has one."""
+        P = self.neck.forward(C)
+        return P if self.bfp is None else self.bfp.forward(P)
 
     def predict(self, image, im_info, score_thresh=0.05, nms_thresh=0.5, max_per_image=100, with_masks=False,
                 mask_thresh=0.5, nms_method="hard", soft_sigma=0.5, with_keypoints=False):
@@ -301,7 +329,7 @@ class FasterRCNN(DetectorBase):
         N, _, H, W = image.shape
         g_max = self.planned[3] if self.planned is not None and self.planned[:3] == (N, H, W) else 100
         self.plan(N, H, W, g_max)
-        P = self.neck.forward(self.backbone.forward(image))
+        P = self._neck_forward(self.backbone.forward(image))
         self.rpn_head.forward(P)
         rois, _, _, num_rois = self.rpn_head.get_proposals(im_info)
         pooled = self.roi_extractor.forward(P, rois.view(-1, 5))

@@ -47,7 +47,7 @@ DEFAULTS = {
         "bbox_head": "2fc",               # box head trunk: 2fc | 4conv1fc (four 3x3 convs + one FC)
         "head_norm": "none",              # none | gn: GroupNorm after every conv of the 4conv1fc box head and of the mask head
         "gn_groups": 32,                  # GroupNorm groups (256 / gn_groups must be a multiple of 8)
-        "reg_loss": "smooth_l1",          # box regression loss of the box head / the RetinaNet head: smooth_l1 | iou | giou | diou
+        "reg_loss": "smooth_l1",          # box regression loss of the box head / the RetinaNet head: smooth_l1 | iou | giou | diou | balanced_l1 (box head only)
         "reg_loss_weight": 1.0,           # weight of an IoU-family reg_loss (on the decoded box); smooth_l1 takes none. The RPN keeps smooth-L1
         "cls_loss": "focal",              # retinanet class loss: focal | qfl (Li et al. 2020) | vfl (Zhang et al. 2021); qfl / vfl need an IoU-family reg_loss
         "cls_loss_alpha": None,           # null = the kind's published setting (focal 0.25, vfl 0.75; qfl takes none)
@@ -67,6 +67,13 @@ DEFAULTS = {
         "keypoints": 0,                   # faster_rcnn / mask_rcnn: 1 = Keypoint R-CNN's keypoint head (He et al. 2017); training then reads the roidb's keypoints
         "keypoint_weight": 1.0,           # weight of the keypoint heatmap loss
         "num_keypoints": 17,              # keypoints per instance (COCO person: 17)
+        "neck": "fpn",                    # faster_rcnn / mask_rcnn: fpn | bfp (Libra R-CNN's Balanced Feature Pyramid behind the FPN; Pang et al. 2019)
+        "bfp_refine": "conv",             # refine step of the balanced map: conv (one 3x3 convolution) | none
+        "sampler": "random",              # box head's RoI sampler: random | iou_balanced (background quota per IoU bin; not with ohem)
+        "sampler_bins": 3,                # IoU bins of the iou_balanced sampler (1..8)
+        "bl1_alpha": 0.5,                 # Balanced L1 (reg_loss: balanced_l1, box head only; times reg_loss_weight): alpha ...
+        "bl1_gamma": 1.5,                 # ... gamma ...
+        "bl1_beta": 1.0,                  # ... beta, as published
     },
     "dataset": {
         "type": "synthetic",              # synthetic | coco | voc (ann_file = Annotations directory)

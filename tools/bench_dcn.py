@@ -11,8 +11,9 @@ padded to 1344, weight gradients grouped on a side stream, RPN branch on its own
     python tools/bench_dcn.py --dcn-stages '' --mask 1 --mask-iou 1     # Mask Scoring R-CNN: the MaskIoU head on the mask branch
     python tools/bench_dcn.py --dcn-stages '' --ohem 1 --ohem-nms 0.7   # online hard example mining in the box head
     python tools/bench_dcn.py --dcn-stages '' --keypoints 1             # Keypoint R-CNN: the keypoint head beside the box head
+    python tools/bench_dcn.py --dcn-stages '' --neck bfp --sampler iou_balanced --reg-loss balanced_l1     # Libra R-CNN
 
-Prints one JSON line: {"dcn_stages", "modulated", "groups", "roi_pool", "mask", "mask_iou", "ohem", "keypoints", "img_per_s", "step_ms", "losses"}.
+Prints one JSON line: {"dcn_stages", "modulated", "groups", "roi_pool", "mask", "mask_iou", "ohem", "keypoints", "neck", "sampler", "img_per_s", "step_ms", "losses"}.
 """
 import argparse
 import json
@@ -33,7 +34,7 @@ def main():
     ap.add_argument("--bbox-head", default="2fc", choices=("2fc", "4conv1fc"))
     ap.add_argument("--head-norm", default="none", choices=("none", "gn"))
     ap.add_argument("--gn-groups", type=int, default=32)
-    ap.add_argument("--reg-loss", default="smooth_l1", choices=("smooth_l1", "iou", "giou", "diou"))
+    ap.add_argument("--reg-loss", default="smooth_l1", choices=("smooth_l1", "iou", "giou", "diou", "balanced_l1"))
     ap.add_argument("--reg-loss-weight", type=float, default=1.0)
     ap.add_argument("--mask", type=int, default=0, help="1 = Mask R-CNN (ground-truth masks: an ellipse in every box, as bench.py)")
     ap.add_argument("--mask-iou", type=int, default=0, help="1 = Mask Scoring R-CNN's MaskIoU head (needs --mask 1)")
@@ -42,6 +43,10 @@ def main():
     ap.add_argument("--ohem-nms", type=float, default=0.7, help="dedup IoU of --ohem 1, in (0, 1]; 1 = none")
     ap.add_argument("--keypoints", type=int, default=0, choices=(0, 1),
                     help="1 = Keypoint R-CNN's keypoint head (ground-truth keypoints: 17 points inside every box)")
+    ap.add_argument("--neck", default="fpn", choices=("fpn", "bfp"), help="bfp = Balanced Feature Pyramid behind the FPN")
+    ap.add_argument("--bfp-refine", default="conv", choices=("conv", "none"))
+    ap.add_argument("--sampler", default="random", choices=("random", "iou_balanced"))
+    ap.add_argument("--sampler-bins", type=int, default=3)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     args = ap.parse_args()
@@ -57,7 +62,8 @@ def main():
                        head_norm=args.head_norm, gn_groups=args.gn_groups, with_mask=bool(args.mask),
                        reg_loss=args.reg_loss, reg_loss_weight=args.reg_loss_weight, mask_iou=bool(args.mask_iou),
                        mask_iou_weight=args.mask_iou_weight, ohem=bool(args.ohem), ohem_nms=args.ohem_nms,
-                       with_keypoints=bool(args.keypoints))
+                       with_keypoints=bool(args.keypoints), neck=args.neck, bfp_refine=args.bfp_refine, sampler=args.sampler,
+                       sampler_bins=args.sampler_bins)
     model.enable_wgrad_stream()
     model.enable_branch_stream()
     model.enable_grouped_wgrad()
@@ -99,7 +105,7 @@ def main():
     dt = time.perf_counter() - t0
     vals = [float(v) for v in torch.cat(list(losses)).cpu().numpy()]
     print(json.dumps({"dcn_stages": list(stages), "modulated": bool(args.modulated), "groups": args.groups,
-                      "roi_pool": args.roi_pool, "mask": bool(args.mask), "mask_iou": bool(args.mask_iou), "ohem": bool(args.ohem), "keypoints": bool(args.keypoints), "bbox_head": args.bbox_head, "head_norm": args.head_norm,
+                      "roi_pool": args.roi_pool, "mask": bool(args.mask), "mask_iou": bool(args.mask_iou), "ohem": bool(args.ohem), "keypoints": bool(args.keypoints), "neck": args.neck, "sampler": args.sampler, "bbox_head": args.bbox_head, "head_norm": args.head_norm,
                       "reg_loss": args.reg_loss,
                       "img_per_s": round(BATCH_PER_GPU * args.steps / dt, 2),
                       "step_ms": round(1e3 * dt / args.steps, 3), "losses": vals}), flush=True)
