@@ -1018,6 +1018,32 @@ int mxdet_bfp_scatter_bwd(const mxdet_bfp_desc_t* d, uint16_t* dRf, const void* 
 int mxdet_bfp_gather_bwd(const mxdet_bfp_desc_t* d, const uint16_t* dB, const void* workspace, size_t workspace_bytes,
                          mxdet_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * models/necks -- batched single-head softmax attention: the activation x activation products of the
+ * Balanced Feature Pyramid's embedded-Gaussian non-local refine (Libra R-CNN; Wang et al., Non-local Neural Networks,
+ * CVPR 2018). qkv is bf16 [N, L, row_stride]; Q, K and V are the d columns from q_off, k_off and v_off of every row
+ * (what one 1x1 convolution C -> 3 d writes: nothing is split or copied).
+ *   fwd:  s_ij = scale * sum_c Q_ic K_jc (fp32); O_i = sum_j P_ij V_j with P_ij = exp(s_ij - m_i) / l_i, online over
+ *         64-key tiles; out bf16 [N, L, d] dense, lse f32 [N, L] = m_i + ln l_i. fp32 accumulation; p is rounded to bf16
+ *         only as the operand of the P V product. The L x L matrix never reaches memory.
+ *   bwd:  P is recomputed from Q, K and lse. d_qkv bf16 [N, L, row_stride] receives dQ, dK and dV at the same offsets;
+ *         its other columns are left untouched. delta_i = sum_c dO_ic O_ic goes to the workspace first. Two sweeps (a
+ *         workgroup owns a key block for dK and dV, then a query block for dQ): every output element is summed by one
+ *         wave in a fixed order -- no float atomics, no hand-off between workgroups, bit-identical run to run.
+ * Host checks before any launch: d must be 64 or 128, 1 <= L <= 65536, 1 <= N <= 65535, row_stride and the offsets
+ * multiples of 8 with off + d <= row_stride (MXDET_ESHAPE); scale positive and finite, no null pointer, every pointer
+ * 16-byte aligned (MXDET_EINVAL); workspace (MXDET_EWORKSPACE). No allocation, no host synchronisation; capturable.
+ * mxdet_attention_workspace_bytes returns 0 for a descriptor that fails the checks. */
+typedef struct {
+  int32_t N, L, d, row_stride;
+  int32_t q_off, k_off, v_off;
+  float scale;
+} mxdet_attn_desc_t;
+size_t mxdet_attention_workspace_bytes(const mxdet_attn_desc_t* d);
+int mxdet_attention_fwd(const mxdet_attn_desc_t* d, const uint16_t* qkv, uint16_t* out, float* lse, mxdet_stream_t stream);
+int mxdet_attention_bwd(const mxdet_attn_desc_t* d, const uint16_t* qkv, const uint16_t* out, const uint16_t* d_out,
+                        const float* lse, uint16_t* d_qkv, void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
+
 /* One-stage (RetinaNet) test-time detection, MXNet-lineage role: per level top-k of sigmoid scores over (anchor, class),
  * decode, concatenate levels, per-class NMS, max_per_image -- a host loop in the lineage.
  * p describes the head outputs with p->classes = C foreground classes and p->A = anchors_per_cell * C:

@@ -88,6 +88,12 @@ class BfpDescT(C.Structure):
                 ("feat", c_vp * 8), ("out", c_vp * 8)]
 
 
+class AttnDescT(C.Structure):
+    """mxdet_attn_desc_t (include/mxdet.h)."""
+    _fields_ = [("N", c_i32), ("L", c_i32), ("d", c_i32), ("row_stride", c_i32), ("q_off", c_i32), ("k_off", c_i32),
+                ("v_off", c_i32), ("scale", c_f32)]
+
+
 class RpnOrderedItemT(C.Structure):
     """mxdet_rpn_ordered_item_t (include/mxdet.h)."""
     _fields_ = [("kind", c_i32), ("H", c_i32), ("W", c_i32), ("halves_per_slab", c_i32), ("slab0", c_i32),
@@ -267,6 +273,9 @@ SIGNATURES = {
     "mxdet_bfp_scatter_fwd": (c_i32, [P(BfpDescT), c_vp, c_vp, c_sz, c_vp]),
     "mxdet_bfp_scatter_bwd": (c_i32, [P(BfpDescT), c_vp, c_vp, c_sz, c_vp]),
     "mxdet_bfp_gather_bwd": (c_i32, [P(BfpDescT), c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_attention_workspace_bytes": (c_sz, [P(AttnDescT)]),
+    "mxdet_attention_fwd": (c_i32, [P(AttnDescT), c_vp, c_vp, c_vp, c_vp]),
+    "mxdet_attention_bwd": (c_i32, [P(AttnDescT), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mxdet_add_bf16": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "mxdet_relu_bwd_bf16": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "mxdet_f32_to_bf16": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
@@ -308,6 +317,8 @@ REG_MAX_LIMIT = 31
 # bounds of the Libra R-CNN entries (MXDET_SAMPLER_MAX_BINS, MXDET_BFP_MAX_LEVELS)
 SAMPLER_MAX_BINS = 8
 BFP_MAX_LEVELS = 6
+# head widths of the attention entries (mxdet_attn_desc_t.d)
+ATTN_HEAD_DIMS = (64, 128)
 
 _lib = None
 

@@ -27,7 +27,8 @@ def build_detector(cfg, device="cuda"):
                      dpool_sample_per_part=int(net.dpool_sample_per_part), dpool_offset_fcs=int(net.dpool_offset_fcs))
         heads = dict(bbox_head=str(net.bbox_head), head_norm=str(net.head_norm), gn_groups=net.gn_groups)
         libra = dict(neck=str(net.neck), bfp_refine=str(net.bfp_refine), sampler=str(net.sampler), sampler_bins=net.sampler_bins,
-                     bl1_alpha=net.bl1_alpha, bl1_gamma=net.bl1_gamma, bl1_beta=net.bl1_beta)
+                     bl1_alpha=net.bl1_alpha, bl1_gamma=net.bl1_gamma, bl1_beta=net.bl1_beta,
+                     bfp_nl_reduction=net.bfp_nl_reduction, bfp_nl_use_scale=net.bfp_nl_use_scale)
         model = FasterRCNN(device, depth=net.backbone_depth, num_classes=net.num_classes, seed=net.seed,
                            rois_per_image=tr.batch_rois, pre_nms_top_n=tr.rpn_pre_nms_top_n,
                            post_nms_top_n=tr.rpn_post_nms_top_n, with_mask=(net.type == "mask_rcnn"), **dcn, **dpool, **heads,
@@ -48,6 +49,9 @@ def build_detector(cfg, device="cuda"):
         if net.neck != "fpn":
             raise ValueError("network.neck = %r: retinanet keeps its own pyramid (the Balanced Feature Pyramid is a "
                              "faster_rcnn / mask_rcnn option)" % (net.neck,))
+        if net.bfp_nl_reduction != 2 or net.bfp_nl_use_scale:
+            raise ValueError("network.bfp_nl_reduction / network.bfp_nl_use_scale = %r / %r: retinanet has no Balanced Feature "
+                             "Pyramid to refine (faster_rcnn / mask_rcnn options)" % (net.bfp_nl_reduction, net.bfp_nl_use_scale))
         if net.sampler != "random":
             raise ValueError("network.sampler = %r: retinanet has no RoI sampler (iou_balanced is a faster_rcnn / mask_rcnn "
                              "option)" % (net.sampler,))

@@ -48,7 +48,7 @@ class FasterRCNN(DetectorBase):
                  bbox_head="2fc", head_norm="none", gn_groups=32, reg_loss="smooth_l1", reg_loss_weight=1.0,
                  mask_iou=False, mask_iou_weight=1.0, ohem=False, ohem_nms=0.7, with_keypoints=False, num_keypoints=17,
                  keypoint_weight=1.0, neck="fpn", bfp_refine="conv", sampler="random", sampler_bins=3, bl1_alpha=0.5,
-                 bl1_gamma=1.5, bl1_beta=1.0):
+                 bl1_gamma=1.5, bl1_beta=1.0, bfp_nl_reduction=2, bfp_nl_use_scale=False):
         """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
         roi_pool: the box branch's RoI pooling -- 'roi_align', or deformable RoI pooling with its offset head, 'dpool'
         (v1) / 'mdpool' (v2, modulated) (roi_extractors.DeformRoIExtractor, options dpool_*). The mask branch keeps its
@@ -71,11 +71,13 @@ class FasterRCNN(DetectorBase):
         predict(with_keypoints=True) returns the decoded keypoints. The head draws its initial weights from a generator of
         its own, so every other parameter starts exactly as in the model without it.
         Libra R-CNN (Pang et al. 2019), three independent parts: neck = 'bfp' / bfp_refine -- the Balanced Feature Pyramid
-        behind the FPN (necks.BFP; refine 'conv' = one 3x3 convolution, 'none'); every head, the RPN and predict then read
-        the balanced levels, and the refine convolution draws from a generator of its own. sampler = 'iou_balanced' /
+        behind the FPN (necks.BFP; refine 'conv' = one 3x3 convolution, 'embedded_gaussian' = the paper's non-local block on
+        the attention entries with Ci = 256 / bfp_nl_reduction (2 or 4) and logits scaled by 1 / sqrt(Ci) if
+        bfp_nl_use_scale, 'none'); every head, the RPN and predict then read the balanced levels, and the refine layers draw
+        from a generator of their own. sampler = 'iou_balanced' /
         sampler_bins -- the box head's background RoIs keep a quota per IoU bin (not with ohem). reg_loss = 'balanced_l1' /
         bl1_alpha, bl1_gamma, bl1_beta -- Balanced L1 on the encoded deltas, times reg_loss_weight (not with ohem)."""
-        check_neck(neck, bfp_refine)
+        check_neck(neck, bfp_refine, bfp_nl_reduction, bfp_nl_use_scale)
         check_head_options(bbox_head, head_norm, gn_groups, with_mask)
         if mask_iou and not with_mask:
             raise ValueError("mask_iou needs the mask branch (with_mask=True): the MaskIoU head scores the mask head's output")
@@ -146,10 +148,11 @@ class FasterRCNN(DetectorBase):
         self.rpn_head = RPNHead(256, self.strides, self.arena, self.ws_rpn, device, gen, pre_nms_top_n=pre_nms_top_n,
                                 post_nms_top_n=post_nms_top_n, seed=rpn_seed)
         self.mark_rpn = self.arena.size
-        # Balanced Feature Pyramid: its refine convolution's backward completes before the FPN's, so it is registered first
+        # Balanced Feature Pyramid: its refine layers' backward completes before the FPN's, so they are registered first
         # among the neck's layers (inside the FPN bucket)
         self.bfp = BFP(256, self.arena, self.ws, device, torch.Generator().manual_seed(seed + 15485863),
-                       refine=bfp_refine) if neck == "bfp" else None
+                       refine=bfp_refine, nl_reduction=bfp_nl_reduction,
+                       nl_use_scale=bool(bfp_nl_use_scale)) if neck == "bfp" else None
         self.neck = FPN([256, 512, 1024, 2048], 256, self.arena, self.ws, device, gen)
         self.mark_fpn = self.arena.size
         self.backbone = ResNet(depth, self.arena, self.ws, device, gen, dcn_stages=dcn_stages,

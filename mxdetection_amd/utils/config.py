@@ -68,7 +68,9 @@ DEFAULTS = {
         "keypoint_weight": 1.0,           # weight of the keypoint heatmap loss
         "num_keypoints": 17,              # keypoints per instance (COCO person: 17)
         "neck": "fpn",                    # faster_rcnn / mask_rcnn: fpn | bfp (Libra R-CNN's Balanced Feature Pyramid behind the FPN; Pang et al. 2019)
-        "bfp_refine": "conv",             # refine step of the balanced map: conv (one 3x3 convolution) | none
+        "bfp_refine": "conv",             # refine step of the balanced map: conv (one 3x3 convolution) | embedded_gaussian (the paper's non-local block) | none
+        "bfp_nl_reduction": 2,            # embedded_gaussian: inner channels Ci = 256 / reduction; 2 or 4 (Ci = 128 or 64)
+        "bfp_nl_use_scale": False,        # embedded_gaussian: logits times 1 / sqrt(Ci)
         "sampler": "random",              # box head's RoI sampler: random | iou_balanced (background quota per IoU bin; not with ohem)
         "sampler_bins": 3,                # IoU bins of the iou_balanced sampler (1..8)
         "bl1_alpha": 0.5,                 # Balanced L1 (reg_loss: balanced_l1, box head only; times reg_loss_weight): alpha ...

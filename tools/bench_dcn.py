@@ -12,8 +12,9 @@ padded to 1344, weight gradients grouped on a side stream, RPN branch on its own
     python tools/bench_dcn.py --dcn-stages '' --ohem 1 --ohem-nms 0.7   # online hard example mining in the box head
     python tools/bench_dcn.py --dcn-stages '' --keypoints 1             # Keypoint R-CNN: the keypoint head beside the box head
     python tools/bench_dcn.py --dcn-stages '' --neck bfp --sampler iou_balanced --reg-loss balanced_l1     # Libra R-CNN
+    python tools/bench_dcn.py --dcn-stages '' --neck bfp --bfp-refine embedded_gaussian --sampler iou_balanced --reg-loss balanced_l1     # ... with the paper's non-local refine
 
-Prints one JSON line: {"dcn_stages", "modulated", "groups", "roi_pool", "mask", "mask_iou", "ohem", "keypoints", "neck", "sampler", "img_per_s", "step_ms", "losses"}.
+Prints one JSON line: {"dcn_stages", "modulated", "groups", "roi_pool", "mask", "mask_iou", "ohem", "keypoints", "neck", "bfp_refine", "sampler", "img_per_s", "step_ms", "losses"}.
 """
 import argparse
 import json
@@ -44,7 +45,10 @@ def main():
     ap.add_argument("--keypoints", type=int, default=0, choices=(0, 1),
                     help="1 = Keypoint R-CNN's keypoint head (ground-truth keypoints: 17 points inside every box)")
     ap.add_argument("--neck", default="fpn", choices=("fpn", "bfp"), help="bfp = Balanced Feature Pyramid behind the FPN")
-    ap.add_argument("--bfp-refine", default="conv", choices=("conv", "none"))
+    ap.add_argument("--bfp-refine", default="conv", choices=("conv", "none", "embedded_gaussian"),
+                    help="embedded_gaussian = the non-local block on the attention entries")
+    ap.add_argument("--bfp-nl-reduction", type=int, default=2, choices=(2, 4))
+    ap.add_argument("--bfp-nl-use-scale", type=int, default=0, choices=(0, 1))
     ap.add_argument("--sampler", default="random", choices=("random", "iou_balanced"))
     ap.add_argument("--sampler-bins", type=int, default=3)
     ap.add_argument("--steps", type=int, default=30)
@@ -63,7 +67,8 @@ def main():
                        reg_loss=args.reg_loss, reg_loss_weight=args.reg_loss_weight, mask_iou=bool(args.mask_iou),
                        mask_iou_weight=args.mask_iou_weight, ohem=bool(args.ohem), ohem_nms=args.ohem_nms,
                        with_keypoints=bool(args.keypoints), neck=args.neck, bfp_refine=args.bfp_refine, sampler=args.sampler,
-                       sampler_bins=args.sampler_bins)
+                       sampler_bins=args.sampler_bins, bfp_nl_reduction=args.bfp_nl_reduction,
+                       bfp_nl_use_scale=bool(args.bfp_nl_use_scale))
     model.enable_wgrad_stream()
     model.enable_branch_stream()
     model.enable_grouped_wgrad()
@@ -105,7 +110,7 @@ def main():
     dt = time.perf_counter() - t0
     vals = [float(v) for v in torch.cat(list(losses)).cpu().numpy()]
     print(json.dumps({"dcn_stages": list(stages), "modulated": bool(args.modulated), "groups": args.groups,
-                      "roi_pool": args.roi_pool, "mask": bool(args.mask), "mask_iou": bool(args.mask_iou), "ohem": bool(args.ohem), "keypoints": bool(args.keypoints), "neck": args.neck, "sampler": args.sampler, "bbox_head": args.bbox_head, "head_norm": args.head_norm,
+                      "roi_pool": args.roi_pool, "mask": bool(args.mask), "mask_iou": bool(args.mask_iou), "ohem": bool(args.ohem), "keypoints": bool(args.keypoints), "neck": args.neck, "bfp_refine": args.bfp_refine, "sampler": args.sampler, "bbox_head": args.bbox_head, "head_norm": args.head_norm,
                       "reg_loss": args.reg_loss,
                       "img_per_s": round(BATCH_PER_GPU * args.steps / dt, 2),
                       "step_ms": round(1e3 * dt / args.steps, 3), "losses": vals}), flush=True)
