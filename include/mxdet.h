@@ -1044,6 +1044,32 @@ int mxdet_attention_fwd(const mxdet_attn_desc_t* d, const uint16_t* qkv, uint16_
 int mxdet_attention_bwd(const mxdet_attn_desc_t* d, const uint16_t* qkv, const uint16_t* out, const uint16_t* d_out,
                         const float* lse, uint16_t* d_qkv, void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * models/necks -- CARAFE upsampling (Wang et al., Content-Aware ReAssembly of FEatures, ICCV 2019): the
+ * learned replacement of the FPN's nearest-neighbour top-down upsample. Factor 2; reassembly kernel k = 3 or 5, r = k / 2.
+ *   X bf16 [N,H,W,C] the coarse map; M bf16 [N,H,W,Cm] the kernel logits, of which channels 0 .. 4 k^2 - 1 are real and
+ *   the others alignment padding that is never read; Y bf16 [N,Hf,Wf,C] with Hf = 2 H or 2 H - 1, Wf = 2 W or 2 W - 1 (what
+ *   a pyramid level of (Hf + 1) / 2 rows produces): rows / columns of the 2 H x 2 W grid past Hf / Wf are not computed.
+ *   fwd:  output pixel (i, j) has source q = (i >> 1, j >> 1) and sub-position s = (i & 1) * 2 + (j & 1); tap t = a * k + b
+ *         reads X at (q_y + a - r, q_x + b - r), zero outside the map; its logit is channel t * 4 + s (the published
+ *         pixel-shuffle order); w = softmax over the k^2 taps in fp32, maximum subtracted;
+ *         Y[n,i,j,c] = bf16(sum_t w_t X[n,src(t),c]), fp32 sum in tap order, one rounding.
+ *   bwd:  the weights are recomputed from M (the forward's function). dX[n,p,c] = bf16((accumulate ? f32(dX) : 0) + sum of
+ *         w[q,s,t(p - q)] dY[n,2q+s,c] over the sources q within r of p in row-major order and their sub-positions inside
+ *         Hf x Wf); dM[n,q,t*4+s] = bf16(w_t (g_t - sum_u w_u g_u)), g_t = sum_c dY[n,2q+s,c] X[n,src(t),c]; dM is exactly 0
+ *         for a cropped sub-position and in every padding channel. Gather form, no float atomics: the same bits run to run.
+ * Host checks before any launch: k in {3, 5}, N, H, W positive, C a positive multiple of 8, Cm >= 4 k^2, Hf and Wf as above
+ * (MXDET_ESHAPE); no null pointer, X / Y / dY / dX 16-byte aligned (MXDET_EINVAL). No workspace, no allocation, no host
+ * synchronisation; capturable. */
+typedef struct {
+  int32_t N, H, W, C;
+  int32_t Cm, k;
+  int32_t Hf, Wf;
+} mxdet_carafe_desc_t;
+int mxdet_carafe_fwd(const mxdet_carafe_desc_t* d, const uint16_t* X, const uint16_t* M, uint16_t* Y, mxdet_stream_t stream);
+int mxdet_carafe_bwd(const mxdet_carafe_desc_t* d, const uint16_t* X, const uint16_t* M, const uint16_t* dY, uint16_t* dX,
+                     uint16_t* dM, int32_t accumulate, mxdet_stream_t stream);
+
 /* One-stage (RetinaNet) test-time detection, MXNet-lineage role: per level top-k of sigmoid scores over (anchor, class),
  * decode, concatenate levels, per-class NMS, max_per_image -- a host loop in the lineage.
  * p describes the head outputs with p->classes = C foreground classes and p->A = anchors_per_cell * C:

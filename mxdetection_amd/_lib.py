@@ -94,6 +94,12 @@ class AttnDescT(C.Structure):
                 ("v_off", c_i32), ("scale", c_f32)]
 
 
+class CarafeDescT(C.Structure):
+    """mxdet_carafe_desc_t (include/mxdet.h)."""
+    _fields_ = [("N", c_i32), ("H", c_i32), ("W", c_i32), ("C", c_i32), ("Cm", c_i32), ("k", c_i32), ("Hf", c_i32),
+                ("Wf", c_i32)]
+
+
 class RpnOrderedItemT(C.Structure):
     """mxdet_rpn_ordered_item_t (include/mxdet.h)."""
     _fields_ = [("kind", c_i32), ("H", c_i32), ("W", c_i32), ("halves_per_slab", c_i32), ("slab0", c_i32),
@@ -276,6 +282,8 @@ SIGNATURES = {
     "mxdet_attention_workspace_bytes": (c_sz, [P(AttnDescT)]),
     "mxdet_attention_fwd": (c_i32, [P(AttnDescT), c_vp, c_vp, c_vp, c_vp]),
     "mxdet_attention_bwd": (c_i32, [P(AttnDescT), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_carafe_fwd": (c_i32, [P(CarafeDescT), c_vp, c_vp, c_vp, c_vp]),
+    "mxdet_carafe_bwd": (c_i32, [P(CarafeDescT), c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "mxdet_add_bf16": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "mxdet_relu_bwd_bf16": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "mxdet_f32_to_bf16": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
@@ -319,6 +327,8 @@ SAMPLER_MAX_BINS = 8
 BFP_MAX_LEVELS = 6
 # head widths of the attention entries (mxdet_attn_desc_t.d)
 ATTN_HEAD_DIMS = (64, 128)
+# reassembly kernel sizes of the CARAFE entries (mxdet_carafe_desc_t.k)
+CARAFE_KERNELS = (3, 5)
 
 _lib = None
 

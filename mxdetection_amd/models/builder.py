@@ -29,11 +29,13 @@ def build_detector(cfg, device="cuda"):
         libra = dict(neck=str(net.neck), bfp_refine=str(net.bfp_refine), sampler=str(net.sampler), sampler_bins=net.sampler_bins,
                      bl1_alpha=net.bl1_alpha, bl1_gamma=net.bl1_gamma, bl1_beta=net.bl1_beta,
                      bfp_nl_reduction=net.bfp_nl_reduction, bfp_nl_use_scale=net.bfp_nl_use_scale)
+        carafe = dict(fpn_upsample=str(net.fpn_upsample), carafe_k=net.carafe_k, carafe_compress=net.carafe_compress,
+                      carafe_enc_kernel=net.carafe_enc_kernel)
         model = FasterRCNN(device, depth=net.backbone_depth, num_classes=net.num_classes, seed=net.seed,
                            rois_per_image=tr.batch_rois, pre_nms_top_n=tr.rpn_pre_nms_top_n,
                            post_nms_top_n=tr.rpn_post_nms_top_n, with_mask=(net.type == "mask_rcnn"), **dcn, **dpool, **heads,
                            **reg, mask_iou=bool(net.mask_iou), mask_iou_weight=net.mask_iou_weight, ohem=bool(net.ohem),
-                           ohem_nms=net.ohem_nms, **kpt, **libra)
+                           ohem_nms=net.ohem_nms, **kpt, **libra, **carafe)
     elif net.type == "retinanet":
         if net.ohem:
             raise ValueError("network.ohem = %r: retinanet has no box head to mine RoIs for (OHEM is a faster_rcnn / mask_rcnn "
@@ -52,6 +54,9 @@ def build_detector(cfg, device="cuda"):
         if net.bfp_nl_reduction != 2 or net.bfp_nl_use_scale:
             raise ValueError("network.bfp_nl_reduction / network.bfp_nl_use_scale = %r / %r: retinanet has no Balanced Feature "
                              "Pyramid to refine (faster_rcnn / mask_rcnn options)" % (net.bfp_nl_reduction, net.bfp_nl_use_scale))
+        if net.fpn_upsample != "nearest":
+            raise ValueError("network.fpn_upsample = %r: retinanet keeps its own pyramid, whose top-down path upsamples "
+                             "nearest-neighbour (CARAFE is a faster_rcnn / mask_rcnn option)" % (net.fpn_upsample,))
         if net.sampler != "random":
             raise ValueError("network.sampler = %r: retinanet has no RoI sampler (iou_balanced is a faster_rcnn / mask_rcnn "
                              "option)" % (net.sampler,))

@@ -13,7 +13,7 @@ from ..core.loss import check_balanced_l1, check_reg_loss
 from .backbones import ResNet
 from .bbox_heads import BBoxHead, ConvFCBBoxHead
 from .mask_heads import FCNMaskHead, KeypointHead, MaskIoUHead
-from .necks import BFP, FPN, check_neck
+from .necks import BFP, FPN, check_neck, check_upsample
 from .roi_extractors import DeformRoIExtractor, FPNRoIExtractor
 from .rpn_heads import RPNHead
 from .utils.detector import DetectorBase
@@ -48,7 +48,8 @@ class FasterRCNN(DetectorBase):
                  bbox_head="2fc", head_norm="none", gn_groups=32, reg_loss="smooth_l1", reg_loss_weight=1.0,
                  mask_iou=False, mask_iou_weight=1.0, ohem=False, ohem_nms=0.7, with_keypoints=False, num_keypoints=17,
                  keypoint_weight=1.0, neck="fpn", bfp_refine="conv", sampler="random", sampler_bins=3, bl1_alpha=0.5,
-                 bl1_gamma=1.5, bl1_beta=1.0, bfp_nl_reduction=2, bfp_nl_use_scale=False):
+                 bl1_gamma=1.5, bl1_beta=1.0, bfp_nl_reduction=2, bfp_nl_use_scale=False, fpn_upsample="nearest", carafe_k=5,
+                 carafe_compress=64, carafe_enc_kernel=3):
         """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
         roi_pool: the box branch's RoI pooling -- 'roi_align', or deformable RoI pooling with its offset head, 'dpool'
         (v1) / 'mdpool' (v2, modulated) (roi_extractors.DeformRoIExtractor, options dpool_*). The mask branch keeps its
@@ -76,7 +77,12 @@ class FasterRCNN(DetectorBase):
         bfp_nl_use_scale, 'none'); every head, the RPN and predict then read the balanced levels, and the refine layers draw
         from a generator of their own. sampler = 'iou_balanced' /
         sampler_bins -- the box head's background RoIs keep a quota per IoU bin (not with ohem). reg_loss = 'balanced_l1' /
-        bl1_alpha, bl1_gamma, bl1_beta -- Balanced L1 on the encoded deltas, times reg_loss_weight (not with ohem)."""
+        bl1_alpha, bl1_gamma, bl1_beta -- Balanced L1 on the encoded deltas, times reg_loss_weight (not with ohem).
+        fpn_upsample = 'carafe' / carafe_k, carafe_compress, carafe_enc_kernel: CARAFE (Wang et al. 2019) in place of the
+        FPN's nearest-neighbour top-down upsample (necks.FPN): per merge a 1x1 conv 256 -> carafe_compress (a multiple of 64)
+        and a carafe_enc_kernel (1 or 3) conv onto the 4 k^2 logits of a carafe_k x carafe_k (3 or 5) reassembly kernel. The
+        new layers draw from a generator of their own; composes with every other option, neck = 'bfp' included."""
+        check_upsample(fpn_upsample, carafe_k, carafe_compress, carafe_enc_kernel)
         check_neck(neck, bfp_refine, bfp_nl_reduction, bfp_nl_use_scale)
         check_head_options(bbox_head, head_norm, gn_groups, with_mask)
         if mask_iou and not with_mask:
@@ -153,7 +159,9 @@ class FasterRCNN(DetectorBase):
         self.bfp = BFP(256, self.arena, self.ws, device, torch.Generator().manual_seed(seed + 15485863),
                        refine=bfp_refine, nl_reduction=bfp_nl_reduction,
                        nl_use_scale=bool(bfp_nl_use_scale)) if neck == "bfp" else None
-        self.neck = FPN([256, 512, 1024, 2048], 256, self.arena, self.ws, device, gen)
+        self.neck = FPN([256, 512, 1024, 2048], 256, self.arena, self.ws, device, gen, upsample=fpn_upsample,
+                        carafe_k=carafe_k, carafe_compress=carafe_compress, carafe_enc_kernel=carafe_enc_kernel,
+                        carafe_gen=torch.Generator().manual_seed(seed + 32452843))
         self.mark_fpn = self.arena.size
         self.backbone = ResNet(depth, self.arena, self.ws, device, gen, dcn_stages=dcn_stages,
                                dcn_modulated=dcn_modulated, dcn_groups=dcn_groups)

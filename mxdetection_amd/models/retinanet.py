@@ -26,7 +26,7 @@ class RetinaNet(DetectorBase):
     def __init__(self, device="cuda", depth=101, num_classes=80, seed=7, dcn_stages=(), dcn_modulated=True, dcn_groups=1,
                  reg_loss="smooth_l1", reg_loss_weight=1.0, assigner="max_iou", atss_topk=9, anchor_ratios=(0.5, 1.0, 2.0),
                  anchor_scales_per_octave=3, anchor_scale=4.0, cls_loss="focal", cls_loss_alpha=None, cls_loss_gamma=None,
-                 reg_max=0, dfl_weight=0.25):
+                 reg_max=0, dfl_weight=0.25, fpn_upsample="nearest"):
         """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
         reg_loss / reg_loss_weight: the head's box loss -- 'smooth_l1', or 'iou' / 'giou' / 'diou' on the decoded box times
         reg_loss_weight (rpn_heads.RetinaHead).
@@ -38,7 +38,11 @@ class RetinaNet(DetectorBase):
         reg_max / dfl_weight: reg_max > 0 = the distribution box head of Generalized Focal Loss -- retina.box_out emits
         4 * (reg_max + 1) logits per anchor, the box is their integral decode (training and predict), the loss gains a third
         component dfl_weight * DFL (rpn_heads.RetinaHead; needs an IoU-family reg_loss). As published: 16, 0.25 with ATSS,
-        qfl and reg_loss_weight 2. The layout of retina.box_out depends on it; load_checkpoint refuses the other layout."""
+        qfl and reg_loss_weight 2. The layout of retina.box_out depends on it; load_checkpoint refuses the other layout.
+        fpn_upsample: 'nearest' only -- CARAFE is an option of the R-CNN models' FPN (necks.FPN), not of RetinaFPN."""
+        if fpn_upsample != "nearest":
+            raise ValueError("fpn_upsample = %r: RetinaNet's pyramid (RetinaFPN) upsamples nearest-neighbour only; CARAFE is "
+                             "a FasterRCNN option" % (fpn_upsample,))
         check_reg_loss(reg_loss, reg_loss_weight)
         check_reg_max(reg_max, reg_loss, dfl_weight)
         check_cls_loss(cls_loss, reg_loss, cls_loss_alpha, cls_loss_gamma)

@@ -71,6 +71,10 @@ DEFAULTS = {
         "bfp_refine": "conv",             # refine step of the balanced map: conv (one 3x3 convolution) | embedded_gaussian (the paper's non-local block) | none
         "bfp_nl_reduction": 2,            # embedded_gaussian: inner channels Ci = 256 / reduction; 2 or 4 (Ci = 128 or 64)
         "bfp_nl_use_scale": False,        # embedded_gaussian: logits times 1 / sqrt(Ci)
+        "fpn_upsample": "nearest",        # faster_rcnn / mask_rcnn: nearest | carafe (CARAFE in the FPN's top-down path; Wang et al. 2019)
+        "carafe_k": 5,                    # carafe: reassembly kernel, 3 | 5
+        "carafe_compress": 64,            # carafe: channels of the 1x1 compressor, a multiple of 64
+        "carafe_enc_kernel": 3,           # carafe: kernel of the logit encoder, 1 | 3
         "sampler": "random",              # box head's RoI sampler: random | iou_balanced (background quota per IoU bin; not with ohem)
         "sampler_bins": 3,                # IoU bins of the iou_balanced sampler (1..8)
         "bl1_alpha": 0.5,                 # Balanced L1 (reg_loss: balanced_l1, box head only; times reg_loss_weight): alpha ...
