@@ -1070,6 +1070,55 @@ int mxdet_carafe_fwd(const mxdet_carafe_desc_t* d, const uint16_t* X, const uint
 int mxdet_carafe_bwd(const mxdet_carafe_desc_t* d, const uint16_t* X, const uint16_t* M, const uint16_t* dY, uint16_t* dX,
                      uint16_t* dM, int32_t accumulate, mxdet_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * models/backbones -- the global context block of GCNet (Cao et al., GCNet: Non-local Networks Meet Squeeze-Excitation
+ * Networks and Beyond, ICCVW 2019): attention pooling, channel_add fusion, placed after a bottleneck's
+ * conv3 and in front of its shortcut add. t bf16 [N,HW,C] is conv3's output without residual or ReLU, sc bf16 the shortcut,
+ * P the transform's inner width. wk [C], W1 [P,C] and W2 [C,P] are bf16; b1, gamma, beta [P] and b2 [C] fp32.
+ *   pool_fwd       logits[n,p] = sum_c t[n,p,c] wk[c] (f32 [N,HW]; no bias: a softmax ignores a shift); per chunk of 64
+ *                  positions the online softmax (maximum, sum, weighted column sums) into the workspace.
+ *   transform_fwd  folds the chunks in a fixed order: lse[n] = max + ln sum exp(logit - max), ctx[n,c] = sum_p att t with
+ *                  att = exp(logit - lse) (f32 [N,C]); h = W1 ctx + b1 [N,P]; mean, rstd [N] of LayerNorm over the P values
+ *                  (biased variance, eps); u = relu(gamma (h - mean) rstd + beta); add = W2 u + b2 (f32 [N,C]).
+ *   fuse_fwd       y = bf16(relu((f32(t) + add[n,c]) + f32(sc))), one rounding; y_bits (may be null): the 1-bit mask of the
+ *                  stored y in the convolution entries' format (mxdet_conv_desc_t.relu_bits).
+ *   reduce_bwd     per chunk column sums of ds (the gradient at the pre-activation sum, already masked by y > 0).
+ *   transform_bwd  d_add[n,c] = sum_p ds (f32 [N,C]); dW2 = d_add^T u, db2 = sum_n d_add; du = d_add W2; gz = du (u > 0);
+ *                  dgamma = sum_n gz xh, dbeta = sum_n gz; gg = gz gamma; dh = rstd (gg - mean_P(gg) - xh mean_P(gg xh));
+ *                  dW1 = dh^T ctx, db1 = sum_n dh; d_ctx = dh W1 (f32 [N,C]). The six parameter gradients are fp32 in the
+ *                  parameters' shapes, overwritten or, with accumulate, added to.
+ *   pool_bwd       e[n,p] = sum_c d_ctx[n,c] t[n,p,c]; S[n] = sum_p att e; dl = att (e - S);
+ *                  d_t = bf16((f32(ds) + att d_ctx[n,c]) + dl wk[c]), one rounding; d_wk[c] (+)= sum_{n,p} dl t[n,p,c].
+ * All arithmetic is fp32; every summation order depends on the shape alone (DESIGN.md 5u lists them); no float atomics:
+ * the same bits run to run. The workspace carries the chunk partials from pool_fwd to transform_fwd, from reduce_bwd to
+ * transform_bwd and, inside transform_bwd and pool_bwd, between their kernels: one workspace per block, the calls of a
+ * step in the order above on one stream.
+ * Host checks before any launch: C % 8 == 0 in [8, 2048], P % 8 == 0 in [8, 512], 1 <= HW < 2^20, 1 <= N <= 65535,
+ * N HW C < 2^31 (MXDET_ESHAPE); eps in (0, 1), no null pointer (y_bits excepted), every pointer 16-byte aligned
+ * (MXDET_EINVAL); workspace (MXDET_EWORKSPACE). No allocation, no host synchronisation; capturable.
+ * mxdet_gc_workspace_bytes returns 0 for a descriptor that fails the checks. */
+typedef struct {
+  int32_t N, HW, C, P;
+  float eps;
+} mxdet_gc_desc_t;
+size_t mxdet_gc_workspace_bytes(const mxdet_gc_desc_t* d);
+int mxdet_gc_pool_fwd(const mxdet_gc_desc_t* d, const uint16_t* t, const uint16_t* wk, float* logits, void* workspace,
+                      size_t workspace_bytes, mxdet_stream_t stream);
+int mxdet_gc_transform_fwd(const mxdet_gc_desc_t* d, const uint16_t* W1, const float* b1, const float* gamma, const float* beta,
+                           const uint16_t* W2, const float* b2, float* lse, float* ctx, float* h, float* mean, float* rstd,
+                           float* add, const void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
+int mxdet_gc_fuse_fwd(const mxdet_gc_desc_t* d, const uint16_t* t, const float* add, const uint16_t* sc, uint16_t* y,
+                      uint8_t* y_bits, mxdet_stream_t stream);
+int mxdet_gc_reduce_bwd(const mxdet_gc_desc_t* d, const uint16_t* ds, void* workspace, size_t workspace_bytes,
+                        mxdet_stream_t stream);
+int mxdet_gc_transform_bwd(const mxdet_gc_desc_t* d, const uint16_t* W1, const float* gamma, const float* beta,
+                           const uint16_t* W2, const float* ctx, const float* h, const float* mean, const float* rstd,
+                           float* d_add, float* d_ctx, float* dW1, float* db1, float* dgamma, float* dbeta, float* dW2,
+                           float* db2, int32_t accumulate, void* workspace, size_t workspace_bytes, mxdet_stream_t stream);
+int mxdet_gc_pool_bwd(const mxdet_gc_desc_t* d, const uint16_t* t, const uint16_t* wk, const uint16_t* ds, const float* logits,
+                      const float* lse, const float* d_ctx, uint16_t* d_t, float* d_wk, int32_t accumulate, void* workspace,
+                      size_t workspace_bytes, mxdet_stream_t stream);
+
 /* One-stage (RetinaNet) test-time detection, MXNet-lineage role: per level top-k of sigmoid scores over (anchor, class),
  * decode, concatenate levels, per-class NMS, max_per_image -- a host loop in the lineage.
  * p describes the head outputs with p->classes = C foreground classes and p->A = anchors_per_cell * C:

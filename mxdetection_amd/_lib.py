@@ -100,6 +100,11 @@ class CarafeDescT(C.Structure):
                 ("Wf", c_i32)]
 
 
+class GcDescT(C.Structure):
+    """mxdet_gc_desc_t (include/mxdet.h)."""
+    _fields_ = [("N", c_i32), ("HW", c_i32), ("C", c_i32), ("P", c_i32), ("eps", c_f32)]
+
+
 class RpnOrderedItemT(C.Structure):
     """mxdet_rpn_ordered_item_t (include/mxdet.h)."""
     _fields_ = [("kind", c_i32), ("H", c_i32), ("W", c_i32), ("halves_per_slab", c_i32), ("slab0", c_i32),
@@ -284,6 +289,13 @@ SIGNATURES = {
     "mxdet_attention_bwd": (c_i32, [P(AttnDescT), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mxdet_carafe_fwd": (c_i32, [P(CarafeDescT), c_vp, c_vp, c_vp, c_vp]),
     "mxdet_carafe_bwd": (c_i32, [P(CarafeDescT), c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "mxdet_gc_workspace_bytes": (c_sz, [P(GcDescT)]),
+    "mxdet_gc_pool_fwd": (c_i32, [P(GcDescT), c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_gc_transform_fwd": (c_i32, [P(GcDescT)] + [c_vp] * 13 + [c_sz, c_vp]),
+    "mxdet_gc_fuse_fwd": (c_i32, [P(GcDescT), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mxdet_gc_reduce_bwd": (c_i32, [P(GcDescT), c_vp, c_vp, c_sz, c_vp]),
+    "mxdet_gc_transform_bwd": (c_i32, [P(GcDescT)] + [c_vp] * 16 + [c_i32, c_vp, c_sz, c_vp]),
+    "mxdet_gc_pool_bwd": (c_i32, [P(GcDescT)] + [c_vp] * 8 + [c_i32, c_vp, c_sz, c_vp]),
     "mxdet_add_bf16": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "mxdet_relu_bwd_bf16": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "mxdet_f32_to_bf16": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
@@ -329,6 +341,9 @@ BFP_MAX_LEVELS = 6
 ATTN_HEAD_DIMS = (64, 128)
 # reassembly kernel sizes of the CARAFE entries (mxdet_carafe_desc_t.k)
 CARAFE_KERNELS = (3, 5)
+# positions per workgroup of the global context entries' map kernels (kGcChunk in csrc/context.hip) and their bounds
+GC_CHUNK = 64
+GC_MAX_C, GC_MAX_P = 2048, 512
 
 _lib = None
 

@@ -11,7 +11,7 @@ import os
 import torch
 
 from ...ops import dense
-from ..utils.layers import ConvLayer, DeformConvLayer, cached_buf
+from ..utils.layers import ContextBlock, ConvLayer, DeformConvLayer, cached_buf
 
 
 BITMASKS = os.environ.get("MXDET_TUNE_RELU_BITS", "1") == "1"      # 1-bit ReLU masks for the backbone's data gradients
@@ -21,11 +21,46 @@ CHAIN_FROZEN = os.environ.get("MXDET_TUNE_CHAIN", "1") != "0"
 CHAIN3_FROZEN = os.environ.get("MXDET_TUNE_CHAIN", "2") not in ("0", "1")
 
 
+STAGE_CHANNELS = {3: 512, 4: 1024, 5: 2048}      # output channels of C3..C5
+
+
+def check_gcb(gcb_stages=(), gcb_reduction=16, frozen_stages=1):
+    """The global context options of ResNet, checked before anything is allocated; -> the sorted stages. The reduction is
+    looked at only when a stage is chosen: without one it has no meaning, and a model without blocks takes any value."""
+    try:
+        stages = set(int(s) for s in gcb_stages)
+    except (TypeError, ValueError):
+        raise ValueError("gcb_stages %r: expected a list of stages among 3, 4, 5" % (gcb_stages,))
+    bad = [s for s in stages if s not in (3, 4, 5) or s - 2 < max(1, frozen_stages)]
+    if bad:
+        raise ValueError("gcb_stages %s: only trainable stages among 3, 4, 5" % sorted(bad))
+    if not stages:
+        return []
+    r = gcb_reduction
+    if not isinstance(r, int) or isinstance(r, bool) or r <= 0:
+        raise ValueError("gcb_reduction must be a positive integer (got %r)" % (r,))
+    for s in sorted(stages):
+        C = STAGE_CHANNELS[s]
+        if C % r or (C // r) % 8 or not 8 <= C // r <= 512:
+            raise ValueError("gcb_reduction = %r: stage %d has %d channels, and %d / %r must be a multiple of 8 in [8, 512]"
+                             % (r, s, C, C, r))
+    return sorted(stages)
+
+
 class Bottleneck:
-    def __init__(self, name, cin, planes, stride, downsample, trainable, need_dx, arena, ws, device, gen, dcn=None):
-        """dcn: None, or {"groups": G, "modulated": bool} -- conv2 is then a deformable convolution (trainable blocks)."""
+    def __init__(self, name, cin, planes, stride, downsample, trainable, need_dx, arena, ws, device, gen, dcn=None, gcb=None):
+        """dcn: None, or {"groups": G, "modulated": bool} -- conv2 is then a deformable convolution (trainable blocks).
+        gcb: None, or {"reduction": r, "gen": generator} -- a global context block (utils.layers.ContextBlock) between conv3
+        and the shortcut add: conv3 then runs without residual and ReLU into a buffer `t`, and the block's fused pass writes
+        y = relu(t + add + shortcut) and its 1-bit mask."""
         kw = dict(arena=arena, ws=ws, device=device, gen=gen, trainable=trainable, train_bias=False)
         self.trainable, self.need_dx = trainable, need_dx
+        # the context block's gradients complete before conv3's: registered first
+        self.gcb = None
+        if gcb is not None:
+            assert trainable, "global context blocks only in trainable stages"
+            self.gcb = ContextBlock(name + ".gc", planes * 4, gcb["reduction"], arena, device, gcb["gen"])
+        self.t = None
         # registered in backward completion order: conv3, conv2 (+ its offset conv), conv1 / downsample
         # random-init stand-in for pretrained weights: the residual branch's last conv starts small so that
         # activations stay O(1) through 16 blocks without live BatchNorm statistics (frozen BN is identity here)
@@ -58,7 +93,10 @@ class Bottleneck:
         self.conv3.plan(s2)
         if self.down is not None:
             self.down.plan(x_shape)
-        return self.conv3.out_shape(s2)
+        so = self.conv3.out_shape(s2)
+        if self.gcb is not None:
+            self.gcb.plan(so[0], so[1] * so[2])
+        return so
 
     def _bits(self, key, shape):
         return cached_buf(self.bufs, key, shape[:3] + (shape[3] // 8,), torch.uint8, self.conv1.device)
@@ -111,6 +149,10 @@ class Bottleneck:
             self.y = r[0] if nb is not None else r
             return self.y
         self.a2 = self.conv2.forward(self.a1, relu=True, out=self._buf("a2", s2), bits_out=self.a2_bits)
+        if self.gcb is not None:
+            self.t = self.conv3.forward(self.a2, out=self._buf("t", oshape))
+            self.y = self.gcb.forward(self.t, sc, self._buf(self.y_key, oshape), self.y_bits)
+            return self.y
         self.y = self.conv3.forward(self.a2, relu=True, residual=sc, out=self._buf(self.y_key, oshape), bits_out=self.y_bits)
         return self.y
 
@@ -121,8 +163,12 @@ class Bottleneck:
         masked by (x > 0); if dx_has_grad it already holds a partial gradient (FPN lateral) to add to.
         """
         c1, c2, c3 = self.conv1, self.conv2, self.conv3
-        c3.backward_weight(self.a2, ds)
-        d_a2 = c3.backward_data(ds, self.a2.shape, relu_mask=self.a2, out=self._buf("d_a2", self.a2.shape),
+        d_t = ds
+        if self.gcb is not None:
+            # a buffer of its own: the deferred weight gradient of conv3 reads it at the bucket's flush
+            d_t = self.gcb.backward(self.t, ds, self._buf("d_t", ds.shape))
+        c3.backward_weight(self.a2, d_t)
+        d_a2 = c3.backward_data(d_t, self.a2.shape, relu_mask=self.a2, out=self._buf("d_a2", self.a2.shape),
                                 relu_bits=self.a2_bits)
         c2.backward_weight(self.a1, d_a2)
         d_a1 = c2.backward_data(d_a2, self.a1.shape, relu_mask=self.a1, out=self._buf("d_a1", self.a1.shape),
@@ -148,9 +194,18 @@ class Bottleneck:
 class ResNet:
     """depth 50: (3,4,6,3), depth 101: (3,4,23,3). Returns C2..C5 (bf16 channels-last)."""
 
-    def __init__(self, depth, arena, ws, device, gen, frozen_stages=1, dcn_stages=(), dcn_modulated=True, dcn_groups=1):
+    def __init__(self, depth, arena, ws, device, gen, frozen_stages=1, dcn_stages=(), dcn_modulated=True, dcn_groups=1,
+                 gcb_stages=(), gcb_reduction=16, gcb_gen=None):
         """dcn_stages: subset of {3, 4, 5} (C3..C5, trainable stages only) whose blocks use a deformable conv2 (DCN v2
-        with dcn_modulated, else v1; dcn_groups deformable groups), the stride-2 first block included."""
+        with dcn_modulated, else v1; dcn_groups deformable groups), the stride-2 first block included.
+        gcb_stages / gcb_reduction: subset of the trainable stages among 3, 4, 5 whose blocks -- every one -- get a global
+        context block (GCNet) with inner width C / gcb_reduction (a multiple of 8, at most 512); composes with dcn_stages.
+        gcb_gen: the generator the blocks draw from (required with gcb_stages), so every other parameter starts exactly as
+        without the option."""
+        self.gcb_stages = check_gcb(gcb_stages, gcb_reduction, frozen_stages)
+        if self.gcb_stages and gcb_gen is None:
+            raise ValueError("ResNet(gcb_stages=%s) needs gcb_gen, the generator the context blocks draw from" % self.gcb_stages)
+        gcb = {"reduction": gcb_reduction, "gen": gcb_gen}
         blocks = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3)}[depth]
         self.device = device
         dcn_stages = set(int(s) for s in dcn_stages)
@@ -172,7 +227,8 @@ class ResNet:
                 need_dx = trainable and not (bi == 0 and (si == 0 or si - 1 < frozen_stages))
                 stage.insert(0, Bottleneck("layer%d.%d" % (si + 1, bi), cin, planes, stride, bi == 0, trainable,
                                            need_dx, arena, ws, device, gen,
-                                           dcn=dcn if si + 2 in dcn_stages else None))
+                                           dcn=dcn if si + 2 in dcn_stages else None,
+                                           gcb=gcb if si + 2 in self.gcb_stages else None))
             self.stages[si] = stage
         self.stem_w = (torch.randn((64, 7, 7, 3), generator=gen) * (2.0 / 147) ** 0.5).to(torch.bfloat16).to(device)
         self.stem_b = torch.zeros((64,), dtype=torch.float32, device=device)
@@ -184,6 +240,10 @@ class ResNet:
 
     def layers(self):
         return [l for st in self.stages for b in st for l in b.layers()]
+
+    def norm_layers(self):
+        """The global context blocks (arena parameters that are no ConvLayer), for the detector's `norm_layers`."""
+        return [b.gcb for st in self.stages for b in st if b.gcb is not None]
 
     def plan(self, image_shape):
         N, _, H, W = image_shape

@@ -5,7 +5,8 @@ neck, heads named in an experiment file, /root/reference/README.md:7,13)."""
 def build_detector(cfg, device="cuda"):
     from . import FasterRCNN, RetinaNet
     net, tr = cfg.network, cfg.TRAIN
-    dcn = dict(dcn_stages=tuple(net.dcn_stages), dcn_modulated=bool(net.dcn_modulated), dcn_groups=int(net.dcn_groups))
+    dcn = dict(dcn_stages=tuple(net.dcn_stages), dcn_modulated=bool(net.dcn_modulated), dcn_groups=int(net.dcn_groups),
+               gcb_stages=tuple(net.gcb_stages), gcb_reduction=net.gcb_reduction)
     reg = dict(reg_loss=str(net.reg_loss), reg_loss_weight=net.reg_loss_weight)
     if net.type in ("faster_rcnn", "mask_rcnn"):
         if net.cls_loss != "focal":

@@ -11,6 +11,7 @@ from ..core import mask as M_
 from ..core.bbox import check_ohem, check_sampler
 from ..core.loss import check_balanced_l1, check_reg_loss
 from .backbones import ResNet
+from .backbones.resnet import check_gcb
 from .bbox_heads import BBoxHead, ConvFCBBoxHead
 from .mask_heads import FCNMaskHead, KeypointHead, MaskIoUHead
 from .necks import BFP, FPN, check_neck, check_upsample
@@ -49,8 +50,14 @@ class FasterRCNN(DetectorBase):
                  mask_iou=False, mask_iou_weight=1.0, ohem=False, ohem_nms=0.7, with_keypoints=False, num_keypoints=17,
                  keypoint_weight=1.0, neck="fpn", bfp_refine="conv", sampler="random", sampler_bins=3, bl1_alpha=0.5,
                  bl1_gamma=1.5, bl1_beta=1.0, bfp_nl_reduction=2, bfp_nl_use_scale=False, fpn_upsample="nearest", carafe_k=5,
-                 carafe_compress=64, carafe_enc_kernel=3):
+                 carafe_compress=64, carafe_enc_kernel=3, gcb_stages=(), gcb_reduction=16):
         """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
+        gcb_stages / gcb_reduction: GCNet (Cao et al. 2019) -- a global context block (attention pooling, a bottleneck
+        transform C -> C / gcb_reduction -> C with LayerNorm, broadcast add) in every bottleneck of those backbone stages
+        (trainable ones among 3, 4, 5), after conv3 and in front of the shortcut add, on fused kernels (backbones.ResNet,
+        utils.layers.ContextBlock); 16 and 4 are the published reductions. The blocks draw from a generator of their own and
+        start as the identity (their last layer is zero), so every other parameter starts exactly as in the model without
+        them; composes with dcn_stages and every other option.
         roi_pool: the box branch's RoI pooling -- 'roi_align', or deformable RoI pooling with its offset head, 'dpool'
         (v1) / 'mdpool' (v2, modulated) (roi_extractors.DeformRoIExtractor, options dpool_*). The mask branch keeps its
         14x14 RoIAlign.
@@ -83,6 +90,7 @@ class FasterRCNN(DetectorBase):
         and a carafe_enc_kernel (1 or 3) conv onto the 4 k^2 logits of a carafe_k x carafe_k (3 or 5) reassembly kernel. The
         new layers draw from a generator of their own; composes with every other option, neck = 'bfp' included."""
         check_upsample(fpn_upsample, carafe_k, carafe_compress, carafe_enc_kernel)
+        check_gcb(gcb_stages, gcb_reduction)
         check_neck(neck, bfp_refine, bfp_nl_reduction, bfp_nl_use_scale)
         check_head_options(bbox_head, head_norm, gn_groups, with_mask)
         if mask_iou and not with_mask:
@@ -164,7 +172,8 @@ class FasterRCNN(DetectorBase):
                         carafe_gen=torch.Generator().manual_seed(seed + 32452843))
         self.mark_fpn = self.arena.size
         self.backbone = ResNet(depth, self.arena, self.ws, device, gen, dcn_stages=dcn_stages,
-                               dcn_modulated=dcn_modulated, dcn_groups=dcn_groups)
+                               dcn_modulated=dcn_modulated, dcn_groups=dcn_groups, gcb_stages=gcb_stages,
+                               gcb_reduction=gcb_reduction, gcb_gen=torch.Generator().manual_seed(seed + 49979687))
         self.roi_extractor = self.dpool if self.dpool is not None else FPNRoIExtractor(self.strides[:4], device=device)
         self.bbox_head.ohem_extractor = self.roi_extractor
         layers = self.bbox_head.layers() + (self.dpool.layers() if self.dpool is not None else [])
@@ -178,7 +187,7 @@ class FasterRCNN(DetectorBase):
             norms = self.mask_head.norm_layers() + norms
         if self.keypoint_head is not None:
             layers = self.keypoint_head.layers() + layers
-        self._finalize_params(layers, norm_layers=norms)
+        self._finalize_params(layers, norm_layers=norms + self.backbone.norm_layers())
 
     def plan(self, N, H, W, g_max):
         key = (N, H, W, g_max)

@@ -4,6 +4,7 @@ import torch
 
 from ..core.loss import check_cls_loss, check_reg_loss, check_reg_max
 from .backbones import ResNet
+from .backbones.resnet import check_gcb
 from .necks.fpn import RetinaFPN
 from .rpn_heads.retina_head import RetinaHead, check_assigner
 from .utils.detector import DetectorBase
@@ -26,8 +27,10 @@ class RetinaNet(DetectorBase):
     def __init__(self, device="cuda", depth=101, num_classes=80, seed=7, dcn_stages=(), dcn_modulated=True, dcn_groups=1,
                  reg_loss="smooth_l1", reg_loss_weight=1.0, assigner="max_iou", atss_topk=9, anchor_ratios=(0.5, 1.0, 2.0),
                  anchor_scales_per_octave=3, anchor_scale=4.0, cls_loss="focal", cls_loss_alpha=None, cls_loss_gamma=None,
-                 reg_max=0, dfl_weight=0.25, fpn_upsample="nearest"):
+                 reg_max=0, dfl_weight=0.25, fpn_upsample="nearest", gcb_stages=(), gcb_reduction=16):
         """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
+        gcb_stages / gcb_reduction: a global context block (GCNet) with inner width C / gcb_reduction in every bottleneck of
+        those backbone stages (backbones.ResNet); the blocks draw from a generator of their own.
         reg_loss / reg_loss_weight: the head's box loss -- 'smooth_l1', or 'iou' / 'giou' / 'diou' on the decoded box times
         reg_loss_weight (rpn_heads.RetinaHead).
         assigner / atss_topk: 'max_iou' (thresholds 0.5 / 0.4) or 'atss' (core.anchor.atss_assign).
@@ -43,6 +46,7 @@ class RetinaNet(DetectorBase):
         if fpn_upsample != "nearest":
             raise ValueError("fpn_upsample = %r: RetinaNet's pyramid (RetinaFPN) upsamples nearest-neighbour only; CARAFE is "
                              "a FasterRCNN option" % (fpn_upsample,))
+        check_gcb(gcb_stages, gcb_reduction)
         check_reg_loss(reg_loss, reg_loss_weight)
         check_reg_max(reg_max, reg_loss, dfl_weight)
         check_cls_loss(cls_loss, reg_loss, cls_loss_alpha, cls_loss_gamma)
@@ -60,8 +64,10 @@ class RetinaNet(DetectorBase):
         self.neck = RetinaFPN([512, 1024, 2048], 256, self.arena, self.ws, device, gen)
         self.mark_fpn = self.arena.size
         self.backbone = ResNet(depth, self.arena, self.ws, device, gen, dcn_stages=dcn_stages,
-                               dcn_modulated=dcn_modulated, dcn_groups=dcn_groups)
-        self._finalize_params(self.head.layers() + self.neck.layers() + self.backbone.layers())
+                               dcn_modulated=dcn_modulated, dcn_groups=dcn_groups, gcb_stages=gcb_stages,
+                               gcb_reduction=gcb_reduction, gcb_gen=torch.Generator().manual_seed(seed + 49979687))
+        self._finalize_params(self.head.layers() + self.neck.layers() + self.backbone.layers(),
+                              norm_layers=self.backbone.norm_layers())
         self.head.post_materialize()
 
     def plan(self, N, H, W, g_max):

@@ -310,6 +310,80 @@ class GroupNormLayer:
                                       out=out, workspace=self.plan(self.x.shape)[3])
 
 
+class ContextBlock:
+    """The global context block of GCNet (Cao et al. 2019; ops/context.py) between a bottleneck's conv3
+    and its shortcut add: attention pooling of t = conv3's output, Linear C -> P = C / reduction, LayerNorm, ReLU, Linear
+    P -> C, and y = relu(t + add + shortcut) in one fused pass.
+
+    Seven arena entries, registered in the order their gradients complete: `<name>.fc2.weight` [C,P], `.fc2.bias` [C],
+    `.ln.gamma` [P], `.ln.beta` [P], `.fc1.weight` [P,C], `.fc1.bias` [P], `.mask.weight` [C] (the 1x1 attention filter; it has
+    no bias: a softmax ignores a shift). The kernels read the three filters from the arena's bf16 working copy and the four
+    1-D arrays from the fp32 master. fc2 starts at zero, so a new block computes relu(t + shortcut); the mask filter and fc1 are
+    He-normal draws from `gen`, the blocks' own generator; gamma = 1, beta = 0, fc1.bias = 0.
+    Like GroupNormLayer it is no ConvLayer: detectors keep it in `norm_layers`, and backward() writes its gradients into the
+    arena's gradient slice on the CURRENT stream, before the bucket that holds them is closed (GroupNormLayer's docstring
+    gives the ordering argument)."""
+    trainable = True
+    PARTS = ("fc2.weight", "fc2.bias", "ln.gamma", "ln.beta", "fc1.weight", "fc1.bias", "mask.weight")
+
+    def __init__(self, name, C, reduction, arena, device="cuda", gen=None, eps=1e-5):
+        from ...ops import context
+        if not isinstance(reduction, int) or isinstance(reduction, bool) or reduction <= 0 or C % reduction:
+            raise ValueError("global context block %s: reduction %r does not divide %d channels" % (name, reduction, C))
+        P = C // reduction
+        context.check_shape(C, P)
+        self.name, self.C, self.P, self.eps = name, C, P, eps
+        self.arena, self.device = arena, device
+        shapes = {"fc2.weight": (C, P), "fc2.bias": (C,), "ln.gamma": (P,), "ln.beta": (P,), "fc1.weight": (P, C),
+                  "fc1.bias": (P,), "mask.weight": (C,)}
+        self.idx = {p: arena.register("%s.%s" % (name, p), shapes[p]) for p in self.PARTS}
+        std = math.sqrt(2.0 / C)
+        self._w0 = {"mask.weight": torch.randn((C,), generator=gen) * std, "fc1.weight": torch.randn((P, C), generator=gen) * std}
+        self.plans = {}
+        self.plan_ = None
+
+    def materialize(self):
+        for p, i in self.idx.items():
+            w = self.arena.view(i, "w")
+            if p in self._w0:
+                w.copy_(self._w0[p].to(self.device))
+            else:
+                w.fill_(1.0 if p == "ln.gamma" else 0.0)
+        self._w0 = None
+
+    def named_params(self):
+        return [("%s.%s" % (self.name, p), self.idx[p]) for p in self.PARTS]
+
+    def _v(self, part, which):
+        return self.arena.view(self.idx[part], which)
+
+    def plan(self, N, HW):
+        """The plan (descriptor, statistics, workspace) for maps of N x HW positions: made at the first call for a shape."""
+        p = self.plans.get((N, HW))
+        if p is None:
+            from ...ops.context import ContextPlan
+            p = self.plans[(N, HW)] = ContextPlan(N, HW, self.C, self.P, self.device, self.eps)
+        return p
+
+    def forward(self, t, sc, out, bits_out=None):
+        """out = bf16(relu(t + add + sc)) (and its 1-bit mask); t, sc, out bf16 [N,H,W,C]."""
+        p = self.plan_ = self.plan(t.shape[0], t.shape[1] * t.shape[2])
+        p.pool_forward(t, self._v("mask.weight", "wb"))
+        p.transform_forward(self._v("fc1.weight", "wb"), self._v("fc1.bias", "w"), self._v("ln.gamma", "w"), self._v("ln.beta", "w"),
+                            self._v("fc2.weight", "wb"), self._v("fc2.bias", "w"))
+        return p.fuse_forward(t, sc, out, bits_out)
+
+    def backward(self, t, ds, d_t):
+        """d_t: the gradient w.r.t. t (ds is that of the pre-activation sum, already masked); the seven parameter gradients
+        go to the arena's gradient slice."""
+        p = self.plan_
+        p.reduce_backward(ds)
+        p.transform_backward(self._v("fc1.weight", "wb"), self._v("ln.gamma", "w"), self._v("ln.beta", "w"),
+                             self._v("fc2.weight", "wb"), self._v("fc1.weight", "g"), self._v("fc1.bias", "g"),
+                             self._v("ln.gamma", "g"), self._v("ln.beta", "g"), self._v("fc2.weight", "g"), self._v("fc2.bias", "g"))
+        return p.pool_backward(t, self._v("mask.weight", "wb"), ds, d_t, self._v("mask.weight", "g"))
+
+
 def fc_ksplit():
     """MXDET_TUNE_FC1_KSPLIT (read when a head is built, never in a step): the split of fc_forward, 1 = never split."""
     return int(os.environ.get("MXDET_TUNE_FC1_KSPLIT", "4"))

@@ -41,6 +41,8 @@ DEFAULTS = {
         "dcn_stages": [],                 # backbone stages (subset of 3, 4, 5) whose conv2 is deformable (contrib.DeformableConvolution)
         "dcn_modulated": True,            # DCN v2 (sigmoid mask) when true, v1 otherwise
         "dcn_groups": 1,                  # deformable groups
+        "gcb_stages": [],                 # backbone stages (subset of 3, 4, 5) whose bottlenecks get a global context block (GCNet; Cao et al. 2019)
+        "gcb_reduction": 16,              # inner width of the block's transform = C / gcb_reduction (a multiple of 8, at most 512); published: 16 | 4
         "roi_pool": "roi_align",          # box branch pooling: roi_align | dpool | mdpool (contrib.DeformablePSROIPooling)
         "dpool_trans_std": 0.1,           # scale of the predicted bin offsets (in roi widths / heights)
         "dpool_sample_per_part": 4,       # samples per bin and axis

@@ -14,8 +14,9 @@ padded to 1344, weight gradients grouped on a side stream, RPN branch on its own
     python tools/bench_dcn.py --dcn-stages '' --neck bfp --sampler iou_balanced --reg-loss balanced_l1     # Libra R-CNN
     python tools/bench_dcn.py --dcn-stages '' --neck bfp --bfp-refine embedded_gaussian --sampler iou_balanced --reg-loss balanced_l1     # ... with the paper's non-local refine
     python tools/bench_dcn.py --dcn-stages '' --fpn-upsample carafe     # CARAFE in the FPN's top-down path
+    python tools/bench_dcn.py --dcn-stages '' --gcb-stages 3,4,5 --gcb-reduction 16     # GCNet's global context blocks in C3..C5
 
-Prints one JSON line: {"dcn_stages", "modulated", "groups", "roi_pool", "mask", "mask_iou", "ohem", "keypoints", "neck", "bfp_refine", "fpn_upsample", "sampler", "img_per_s", "step_ms", "losses"}.
+Prints one JSON line: {"dcn_stages", "modulated", "groups", "roi_pool", "mask", "mask_iou", "ohem", "keypoints", "neck", "bfp_refine", "fpn_upsample", "gcb_stages", "gcb_reduction", "sampler", "img_per_s", "step_ms", "losses"}.
 """
 import argparse
 import json
@@ -52,6 +53,8 @@ def main():
     ap.add_argument("--bfp-nl-use-scale", type=int, default=0, choices=(0, 1))
     ap.add_argument("--fpn-upsample", default="nearest", choices=("nearest", "carafe"),
                     help="carafe = CARAFE in the FPN's top-down path (k 5, compressor 64, encoder 3 x 3)")
+    ap.add_argument("--gcb-stages", default="", help="comma-separated subset of 3,4,5 whose bottlenecks get a global context block")
+    ap.add_argument("--gcb-reduction", type=int, default=16, help="inner width of the blocks = C / reduction (published: 16, 4)")
     ap.add_argument("--sampler", default="random", choices=("random", "iou_balanced"))
     ap.add_argument("--sampler-bins", type=int, default=3)
     ap.add_argument("--steps", type=int, default=30)
@@ -63,6 +66,7 @@ def main():
     from bench import BATCH_PER_GPU, IM_H, PAD_W, synth_batch
     from mxdetection_amd.models import FasterRCNN
     stages = tuple(int(s) for s in args.dcn_stages.split(",") if s.strip())
+    gcb_stages = tuple(int(s) for s in args.gcb_stages.split(",") if s.strip())
     device = "cuda"
     model = FasterRCNN(device, depth=50, seed=7, dcn_stages=stages, dcn_modulated=bool(args.modulated),
                        dcn_groups=args.groups, roi_pool=args.roi_pool, bbox_head=args.bbox_head,
@@ -71,7 +75,8 @@ def main():
                        mask_iou_weight=args.mask_iou_weight, ohem=bool(args.ohem), ohem_nms=args.ohem_nms,
                        with_keypoints=bool(args.keypoints), neck=args.neck, bfp_refine=args.bfp_refine, sampler=args.sampler,
                        sampler_bins=args.sampler_bins, bfp_nl_reduction=args.bfp_nl_reduction,
-                       bfp_nl_use_scale=bool(args.bfp_nl_use_scale), fpn_upsample=args.fpn_upsample)
+                       bfp_nl_use_scale=bool(args.bfp_nl_use_scale), fpn_upsample=args.fpn_upsample,
+                       gcb_stages=gcb_stages, gcb_reduction=args.gcb_reduction)
     model.enable_wgrad_stream()
     model.enable_branch_stream()
     model.enable_grouped_wgrad()
@@ -113,7 +118,7 @@ def main():
     dt = time.perf_counter() - t0
     vals = [float(v) for v in torch.cat(list(losses)).cpu().numpy()]
     print(json.dumps({"dcn_stages": list(stages), "modulated": bool(args.modulated), "groups": args.groups,
-                      "roi_pool": args.roi_pool, "mask": bool(args.mask), "mask_iou": bool(args.mask_iou), "ohem": bool(args.ohem), "keypoints": bool(args.keypoints), "neck": args.neck, "bfp_refine": args.bfp_refine, "fpn_upsample": args.fpn_upsample, "sampler": args.sampler, "bbox_head": args.bbox_head, "head_norm": args.head_norm,
+                      "roi_pool": args.roi_pool, "mask": bool(args.mask), "mask_iou": bool(args.mask_iou), "ohem": bool(args.ohem), "keypoints": bool(args.keypoints), "neck": args.neck, "bfp_refine": args.bfp_refine, "fpn_upsample": args.fpn_upsample, "gcb_stages": list(gcb_stages), "gcb_reduction": args.gcb_reduction, "sampler": args.sampler, "bbox_head": args.bbox_head, "head_norm": args.head_norm,
                       "reg_loss": args.reg_loss,
                       "img_per_s": round(BATCH_PER_GPU * args.steps / dt, 2),
                       "step_ms": round(1e3 * dt / args.steps, 3), "losses": vals}), flush=True)
