@@ -129,6 +129,19 @@ __device__ __forceinline__ int xcd_tile_order(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
+// Grouped launches: one grid for the workgroups of `n` table entries, entry i owning those from table[i].*First on
+// (First non-decreasing in i, table[0].*First == 0). Index of the entry that owns workgroup `bid`: the last one whose
+// First is <= bid. A workgroup past that entry's count is alignment padding; the caller tests for it.
+template <typename T, int T::*First>
+__device__ __forceinline__ int table_lookup(const T* table, int n, int bid) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (table[mid].*First <= bid) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
 // exact floor(n / d) and remainder for 0 <= n < 2^24 through one float multiply + a +-1 correction (an integer division
 // is ~40 instructions): the tile prologues do two per row
 __device__ __forceinline__ int fast_divmod(int n, int d, float rcp, int* rem) {

@@ -824,12 +824,8 @@ struct ConvG {
 template <int BM, int BN, int WM, int WN, int NS, bool DGRAD, int TAPS = 0>
 __global__ void __launch_bounds__(64 * WM * WN)
 conv_igemm_grouped_kernel(const ConvG* __restrict__ table, int n) {
-  int lo = 0, hi = n - 1;
   const int bid = (int)blockIdx.x;
-  while (lo < hi) {
-    int mid = (lo + hi + 1) >> 1;
-    if (table[mid].block0 <= bid) lo = mid; else hi = mid - 1;
-  }
+  const int lo = table_lookup<ConvG, &ConvG::block0>(table, n, bid);
   const int b = bid - table[lo].block0;
   const int nb = table[lo].nblocks;
   if (b >= nb) return;                      // alignment padding between items

@@ -2,8 +2,9 @@
 the kernel instantiation it is named after.
 
 The library's route probe (mxdet_debug_route_probe, include/mxdet_debug.h) makes the launchers record the instantiation
-and grid they would launch and return before touching the device, so the real selector (conv.hip launch(), wgrad.hip
-plan_wgrad()) is asked, not re-stated here. tests/test_gpu_conv_routes.py runs the same tables on the GPU against fp64.
+and grid they would launch and return before touching the device, so the real selector (conv.hip launch(); wgrad.hip
+plan_wgrad() / single_split() for one call, grouped_split() / group_three_tap_steps() for a group) is asked, not re-stated
+here. tests/test_gpu_conv_routes.py runs the same tables on the GPU against fp64.
 
 A route is written  "BMxBN/WMxWN/NS fwd|dgrad [par] T<taps> [chain<C>]"  (T0 = run-time geometry K loop, T1 / T9 = the
 unrolled static-tap loops). Tuning keys, the forced configuration and the forced split are always changed inside
