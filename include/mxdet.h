@@ -325,7 +325,8 @@ int mxdet_roi_align_bwd(const mxdet_feat_pyramid_t* f, int32_t N, int32_t C, con
  * run, last-bit different from the sample-by-sample order of mxdet_roi_align_bwd. Requires sampling_ratio > 0 and at
  * most 32 samples per axis. The per-roi records the gather reads depend only on the rois: `_prepare` writes them into
  * the workspace (it can be issued as soon as the rois exist, e.g. in the forward pass) and `_prepared` is the gather
- * without that pass; the plain call does both. */
+ * without that pass; the plain call does both. R = 0 is the limit of the definition: all-zero maps (accumulate = 0) or
+ * untouched ones (accumulate = 1); rois, levels and grad_out may be null then, the workspace (sized for R = 0) may not. */
 size_t mxdet_roi_align_bwd_gather_workspace_bytes(const mxdet_feat_pyramid_t* f, int32_t N, int64_t R);
 int mxdet_roi_align_bwd_gather(const mxdet_feat_pyramid_t* f, int32_t N, int32_t C, const float* rois,
                                const int32_t* levels, int64_t R, int32_t PH, int32_t PW, int32_t sampling_ratio,

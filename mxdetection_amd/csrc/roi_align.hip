@@ -688,11 +688,11 @@ static size_t roi_gather_carve(const FeatPyr& d, long long R, RoiRows* rr, size_
 }
 
 extern "C" size_t mxdet_roi_align_bwd_gather_workspace_bytes(const mxdet_feat_pyramid_t* f, int32_t N, int64_t R) {
-  if (!f || N <= 0 || R <= 0 || f->num_levels <= 0 || f->num_levels > 8) return 0;
+  if (!f || N <= 0 || R < 0 || f->num_levels <= 0 || f->num_levels > 8) return 0;
   FeatPyr d;
   pyr_copy(d, *f, N);
   RoiRows rr; size_t a, b, c, e;
-  return roi_gather_carve(d, R, &rr, &a, &b, &c, &e);
+  return roi_gather_carve(d, R > 0 ? R : 1, &rr, &a, &b, &c, &e);   // R = 0 runs the table kernels on empty lists
 }
 
 // mode: 0 = records + gather, 1 = records only (prepare), 2 = gather only (records already in the workspace)
@@ -710,7 +710,8 @@ static int roi_bwd_gather_impl(const mxdet_feat_pyramid_t* f, int32_t N, int32_t
   MXDET_REQUIRE(R <= 65535, MXDET_ESHAPE, "roi_align_bwd_gather: at most 65535 rois");
   for (int l = 0; l < d.num_levels; ++l)
     MXDET_REQUIRE(d.H[l] < 32768 && d.W[l] < 32768, MXDET_ESHAPE, "roi_align_bwd_gather: level %d too large", l);
-  MXDET_REQUIRE(rois && levels && (grad_out || mode == 1), MXDET_EINVAL, "roi_align_bwd_gather: null pointer");
+  // R = 0 (an empty tensor has no pointer): zero maps, or untouched ones with accumulate, from the table kernels below
+  MXDET_REQUIRE(R == 0 || (rois && levels && (grad_out || mode == 1)), MXDET_EINVAL, "roi_align_bwd_gather: null pointer");
   hipStream_t s = as_stream(stream);
   RoiRows rr; size_t o_tab, o_list, o_cnt, o_box;
   const size_t need = roi_gather_carve(d, R > 0 ? R : 1, &rr, &o_tab, &o_list, &o_cnt, &o_box);
