@@ -579,6 +579,58 @@ int mxdet_retina_loss_level_dfl(const uint16_t* cls, const uint16_t* reg, int32_
                                 float loss_scale, uint16_t* grad_cls, uint16_t* grad_reg, float* partial,
                                 mxdet_stream_t stream);
 
+/* Gradient harmonizing for the RetinaNet head (GHM-C / GHM-R; Li et al., AAAI 2019): every element of the
+ * dense head is weighted by the inverse density of its gradient norm, counted over ALL levels and images of the step.
+ * Valid sets. Class elements: every (anchor, class c) with cls_labels >= 0; target t = 1 if cls_labels == c + 1, else 0;
+ *   padding columns of ld_cls are no elements. Box elements: the four deltas of every anchor with cls_labels > 0 against
+ *   the bbox_targets of mxdet_retina_loss_level (encoded deltas).
+ * Gradient norm. Class: g = |sigmoid(x) - t|. Box: d = delta - target, g = |d| / sqrt(d*d + mu*mu), mu > 0. g is a
+ *   constant of the loss: no gradient flows through the weights.
+ * Bin. For B bins, bin(g) = min(B - 1, (int)(g * (float)B)): unit-region edges k / B, g == 1 in the last bin. One device
+ *   function (csrc/loss_elem.h) and one g expression serve both passes, so no element changes bin between them.
+ * Per step, per histogram (one for class, one for box; per rank, no all-reduce):
+ *   cnt[i] = number of valid elements in bin i (int32).
+ *   acc[i] (float32 device state, starts at 0): for cnt[i] > 0, acc[i] = momentum * acc[i] + (1 - momentum) * cnt[i] if
+ *     momentum > 0, else acc[i] = cnt[i]; bins with cnt[i] == 0 keep their acc and are not counted.
+ *   n = number of bins with cnt[i] > 0; coef[i] = 1 / (n * acc[i]) for those bins, 0 for the others.
+ *   Class loss  = cls_weight * sum coef_c[bin(g)] * BCE(x, t) (the sigmoid_softplus log forms of the focal loss);
+ *     dL/dx = cls_weight * coef * (s - t).
+ *   Box loss    = reg_weight * sum coef_r[bin(g)] * (sqrt(d*d + mu*mu) - mu);
+ *     dL/d delta = reg_weight * coef * d / sqrt(d*d + mu*mu).
+ *   *num_fg does not enter a harmonized term; loss_scale scales gradients as in the entries above. A step without a valid
+ *   element has cnt == 0 everywhere: loss 0, gradients 0, acc untouched, no NaN or Inf.
+ * Published settings: class 30 bins, momentum 0.75, weight 1; box 10 bins, momentum 0.7, weight 10, mu 0.02.
+ * Limits: 1 <= bins <= MXDET_GHM_MAX_BINS, 0 <= momentum < 1, mu > 0, weights > 0; anything else is MXDET_EINVAL.
+ * flags: which halves are harmonized; a row of the count table, acc, cnt and coef hold bins_c class words, then bins_r box
+ * words, whatever the flags (a half left out counts 0, so its coef is 0 and its acc is untouched). */
+#define MXDET_GHM_CLS 1
+#define MXDET_GHM_REG 2
+#define MXDET_GHM_MAX_BINS 64
+/* Histogram pass of one level: the grid and anchor-to-workgroup map of mxdet_retina_loss_level
+ * (mxdet_retina_loss_num_partials workgroups of 256 anchors, the 16-byte class walk under the same condition on cls / reg).
+ * Workgroup i writes row i of counts ([blocks][bins_c + bins_r] int32): the caller lays the levels' rows back to back, as
+ * it does with `partial`. Every row is written whole: nothing has to be zeroed between steps. Integer LDS atomics
+ * (per-wave histograms; lanes that agree on a bin add once): counts do not depend on order. bbox_targets 16-byte aligned. */
+int mxdet_ghm_hist_level(const uint16_t* cls, const uint16_t* reg, int32_t N, int32_t H, int32_t W, int32_t A, int32_t C,
+                         int32_t ld_cls, int32_t ld_reg, const int32_t* cls_labels, const float* bbox_targets,
+                         int64_t A_total, int64_t level_offset, int32_t flags, int32_t bins_c, int32_t bins_r, float mu,
+                         int32_t* counts, mxdet_stream_t stream);
+/* The step's weights, one workgroup: cnt = column sums of the `rows` rows of counts (fixed order), acc updated in place,
+ * coef written; all three [bins_c + bins_r]. The only entry that writes acc. */
+int mxdet_ghm_weights(const int32_t* counts, int32_t rows, int32_t bins_c, int32_t bins_r, float momentum_c,
+                      float momentum_r, float* acc, int32_t* cnt, float* coef, mxdet_stream_t stream);
+/* Loss pass of one level: mxdet_retina_loss_level with the class term (MXDET_GHM_CLS) and / or the box term
+ * (MXDET_GHM_REG) harmonized by coef. Same grid, two-word partial layout, vector / scalar split and finalize (ncomp = 2).
+ * The half that flags leaves out is the focal (alpha, gamma) or smooth-L1 (sigma) half of mxdet_retina_loss_level: its
+ * partial word and gradient are bit-identical to that entry's. coef is read into LDS once per workgroup. No float atomics,
+ * no host synchronisation, nothing allocated, capturable; a replay follows new gt_boxes. */
+int mxdet_retina_loss_level_ghm(const uint16_t* cls, const uint16_t* reg, int32_t N, int32_t H, int32_t W, int32_t A,
+                                int32_t C, int32_t ld_cls, int32_t ld_reg, const int32_t* cls_labels,
+                                const float* bbox_targets, int64_t A_total, int64_t level_offset, int32_t flags, float alpha,
+                                float gamma, float sigma, const float* coef, int32_t bins_c, int32_t bins_r,
+                                float cls_weight, float mu, float reg_weight, const int32_t* num_fg, float loss_scale,
+                                uint16_t* grad_cls, uint16_t* grad_reg, float* partial, mxdet_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * core/mask + mask_heads (README.md:18, :30) -- Mask R-CNN.
  * mask targets: for roi r (batch, box) with matched GT g = matched_gt[r] and class labels[r] > 0, resample the

@@ -53,7 +53,8 @@ int64_t mxdet_debug_get_tuning(int32_t which);
 /* Route probe (per calling thread): which kernel instantiation a dense convolution / weight-gradient call, or which
  * form of the RetinaNet level loss, runs.
  * While the probe is on, mxdet_conv2d_fwd / _fwd_splitk / _fwd_chain / _dgrad / _grouped, mxdet_conv2d_wgrad,
- * mxdet_conv2d_wgrad_grouped(_parts) and mxdet_retina_loss_level(_iou / _quality / _dfl) validate their arguments as usual, record the launch(es) they WOULD make and return
+ * mxdet_conv2d_wgrad_grouped(_parts), mxdet_retina_loss_level(_iou / _quality / _dfl / _ghm) and mxdet_ghm_hist_level validate
+ * their arguments as usual, record the launch(es) they WOULD make and return
  * MXDET_OK without launching, without dereferencing any pointer and without touching the device (so it also works on a
  * machine without a GPU, with dummy non-null pointers). Switching it on clears the records. A record is 16 int32 words,
  * word 0 = kind:
@@ -71,7 +72,12 @@ int64_t mxdet_debug_get_tuning(int32_t which);
  *                             grid (= mxdet_retina_loss_num_partials)
  *   MXDET_ROUTE_RETINA_LOSS_IOU  the same two words for mxdet_retina_loss_level_iou (retina_loss_iou_kernel<vec, false>)
  *   MXDET_ROUTE_RETINA_LOSS_QUALITY  the same two words for mxdet_retina_loss_level_quality (retina_loss_iou_kernel<vec, true>)
- *   MXDET_ROUTE_RETINA_LOSS_DFL  the same two words for mxdet_retina_loss_level_dfl (retina_loss_dfl_kernel<vec, focal>) */
+ *   MXDET_ROUTE_RETINA_LOSS_DFL  the same two words for mxdet_retina_loss_level_dfl (retina_loss_dfl_kernel<vec, focal>)
+ *   MXDET_ROUTE_RETINA_LOSS_GHM  the same two words for mxdet_retina_loss_level_ghm (retina_loss_ghm_kernel<vec, cls, reg>),
+ *                             then flags (MXDET_GHM_CLS | MXDET_GHM_REG)
+ *   MXDET_ROUTE_GHM_HIST      the same three words for mxdet_ghm_hist_level (ghm_hist_kernel<vec>). mxdet_ghm_weights has one
+ *                             route: while the probe is on it validates its arguments and returns MXDET_OK without a launch
+ *                             and without a record, so the head's whole sequence can be probed on a machine without a GPU */
 #define MXDET_ROUTE_CONV 1
 #define MXDET_ROUTE_WGRAD 2
 #define MXDET_ROUTE_CONV_GROUPED 3
@@ -80,6 +86,8 @@ int64_t mxdet_debug_get_tuning(int32_t which);
 #define MXDET_ROUTE_RETINA_LOSS_IOU 6
 #define MXDET_ROUTE_RETINA_LOSS_QUALITY 7
 #define MXDET_ROUTE_RETINA_LOSS_DFL 8
+#define MXDET_ROUTE_RETINA_LOSS_GHM 9
+#define MXDET_ROUTE_GHM_HIST 10
 #define MXDET_ROUTE_WORDS 16
 #define MXDET_ROUTE_MAX 4
 int mxdet_debug_route_probe(int32_t on);

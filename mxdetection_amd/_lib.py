@@ -222,6 +222,12 @@ SIGNATURES = {
     "mxdet_retina_loss_level_dfl": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
                                             c_i32, c_i64, c_i64, c_i32, c_f32, c_f32, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp,
                                             c_f32, c_vp, c_vp, c_vp, c_vp]),
+    "mxdet_ghm_hist_level": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_i64, c_i32,
+                                     c_i32, c_i32, c_f32, c_vp, c_vp]),
+    "mxdet_ghm_weights": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    "mxdet_retina_loss_level_ghm": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_i64,
+                                            c_i32, c_f32, c_f32, c_f32, c_vp, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_f32,
+                                            c_vp, c_vp, c_vp, c_vp]),
     "mxdet_mask_target": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mxdet_pixel_shuffle2": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mxdet_mask_loss_workspace_bytes": (c_sz, [c_i64, c_i32]),
@@ -325,7 +331,7 @@ TUNING_KEYS = {"T64": 0, "T128": 1, "PAR64": 2, "WG_TARGET": 3, "WG_MINSTEPS": 4
                "T128W": 15, "T3_MIX": 16, "SPLITK_TILE": 17, "T3_PER_ITEM": 18}
 # word 0 of a route-probe record (MXDET_ROUTE_* in include/mxdet_debug.h)
 ROUTE_KINDS = {"CONV": 1, "WGRAD": 2, "CONV_GROUPED": 3, "WGRAD_GROUPED": 4, "RETINA_LOSS": 5, "RETINA_LOSS_IOU": 6,
-               "RETINA_LOSS_QUALITY": 7, "RETINA_LOSS_DFL": 8}
+               "RETINA_LOSS_QUALITY": 7, "RETINA_LOSS_DFL": 8, "RETINA_LOSS_GHM": 9, "GHM_HIST": 10}
 
 # `kind` of the IoU-family box losses (MXDET_IOU_LOSS_* in include/mxdet.h)
 IOU_LOSS_KINDS = {"iou": 0, "giou": 1, "diou": 2}
@@ -334,6 +340,9 @@ CLS_LOSS_KINDS = {"qfl": 1, "vfl": 2}
 # `cls_kind` of mxdet_retina_loss_level_dfl: the above and MXDET_CLS_LOSS_FOCAL; reg_max's bound (MXDET_REG_MAX_LIMIT)
 CLS_LOSS_KINDS_DFL = {"focal": 0, "qfl": 1, "vfl": 2}
 REG_MAX_LIMIT = 31
+# `flags` of the gradient-harmonizing entries (MXDET_GHM_CLS / _REG) and the bound of their bins (MXDET_GHM_MAX_BINS)
+GHM_FLAGS = {"cls": 1, "reg": 2, "both": 3}
+GHM_MAX_BINS = 64
 # bounds of the Libra R-CNN entries (MXDET_SAMPLER_MAX_BINS, MXDET_BFP_MAX_LEVELS)
 SAMPLER_MAX_BINS = 8
 BFP_MAX_LEVELS = 6

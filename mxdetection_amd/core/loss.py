@@ -313,6 +313,91 @@ def retina_loss_level_dfl(cls, reg, A, C, cls_labels, anchors, matched_gt, gt_bo
           "retina_loss_level_dfl")
 
 
+# ---- gradient harmonizing of the RetinaNet head: GHM-C / GHM-R (include/mxdet.h) ----
+GHM_MODES = ("none", "cls", "reg", "both")
+GHM_FLAGS = _lib.GHM_FLAGS
+GHM_MAX_BINS = _lib.GHM_MAX_BINS
+GHM_DEFAULTS = dict(cls_bins=30, cls_momentum=0.75, cls_weight=1.0, reg_bins=10, reg_momentum=0.7, reg_mu=0.02,
+                    reg_weight=10.0)                                   # as published (Li et al. 2019; mmdetection)
+
+
+def check_ghm(ghm="none", cls_loss="focal", reg_loss="smooth_l1", reg_max=0, cls_loss_alpha=None, cls_loss_gamma=None,
+              cls_bins=30, cls_momentum=0.75, cls_weight=1.0, reg_bins=10, reg_momentum=0.7, reg_mu=0.02, reg_weight=10.0):
+    """The gradient-harmonizing options of the RetinaNet head, checked before anything is allocated. ghm: 'none', or which
+    terms are harmonized: 'cls' replaces the focal loss, 'reg' the smooth-L1 loss, 'both'. Every mode but 'none' needs
+    cls_loss 'focal', reg_loss 'smooth_l1' and reg_max 0 (the half that is not harmonized is the plain entry's); 'cls' and
+    'both' take no cls_loss_alpha / cls_loss_gamma (GHM-C has neither; with 'reg' they are the focal half's). Returns the
+    seven settings as a dict of ints / floats (the keys of GHM_DEFAULTS)."""
+    if ghm not in GHM_MODES:
+        raise ValueError("ghm must be one of %s (got %r)" % (", ".join(GHM_MODES), ghm))
+    for name, b in (("ghm_cls_bins", cls_bins), ("ghm_reg_bins", reg_bins)):
+        if isinstance(b, bool) or not isinstance(b, int) or not 1 <= b <= GHM_MAX_BINS:
+            raise ValueError("%s must be an integer in 1..%d (got %r)" % (name, GHM_MAX_BINS, b))
+    for name, m in (("ghm_cls_momentum", cls_momentum), ("ghm_reg_momentum", reg_momentum)):
+        if isinstance(m, bool) or not isinstance(m, (int, float)) or not 0 <= m < 1:
+            raise ValueError("%s must lie in [0, 1) (got %r)" % (name, m))
+    for name, v in (("ghm_cls_weight", cls_weight), ("ghm_reg_weight", reg_weight), ("ghm_reg_mu", reg_mu)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 < v < float("inf"):
+            raise ValueError("%s must be a positive finite number (got %r)" % (name, v))
+    cfg = dict(cls_bins=int(cls_bins), cls_momentum=float(cls_momentum), cls_weight=float(cls_weight), reg_bins=int(reg_bins),
+               reg_momentum=float(reg_momentum), reg_mu=float(reg_mu), reg_weight=float(reg_weight))
+    if ghm == "none":
+        return cfg
+    # The level entry's other half is the focal / smooth-L1 half of retina_loss_level and nothing else, so EVERY mode needs
+    # the plain pair: 'cls' beside giou would otherwise train smooth-L1 without saying so, and beside reg_max > 0 walk a
+    # distribution head's channels as four deltas.
+    if cls_loss != "focal":
+        raise ValueError("ghm = %r harmonizes the sigmoid cross-entropy in place of the focal loss, or keeps the focal loss "
+                         "beside a harmonized box term: cls_loss = %r is another class loss (GHM with qfl / vfl is not built)"
+                         % (ghm, cls_loss))
+    if reg_loss != "smooth_l1":
+        raise ValueError("ghm = %r works on the encoded deltas, harmonized ('reg', 'both') or as smooth-L1 beside a harmonized "
+                         "class term ('cls'): reg_loss = %r acts on the decoded box (GHM with the IoU family is not built); "
+                         "keep reg_loss = 'smooth_l1'" % (ghm, reg_loss))
+    if reg_max != 0:
+        raise ValueError("ghm = %r needs plain deltas: reg_max = %r makes the box branch a distribution head" % (ghm, reg_max))
+    if ghm in ("cls", "both") and (cls_loss_alpha is not None or cls_loss_gamma is not None):
+        raise ValueError("ghm = %r: GHM-C has no alpha / gamma (cls_loss_alpha = %r, cls_loss_gamma = %r); its settings "
+                         "are ghm_cls_bins / ghm_cls_momentum / ghm_cls_weight" % (ghm, cls_loss_alpha, cls_loss_gamma))
+    return cfg
+
+
+def _ghm_flags(ghm):
+    if ghm not in GHM_FLAGS:
+        raise ValueError("ghm must be one of %s (got %r)" % (", ".join(GHM_FLAGS), ghm))
+    return GHM_FLAGS[ghm]
+
+
+def ghm_hist_level(cls, reg, A, C, cls_labels, bbox_targets, level_offset, ghm, cls_bins, reg_bins, reg_mu, counts):
+    """Histogram pass of one level: counts = this level's rows ([retina_loss_num_partials, cls_bins + reg_bins] int32) of
+    the step's count table; ghm 'cls' / 'reg' / 'both' = the halves that are counted."""
+    lib = _lib.load()
+    N, H, W, ld_cls = cls.shape
+    check(lib.mxdet_ghm_hist_level(ptr(cls), ptr(reg), N, H, W, A, C, ld_cls, reg.shape[3], ptr(cls_labels), ptr(bbox_targets),
+                                   cls_labels.shape[1], level_offset, _ghm_flags(ghm), cls_bins, reg_bins, reg_mu, ptr(counts),
+                                   stream_ptr()), "ghm_hist_level")
+
+
+def ghm_weights(counts, rows, cls_bins, reg_bins, cls_momentum, reg_momentum, acc, cnt, coef):
+    """The step's weights from the first `rows` rows of the count table: acc (the moving average, f32) is updated in place,
+    cnt (i32) and coef (f32) are written; all three [cls_bins + reg_bins], class bins first."""
+    check(_lib.load().mxdet_ghm_weights(ptr(counts), rows, cls_bins, reg_bins, cls_momentum, reg_momentum, ptr(acc), ptr(cnt),
+                                        ptr(coef), stream_ptr()), "ghm_weights")
+
+
+def retina_loss_level_ghm(cls, reg, A, C, cls_labels, bbox_targets, level_offset, ghm, alpha, gamma, sigma, coef, cls_bins,
+                          reg_bins, cls_weight, reg_mu, reg_weight, num_fg, loss_scale, grad_cls, grad_reg, partial):
+    """retina_loss_level with the class ('cls'), the box ('reg') or both terms harmonized by coef (ghm_weights); the other
+    half is retina_loss_level's, bit for bit."""
+    lib = _lib.load()
+    N, H, W, ld_cls = cls.shape
+    check(lib.mxdet_retina_loss_level_ghm(ptr(cls), ptr(reg), N, H, W, A, C, ld_cls, reg.shape[3], ptr(cls_labels),
+                                          ptr(bbox_targets), cls_labels.shape[1], level_offset, _ghm_flags(ghm), alpha, gamma,
+                                          sigma, ptr(coef), cls_bins, reg_bins, cls_weight, reg_mu, reg_weight, ptr(num_fg),
+                                          loss_scale, ptr(grad_cls), ptr(grad_reg), ptr(partial), stream_ptr()),
+          "retina_loss_level_ghm")
+
+
 # ---- online hard example mining for the box head (include/mxdet.h; DESIGN.md 5o) ----
 def ohem_roi_score(cls_logits, bbox_pred, labels, num_classes, reg_dim, ld_cls, ld_reg, reg_loss="smooth_l1", bbox_targets=None,
                    bbox_weights=None, sigma=1.0, rois=None, matched_gt=None, gt_boxes=None, stds=(0.1, 0.1, 0.2, 0.2),

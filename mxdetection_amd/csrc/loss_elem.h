@@ -22,16 +22,26 @@ __device__ inline float block_sum_fixed(float v, float* smem /* >= blockDim/64 f
   return s;  // valid on thread 0
 }
 
-// The workgroup's K loss sums: block_sum_fixed of v[0], v[1], ... in that order, then partial[K * blockIdx.x + j] = sum * scale.
+// The workgroup's K loss sums: block_sum_fixed of v[0], v[1], ... in that order, then
+// partial[K * blockIdx.x + j] = sum * scale[j] (a kernel whose terms are normalised differently has one scale per sum).
 template <int K>
-__device__ __forceinline__ void store_block_partials(const float (&v)[K], float scale, float* red, float* __restrict__ partial) {
+__device__ __forceinline__ void store_block_partials(const float (&v)[K], const float (&scale)[K], float* red,
+                                                     float* __restrict__ partial) {
   float s[K];
 #pragma unroll
   for (int j = 0; j < K; ++j) s[j] = block_sum_fixed(v[j], red);
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int j = 0; j < K; ++j) partial[K * blockIdx.x + j] = s[j] * scale;
+    for (int j = 0; j < K; ++j) partial[K * blockIdx.x + j] = s[j] * scale[j];
   }
+}
+// the same with one scale for every sum
+template <int K>
+__device__ __forceinline__ void store_block_partials(const float (&v)[K], float scale, float* red, float* __restrict__ partial) {
+  float sc[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) sc[j] = scale;
+  store_block_partials<K>(v, sc, red, partial);
 }
 
 __device__ __forceinline__ float softplus_neg_abs(float z) {
@@ -135,6 +145,41 @@ struct QualityElem {
   float alpha, gamma;
   __device__ __forceinline__ float operator()(float x, bool positive, float quality, float& g) const {
     return quality_cls_elem(x, positive ? quality : 0.0f, cls_kind, alpha, gamma, g);
+  }
+};
+
+// ---------------------------------------------------------------------------------------------
+// Gradient harmonizing (GHM, Li et al. 2019; definition in include/mxdet.h). The histogram pass and the
+// loss pass of a step call the SAME three functions below on the same inputs, so an element lands in the same bin in both.
+//
+// bin of a gradient norm g in [0, 1]: unit-region edges k / B, g == 1 in the last bin
+__device__ __forceinline__ int ghm_bin(const float g, const int B) {
+  const int b = (int)(g * (float)B);
+  return b < 0 ? 0 : (b < B - 1 ? b : B - 1);             // b < 0 does not occur for g >= 0: the index stays in the table
+}
+// class element: g = |sigmoid(x) - t| = 1 - p for the row's own class column, p for any other; p, q = 1 - p, the logs of
+// sigmoid_logs come back for the loss (the histogram pass drops them)
+__device__ __forceinline__ float ghm_cls_norm(const float x, const bool positive, float& p, float& q, float& logp,
+                                              float& log1mp) {
+  sigmoid_logs(x, p, q, logp, log1mp);
+  return positive ? q : p;
+}
+// box element: d = delta - target, r = sqrt(d*d + mu*mu); g = |d| / r
+__device__ __forceinline__ float ghm_reg_norm(const float d, const float mu, float& r) {
+  r = sqrtf(d * d + mu * mu);
+  return (d < 0.0f ? -d : d) / r;
+}
+// The harmonized class element as the class walks take it: coef = the step's B weights (LDS). L = coef[bin] * BCE,
+// g = coef[bin] * (s - t), with s - 1 taken as -(1 - s).
+struct GhmClsElem {
+  static constexpr bool kQuality = false;
+  const float* coef;
+  int B;
+  __device__ __forceinline__ float operator()(float x, bool positive, float, float& g) const {
+    float p, q, logp, log1mp;
+    const float c = coef[ghm_bin(ghm_cls_norm(x, positive, p, q, logp, log1mp), B)];
+    g = c * (positive ? -q : p);
+    return c * (positive ? -logp : -log1mp);
   }
 };
 

@@ -2,6 +2,7 @@
 // level, forward and backward in one pass (the conventions of losses.hip). Four entries share one grid (256 consecutive
 // anchors per workgroup), one vector / scalar split and the pieces below: smooth-L1 (mxdet_retina_loss_level), an IoU-family
 // box term (_iou), that with a quality-aware class term (_quality, 5j), and the distribution head (_dfl, 5k).
+// The gradient-harmonized losses (5v) add a histogram pass on the same grid, a weights kernel and a fifth level entry (_ghm).
 #include "common.h"
 #include "loss_elem.h"
 
@@ -339,6 +340,223 @@ retina_loss_dfl_kernel(const uint16_t* __restrict__ cls, const uint16_t* __restr
   store_block_partials<3>({lc, lr, ldf}, inv, red, partial);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Gradient harmonizing (definition in include/mxdet.h). Three kernels per step: a histogram pass per level
+// (ghm_hist_kernel), one weights launch (ghm_weights_kernel), a loss pass per level (retina_loss_ghm_kernel). The two
+// passes share the grid, the anchor-to-workgroup map and ghm_cls_norm / ghm_reg_norm / ghm_bin of loss_elem.h.
+constexpr int kGhmRow = 2 * MXDET_GHM_MAX_BINS;           // most counts of one row: class bins, then box bins
+
+// One class element of each of the wave's 64 lanes into the wave's own histogram wh; b < 0: the lane has nothing to count.
+// Every lane of the wave calls this together. The lanes that agree with the first counting lane's bin go in as ONE add of
+// their number -- at initialisation (every g near 0.01) and for the negatives of a trained model that is all of them --
+// and only the others add for themselves. Integer counts: the order of the adds does not show in the result.
+__device__ __forceinline__ void ghm_wave_count(int* wh, const int b) {
+  const unsigned long long vm = __ballot(b >= 0);
+  if (vm == 0ull) return;
+  const int first = __ffsll(vm) - 1;
+  const int b0 = __builtin_amdgcn_readlane(b, first);
+  const unsigned long long m = __ballot(b == b0);
+  if (lane_id() == first) atomicAdd(&wh[b0], (int)__popcll(m));
+  if (b >= 0 && b != b0) atomicAdd(&wh[b], 1);
+}
+
+// Histogram pass of one level: workgroup i counts its 256 anchors' valid elements and writes row i of `counts`:
+// Bc class bins, then Br box bins (zeros for a half that `flags` leaves out). Per-wave histograms in LDS, summed per row.
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+ghm_hist_kernel(const uint16_t* __restrict__ cls, const uint16_t* __restrict__ reg, int N, int HW, int A, int C, int ld_cls,
+                int ld_reg, const int32_t* __restrict__ cls_labels, const float4* __restrict__ targets, long long A_total,
+                long long level_offset, int flags, int Bc, int Br, float mu, int32_t* __restrict__ counts) {
+  __shared__ int hist[4][kGhmRow];
+  for (int i = threadIdx.x; i < 4 * kGhmRow; i += 256) (&hist[0][0])[i] = 0;
+  __syncthreads();
+  int* wh = hist[threadIdx.x >> 6];
+  const long long total = (long long)N * HW * A;
+  const long long a_first = (long long)blockIdx.x * 256;
+  const long long idx = a_first + threadIdx.x;
+  if (flags & MXDET_GHM_CLS) {
+    if (VEC) {                                            // the lane map of class_walk_vec; C / 8 trips for every lane
+      const int CH = C >> 3;
+      for (int it = threadIdx.x; it < 256 * CH; it += 256) {
+        const int al = it / CH, ck = it - al * CH;
+        const long long ia = a_first + al;
+        int lab = -1;
+        uint4 zv = make_uint4(0u, 0u, 0u, 0u);
+        if (ia < total) {
+          const LevelAnchor la = level_anchor(ia, HW, A, A_total, level_offset);
+          lab = cls_labels[la.gi];
+          if (lab >= 0) zv = *(const uint4*)(cls + la.cls_off(ld_cls, C) + ck * 8);
+        }
+        const unsigned zw[4] = {zv.x, zv.y, zv.z, zv.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const int c = ck * 8 + 2 * k + h;
+            const float x = h ? __uint_as_float(zw[k] & 0xffff0000u) : __uint_as_float(zw[k] << 16);
+            float p, q, logp, log1mp;
+            const float g = ghm_cls_norm(x, lab == c + 1, p, q, logp, log1mp);
+            ghm_wave_count(wh, lab >= 0 ? ghm_bin(g, Bc) : -1);
+          }
+        }
+      }
+    } else {                                              // the lane's own anchor, C trips for every lane
+      int lab = -1;
+      long long coff = 0;
+      if (idx < total) {
+        const LevelAnchor la = level_anchor(idx, HW, A, A_total, level_offset);
+        lab = cls_labels[la.gi];
+        coff = la.cls_off(ld_cls, C);
+      }
+      for (int c = 0; c < C; ++c) {
+        const float x = lab >= 0 ? bf16_bits_to_f32(cls[coff + c]) : 0.0f;
+        float p, q, logp, log1mp;
+        const float g = ghm_cls_norm(x, lab == c + 1, p, q, logp, log1mp);
+        ghm_wave_count(wh, lab >= 0 ? ghm_bin(g, Bc) : -1);
+      }
+    }
+  }
+  if ((flags & MXDET_GHM_REG) && idx < total) {           // a handful of anchors per workgroup: plain adds
+    const LevelAnchor la = level_anchor(idx, HW, A, A_total, level_offset);
+    if (cls_labels[la.gi] > 0) {
+      const float4 t = targets[la.gi];
+      const float tt[4] = {t.x, t.y, t.z, t.w};
+      float dd[4];
+      load_box4<VEC>(reg + la.box_off(ld_reg, 4), dd);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float r;
+        atomicAdd(&wh[Bc + ghm_bin(ghm_reg_norm(dd[k] - tt[k], mu, r), Br)], 1);
+      }
+    }
+  }
+  __syncthreads();
+  const int nb = Bc + Br;
+  if ((int)threadIdx.x < nb)
+    counts[(long long)blockIdx.x * nb + threadIdx.x] =
+        ((hist[0][threadIdx.x] + hist[1][threadIdx.x]) + hist[2][threadIdx.x]) + hist[3][threadIdx.x];
+}
+
+// The step's weights: cnt = the column sums of the `rows` rows, the moving average acc updated in place for the bins that
+// hold something, coef = 1 / (n * acc) for those (n = their number, per histogram) and 0 for the others. One workgroup:
+// thread (g, i) sums bin i over the rows r = g mod 8, the eight sums are added in order.
+__global__ void __launch_bounds__(1024)
+ghm_weights_kernel(const int32_t* __restrict__ counts, int rows, int Bc, int Br, float mmt_c, float mmt_r,
+                   float* __restrict__ acc, int32_t* __restrict__ cnt, float* __restrict__ coef) {
+  __shared__ int part[8][kGhmRow];
+  __shared__ int tot[kGhmRow];
+  const int nb = Bc + Br, i = threadIdx.x & (kGhmRow - 1), rg = threadIdx.x >> 7;
+  int s = 0;
+  if (i < nb)
+    for (int r = rg; r < rows; r += 8) s += counts[(long long)r * nb + i];
+  part[rg][i] = s;
+  __syncthreads();
+  if (threadIdx.x < kGhmRow) {
+    int c = 0;
+    for (int g = 0; g < 8; ++g) c += part[g][i];
+    tot[i] = c;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < nb) {
+    const bool is_cls = i < Bc;
+    const int lo = is_cls ? 0 : Bc, hi = is_cls ? Bc : nb;
+    int n = 0;
+    for (int j = lo; j < hi; ++j) n += tot[j] > 0 ? 1 : 0;
+    const int c = tot[i];
+    const float mmt = is_cls ? mmt_c : mmt_r;
+    float w = 0.0f;
+    if (c > 0) {
+      float a = (float)c;
+      if (mmt > 0.0f) {
+        const float keep = mmt * acc[i], add = (1.0f - mmt) * (float)c;
+        a = keep + add;
+      }
+      acc[i] = a;
+      w = 1.0f / ((float)n * a);
+    }
+    cnt[i] = c;
+    coef[i] = w;
+  }
+}
+
+// Harmonized box part of one anchor (the deltas of smooth_l1_box_part): sum of coef[bin] * (sqrt(d*d + mu*mu) - mu),
+// gradient coef[bin] * d / sqrt(d*d + mu*mu) * w * loss_scale.
+template <bool VEC>
+__device__ __forceinline__ float ghm_box_part(const uint16_t* __restrict__ d, const float4* __restrict__ target, float mu,
+                                              const float* coef, int B, float w, float loss_scale,
+                                              uint16_t* __restrict__ gd) {
+  float lr = 0.0f;
+  unsigned short gb[4] = {0, 0, 0, 0};
+  if (target) {
+    const float4 t = *target;
+    const float tt[4] = {t.x, t.y, t.z, t.w};
+    float dd[4];
+    load_box4<VEC>(d, dd);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float e = dd[k] - tt[k];
+      float r;
+      const float c = coef[ghm_bin(ghm_reg_norm(e, mu, r), B)];
+      lr += c * (r - mu);
+      gb[k] = f32_to_bf16_bits(c * (e / r) * w * loss_scale);
+    }
+  }
+  store_box4<VEC>(gd, gb);
+  return lr;
+}
+
+// retina_loss_kernel<VEC> with the class element (GC) and / or the box element (GR) harmonized: the step's weights come
+// from `coef` (Bc class, then Br box) into LDS once per workgroup. A harmonized term is scaled by its weight w_c / w_r,
+// not by 1 / num_fg; the other half is retina_loss_kernel's statement for statement.
+template <bool VEC, bool GC, bool GR>
+__global__ void __launch_bounds__(256)
+retina_loss_ghm_kernel(const uint16_t* __restrict__ cls, const uint16_t* __restrict__ reg, int N, int HW, int A, int C,
+                       int ld_cls, int ld_reg, const int32_t* __restrict__ cls_labels, const float4* __restrict__ targets,
+                       long long A_total, long long level_offset, float alpha, float gamma, float sigma2,
+                       const float* __restrict__ coef, int Bc, int Br, float w_c, float mu, float w_r,
+                       const int* __restrict__ num_fg, float loss_scale, uint16_t* __restrict__ gcls,
+                       uint16_t* __restrict__ greg, float* __restrict__ partial) {
+  __shared__ float red[8];
+  __shared__ float cf[kGhmRow];
+  if ((int)threadIdx.x < Bc + Br) cf[threadIdx.x] = coef[threadIdx.x];
+  __syncthreads();
+  const long long total = (long long)N * HW * A;
+  const long long a_first = (long long)blockIdx.x * 256;
+  const long long idx = a_first + threadIdx.x;
+  const int nf = *num_fg;
+  const float inv = 1.0f / (float)(nf > 1 ? nf : 1);
+  const float sc = GC ? w_c : inv, sr = GR ? w_r : inv;
+  int lab = -1;
+  long long coff = 0, roff = 0, gi = 0;
+  if (idx < total) {
+    const LevelAnchor la = level_anchor(idx, HW, A, A_total, level_offset);
+    lab = cls_labels[la.gi];
+    coff = la.cls_off(ld_cls, C);
+    roff = la.box_off(ld_reg, 4);
+    gi = la.gi;
+  }
+  const auto walk = [&](const auto elem) {
+    if (VEC)
+      return class_walk_vec(cls, HW, A, C, ld_cls, cls_labels, A_total, level_offset, elem, nullptr, sc, loss_scale, a_first,
+                            total, gcls);
+    if (idx >= total) return 0.0f;
+    return class_walk_anchor(cls + coff, C, lab, elem, 0.0f, sc, loss_scale, gcls + coff);
+  };
+  float lc, lr = 0.0f;
+  if constexpr (GC)
+    lc = walk(GhmClsElem{cf, Bc});
+  else
+    lc = walk(FocalElem{alpha, gamma});
+  if (idx < total) {
+    const float4* tgt = lab > 0 ? targets + gi : nullptr;
+    if constexpr (GR)
+      lr = ghm_box_part<VEC>(reg + roff, tgt, mu, cf + Bc, Br, w_r, loss_scale, greg + roff);
+    else
+      lr = smooth_l1_box_part<VEC>(reg + roff, tgt, sigma2, inv, loss_scale, greg + roff);
+  }
+  store_block_partials<2>({lc, lr}, {sc, sr}, red, partial);
+}
+
 }  // namespace mxdet
 
 using namespace mxdet;
@@ -519,4 +737,95 @@ extern "C" int mxdet_retina_loss_level_dfl(const uint16_t* cls, const uint16_t* 
                      alpha, gamma, kind, reg_max, stride, reg_weight, dfl_weight, (const int*)num_fg, loss_scale, grad_cls,
                      grad_reg, partial);
   return check_launch("retina_loss_level_dfl");
+}
+
+// ---- gradient harmonizing: the checks the three entries share ----
+static const char* ghm_param_error(int32_t flags, int32_t bins_c, int32_t bins_r, float mu) {
+  if (flags < 1 || flags > (MXDET_GHM_CLS | MXDET_GHM_REG)) return "flags must be MXDET_GHM_CLS, MXDET_GHM_REG or both";
+  if (bins_c < 1 || bins_c > MXDET_GHM_MAX_BINS || bins_r < 1 || bins_r > MXDET_GHM_MAX_BINS) return "bins must lie in 1..64";
+  return mu > 0.0f ? nullptr : "mu must be positive";
+}
+
+static int ghm_level_prepare(const char* entry, int32_t N, int32_t H, int32_t W, int32_t A, int32_t C, int32_t ld_cls,
+                             int32_t ld_reg, int64_t A_total, int64_t level_offset, const char* param_error, bool nulls) {
+  MXDET_REQUIRE(N > 0 && H > 0 && W > 0 && A > 0 && C > 0 && ld_cls >= A * C && ld_reg >= 4 * A, MXDET_ESHAPE, "%s: bad shape",
+                entry);
+  MXDET_REQUIRE(!param_error, MXDET_EINVAL, "%s: %s", entry, param_error);
+  MXDET_REQUIRE(!nulls, MXDET_EINVAL, "%s: null pointer", entry);
+  MXDET_REQUIRE(level_offset >= 0 && level_offset + (int64_t)H * W * A <= A_total, MXDET_ESHAPE,
+                "%s: level outside the anchor range", entry);
+  return MXDET_OK;
+}
+
+extern "C" int mxdet_ghm_hist_level(const uint16_t* cls, const uint16_t* reg, int32_t N, int32_t H, int32_t W, int32_t A,
+                                    int32_t C, int32_t ld_cls, int32_t ld_reg, const int32_t* cls_labels,
+                                    const float* bbox_targets, int64_t A_total, int64_t level_offset, int32_t flags,
+                                    int32_t bins_c, int32_t bins_r, float mu, int32_t* counts, mxdet_stream_t stream) {
+  clear_error();
+  const int rc = ghm_level_prepare("ghm_hist_level", N, H, W, A, C, ld_cls, ld_reg, A_total, level_offset,
+                                   ghm_param_error(flags, bins_c, bins_r, mu),
+                                   !(cls && reg && cls_labels && bbox_targets && counts));
+  if (rc != MXDET_OK) return rc;
+  MXDET_REQUIRE((uintptr_t)bbox_targets % 16 == 0, MXDET_EINVAL, "ghm_hist_level: bbox_targets must be 16-byte aligned");
+  const int blocks = mxdet_retina_loss_num_partials(N, H, W, A);
+  const bool vec = level_vec_ok(cls, reg, C, ld_cls, ld_reg, cls, reg);
+  if (route_probe_on()) {
+    const int32_t rec[kRouteWords] = {MXDET_ROUTE_GHM_HIST, vec ? 1 : 0, blocks, flags};
+    route_record(rec);
+    return MXDET_OK;
+  }
+  hipLaunchKernelGGL(vec ? ghm_hist_kernel<true> : ghm_hist_kernel<false>, dim3(blocks), dim3(256), 0, as_stream(stream), cls,
+                     reg, N, H * W, A, C, ld_cls, ld_reg, cls_labels, (const float4*)bbox_targets, (long long)A_total,
+                     (long long)level_offset, flags, bins_c, bins_r, mu, counts);
+  return check_launch("ghm_hist_level");
+}
+
+extern "C" int mxdet_ghm_weights(const int32_t* counts, int32_t rows, int32_t bins_c, int32_t bins_r, float momentum_c,
+                                 float momentum_r, float* acc, int32_t* cnt, float* coef, mxdet_stream_t stream) {
+  clear_error();
+  MXDET_REQUIRE(rows > 0, MXDET_ESHAPE, "ghm_weights: bad shape");
+  const char* bad = ghm_param_error(MXDET_GHM_CLS, bins_c, bins_r, 1.0f);
+  if (!bad && !(momentum_c >= 0.0f && momentum_c < 1.0f && momentum_r >= 0.0f && momentum_r < 1.0f))
+    bad = "momentum must lie in [0, 1)";
+  MXDET_REQUIRE(!bad, MXDET_EINVAL, "ghm_weights: %s", bad);
+  MXDET_REQUIRE(counts && acc && cnt && coef, MXDET_EINVAL, "ghm_weights: null pointer");
+  if (route_probe_on()) return MXDET_OK;                  // one route, nothing to record: like the level entries, no launch
+  hipLaunchKernelGGL(ghm_weights_kernel, dim3(1), dim3(1024), 0, as_stream(stream), counts, rows, bins_c, bins_r, momentum_c,
+                     momentum_r, acc, cnt, coef);
+  return check_launch("ghm_weights");
+}
+
+template <bool VEC>
+static auto ghm_loss_kernel_of(int32_t flags) {
+  if (flags == MXDET_GHM_CLS) return retina_loss_ghm_kernel<VEC, true, false>;
+  if (flags == MXDET_GHM_REG) return retina_loss_ghm_kernel<VEC, false, true>;
+  return retina_loss_ghm_kernel<VEC, true, true>;
+}
+
+extern "C" int mxdet_retina_loss_level_ghm(const uint16_t* cls, const uint16_t* reg, int32_t N, int32_t H, int32_t W, int32_t A,
+                                           int32_t C, int32_t ld_cls, int32_t ld_reg, const int32_t* cls_labels,
+                                           const float* bbox_targets, int64_t A_total, int64_t level_offset, int32_t flags,
+                                           float alpha, float gamma, float sigma, const float* coef, int32_t bins_c,
+                                           int32_t bins_r, float cls_weight, float mu, float reg_weight, const int32_t* num_fg,
+                                           float loss_scale, uint16_t* grad_cls, uint16_t* grad_reg, float* partial,
+                                           mxdet_stream_t stream) {
+  clear_error();
+  const char* bad = ghm_param_error(flags, bins_c, bins_r, mu);
+  if (!bad && !(cls_weight > 0.0f && reg_weight > 0.0f)) bad = "cls_weight and reg_weight must be positive";
+  const int rc = ghm_level_prepare("retina_loss_level_ghm", N, H, W, A, C, ld_cls, ld_reg, A_total, level_offset, bad,
+                                   !(cls && reg && cls_labels && bbox_targets && coef && num_fg && grad_cls && grad_reg && partial));
+  if (rc != MXDET_OK) return rc;
+  MXDET_REQUIRE((uintptr_t)bbox_targets % 16 == 0, MXDET_EINVAL, "retina_loss_level_ghm: bbox_targets must be 16-byte aligned");
+  const int blocks = mxdet_retina_loss_num_partials(N, H, W, A);
+  const bool vec = level_vec_ok(cls, reg, C, ld_cls, ld_reg, grad_cls, grad_reg);
+  if (route_probe_on()) {
+    const int32_t rec[kRouteWords] = {MXDET_ROUTE_RETINA_LOSS_GHM, vec ? 1 : 0, blocks, flags};
+    route_record(rec);
+    return MXDET_OK;
+  }
+  hipLaunchKernelGGL(vec ? ghm_loss_kernel_of<true>(flags) : ghm_loss_kernel_of<false>(flags), dim3(blocks), dim3(256), 0,
+                     as_stream(stream), cls, reg, N, H * W, A, C, ld_cls, ld_reg, cls_labels, (const float4*)bbox_targets,
+                     (long long)A_total, (long long)level_offset, alpha, gamma, sigma * sigma, coef, bins_c, bins_r, cls_weight,
+                     mu, reg_weight, (const int*)num_fg, loss_scale, grad_cls, grad_reg, partial);
+  return check_launch("retina_loss_level_ghm");
 }

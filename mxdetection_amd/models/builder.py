@@ -18,6 +18,9 @@ def build_detector(cfg, device="cuda"):
         if net.assigner != "max_iou":
             raise ValueError("network.assigner = %r: %s keeps the RPN's sampler (atss is a retinanet option)"
                              % (net.assigner, net.type))
+        if net.ghm != "none":
+            raise ValueError("network.ghm = %r: %s keeps its RPN and box-head losses (gradient harmonizing is a retinanet "
+                             "option)" % (net.ghm, net.type))
         if net.mask_iou and net.type != "mask_rcnn":
             raise ValueError("network.mask_iou = %r: %s has no mask branch to score (the MaskIoU head is a mask_rcnn option)"
                              % (net.mask_iou, net.type))
@@ -70,7 +73,10 @@ def build_detector(cfg, device="cuda"):
                           assigner=str(net.assigner), atss_topk=net.atss_topk, anchor_ratios=tuple(net.anchor_ratios),
                           anchor_scales_per_octave=net.anchor_scales_per_octave, anchor_scale=float(net.anchor_scale),
                           cls_loss=str(net.cls_loss), cls_loss_alpha=net.cls_loss_alpha, cls_loss_gamma=net.cls_loss_gamma,
-                          reg_max=net.reg_max, dfl_weight=net.dfl_weight)
+                          reg_max=net.reg_max, dfl_weight=net.dfl_weight, ghm=str(net.ghm), ghm_cls_bins=net.ghm_cls_bins,
+                          ghm_cls_momentum=net.ghm_cls_momentum, ghm_cls_weight=net.ghm_cls_weight,
+                          ghm_reg_bins=net.ghm_reg_bins, ghm_reg_momentum=net.ghm_reg_momentum, ghm_reg_mu=net.ghm_reg_mu,
+                          ghm_reg_weight=net.ghm_reg_weight)
     else:
         raise ValueError("unknown network.type %r" % (net.type,))
     if net.pretrained:

@@ -2,7 +2,7 @@
 on hand-written HIP kernels, same arena / graph / data-parallel machinery as Faster R-CNN."""
 import torch
 
-from ..core.loss import check_cls_loss, check_reg_loss, check_reg_max
+from ..core.loss import check_cls_loss, check_ghm, check_reg_loss, check_reg_max
 from .backbones import ResNet
 from .backbones.resnet import check_gcb
 from .necks.fpn import RetinaFPN
@@ -27,7 +27,9 @@ class RetinaNet(DetectorBase):
     def __init__(self, device="cuda", depth=101, num_classes=80, seed=7, dcn_stages=(), dcn_modulated=True, dcn_groups=1,
                  reg_loss="smooth_l1", reg_loss_weight=1.0, assigner="max_iou", atss_topk=9, anchor_ratios=(0.5, 1.0, 2.0),
                  anchor_scales_per_octave=3, anchor_scale=4.0, cls_loss="focal", cls_loss_alpha=None, cls_loss_gamma=None,
-                 reg_max=0, dfl_weight=0.25, fpn_upsample="nearest", gcb_stages=(), gcb_reduction=16):
+                 reg_max=0, dfl_weight=0.25, fpn_upsample="nearest", gcb_stages=(), gcb_reduction=16, ghm="none",
+                 ghm_cls_bins=30, ghm_cls_momentum=0.75, ghm_cls_weight=1.0, ghm_reg_bins=10, ghm_reg_momentum=0.7,
+                 ghm_reg_mu=0.02, ghm_reg_weight=10.0):
         """dcn_stages / dcn_modulated / dcn_groups: deformable conv2 in those backbone stages (backbones.ResNet).
         gcb_stages / gcb_reduction: a global context block (GCNet) with inner width C / gcb_reduction in every bottleneck of
         those backbone stages (backbones.ResNet); the blocks draw from a generator of their own.
@@ -42,6 +44,10 @@ class RetinaNet(DetectorBase):
         4 * (reg_max + 1) logits per anchor, the box is their integral decode (training and predict), the loss gains a third
         component dfl_weight * DFL (rpn_heads.RetinaHead; needs an IoU-family reg_loss). As published: 16, 0.25 with ATSS,
         qfl and reg_loss_weight 2. The layout of retina.box_out depends on it; load_checkpoint refuses the other layout.
+        ghm / ghm_*: 'cls' / 'reg' / 'both' = gradient harmonizing (GHM-C / GHM-R, Li et al. 2019) in place of the focal and / or
+        the smooth-L1 term (rpn_heads.RetinaHead; core.loss.check_ghm). The defaults are the published settings. The
+        histograms' moving average is device state of the head, per rank; it is not part of a checkpoint (head.ghm_reset()
+        zeroes it) and the parameter layout does not depend on ghm.
         fpn_upsample: 'nearest' only -- CARAFE is an option of the R-CNN models' FPN (necks.FPN), not of RetinaFPN."""
         if fpn_upsample != "nearest":
             raise ValueError("fpn_upsample = %r: RetinaNet's pyramid (RetinaFPN) upsamples nearest-neighbour only; CARAFE is "
@@ -51,6 +57,10 @@ class RetinaNet(DetectorBase):
         check_reg_max(reg_max, reg_loss, dfl_weight)
         check_cls_loss(cls_loss, reg_loss, cls_loss_alpha, cls_loss_gamma)
         check_assigner(assigner, atss_topk)
+        ghm_kw = dict(ghm_cls_bins=ghm_cls_bins, ghm_cls_momentum=ghm_cls_momentum, ghm_cls_weight=ghm_cls_weight,
+                      ghm_reg_bins=ghm_reg_bins, ghm_reg_momentum=ghm_reg_momentum, ghm_reg_mu=ghm_reg_mu,
+                      ghm_reg_weight=ghm_reg_weight)
+        check_ghm(ghm, cls_loss, reg_loss, reg_max, cls_loss_alpha, cls_loss_gamma, **{k[4:]: v for k, v in ghm_kw.items()})
         ratios, octave_scales = check_anchor_setting(anchor_ratios, anchor_scales_per_octave, anchor_scale)
         gen = torch.Generator().manual_seed(seed)
         self._init_base(device)
@@ -59,7 +69,7 @@ class RetinaNet(DetectorBase):
                                ratios=ratios, octave_scales=octave_scales, anchor_scale=float(anchor_scale),
                                reg_loss=reg_loss, reg_loss_weight=reg_loss_weight, assigner=assigner, atss_topk=atss_topk,
                                cls_loss=cls_loss, cls_loss_alpha=cls_loss_alpha, cls_loss_gamma=cls_loss_gamma,
-                               reg_max=reg_max, dfl_weight=dfl_weight)
+                               reg_max=reg_max, dfl_weight=dfl_weight, ghm=ghm, **ghm_kw)
         self.mark_head = self.arena.size
         self.neck = RetinaFPN([512, 1024, 2048], 256, self.arena, self.ws, device, gen)
         self.mark_fpn = self.arena.size
@@ -83,6 +93,18 @@ class RetinaNet(DetectorBase):
         self.dP = [torch.empty(s, dtype=torch.bfloat16, device=dev) for s in p_shapes]
         self.dC = [None] + [torch.empty(s, dtype=torch.bfloat16, device=dev) for s in c_shapes[1:]]
         self.planned = key
+
+    def ghm_reset(self):
+        """Zero the head's gradient-norm moving average (ghm != 'none'; outside any captured graph)."""
+        self.head.ghm_reset()
+
+    # The eager warm-up steps of capture() DO run the weights kernel, so they move the head's GHM moving average like any
+    # training step; DetectorBase._weights_restored puts it back with the parameters, so replay(step=0) stays the first step.
+    def _step_state(self):
+        return self.head.ghm_state()
+
+    def _set_step_state(self, state):
+        self.head.ghm_set_state(state)
 
     def predict(self, image, im_info, score_thresh=0.05, nms_thresh=0.5, max_per_image=100, pre_nms_top_n=1000,
                 nms_method="hard", soft_sigma=0.5):

@@ -31,7 +31,8 @@ class RetinaHead:
                  octave_scales=(1.0, 2.0 ** (1.0 / 3.0), 2.0 ** (2.0 / 3.0)), anchor_scale=4.0, fg_thresh=0.5,
                  bg_thresh=0.4, alpha=0.25, gamma=2.0, sigma=3.0, prior=0.01, reg_loss="smooth_l1", reg_loss_weight=1.0,
                  assigner="max_iou", atss_topk=9, cls_loss="focal", cls_loss_alpha=None, cls_loss_gamma=None, reg_max=0,
-                 dfl_weight=0.25):
+                 dfl_weight=0.25, ghm="none", ghm_cls_bins=30, ghm_cls_momentum=0.75, ghm_cls_weight=1.0, ghm_reg_bins=10,
+                 ghm_reg_momentum=0.7, ghm_reg_mu=0.02, ghm_reg_weight=10.0):
         """assigner: 'max_iou' (fg_thresh / bg_thresh) or 'atss' (the atss_topk nearest anchors per level and GT).
         reg_loss: 'smooth_l1' on the encoded deltas (core.loss.retina_loss_level), or 'iou' / 'giou' / 'diou' on the
         decoded box times reg_loss_weight (core.loss.retina_loss_level_iou; stds 1, as the inference decode).
@@ -41,7 +42,14 @@ class RetinaHead:
         alpha = 0.75, gamma = 2); with 'focal' they replace alpha / gamma when given.
         reg_max / dfl_weight: reg_max > 0 makes the box branch a distribution head (GFL, Li et al. 2020): 4 * (reg_max + 1)
         logits per anchor, the box their integral decode, reg_loss on that box plus dfl_weight * DFL, any cls_loss
-        (core.loss.retina_loss_level_dfl; needs an IoU-family reg_loss). reg_max = 0: the plain deltas, today's calls."""
+        (core.loss.retina_loss_level_dfl; needs an IoU-family reg_loss). reg_max = 0: the plain deltas, today's calls.
+        ghm / ghm_*: 'cls', 'reg' or 'both' harmonize the class and / or the box term by the step's gradient-norm histogram
+        (GHM, Li et al. 2019; core.loss.check_ghm: needs cls_loss 'focal' without alpha / gamma, reg_loss 'smooth_l1',
+        reg_max 0). The histograms and their moving average (ghm_acc, zeroed by ghm_reset) live on the device, per rank, and
+        are no parameters. 'none': today's calls."""
+        self.ghm = ghm
+        self.ghm_cfg = L_.check_ghm(ghm, cls_loss, reg_loss, reg_max, cls_loss_alpha, cls_loss_gamma, ghm_cls_bins,
+                                    ghm_cls_momentum, ghm_cls_weight, ghm_reg_bins, ghm_reg_momentum, ghm_reg_mu, ghm_reg_weight)
         L_.check_reg_loss(reg_loss, reg_loss_weight)
         check_assigner(assigner, atss_topk)
         L_.check_reg_max(reg_max, reg_loss, dfl_weight)
@@ -108,6 +116,55 @@ class RetinaHead:
         self.nparts = [L_.retina_loss_num_partials(N, H, W, self.A) for (H, W) in self.level_shapes]
         self.partial = torch.zeros((self.ncomp * sum(self.nparts),), dtype=torch.float32, device=dev)
         self.loss = torch.zeros((self.ncomp,), dtype=torch.float32, device=dev)
+        if self.ghm != "none":        # one row of counts per workgroup of the step; the moving average survives a re-plan
+            nb = self.ghm_cfg["cls_bins"] + self.ghm_cfg["reg_bins"]
+            self.ghm_counts = torch.zeros((sum(self.nparts), nb), dtype=torch.int32, device=dev)
+            self.ghm_cnt = torch.zeros((nb,), dtype=torch.int32, device=dev)
+            self.ghm_coef = torch.zeros((nb,), dtype=torch.float32, device=dev)
+            if getattr(self, "ghm_acc", None) is None:
+                self.ghm_acc = torch.zeros((nb,), dtype=torch.float32, device=dev)
+
+    def ghm_reset(self):
+        """Zero the moving average of the gradient-norm histograms (a memset; call it outside any captured graph)."""
+        if getattr(self, "ghm_acc", None) is not None:
+            self.ghm_acc.zero_()
+
+    def ghm_state(self):
+        """A copy of the moving average, or None while there is none (ghm 'none', or not planned yet: a zero state)."""
+        acc = getattr(self, "ghm_acc", None)
+        return None if acc is None else acc.clone()
+
+    def ghm_set_state(self, state):
+        """Put back what ghm_state returned (None: zero). Outside any captured graph."""
+        if getattr(self, "ghm_acc", None) is not None:
+            if state is None:
+                self.ghm_acc.zero_()
+            else:
+                self.ghm_acc.copy_(state)
+
+    def _ghm_loss_and_grad(self, targets, loss_scale):
+        """Histogram passes over all levels, the weights kernel, then the loss passes: one histogram per term and step."""
+        g = self.ghm_cfg
+        off = 0
+        for l in range(len(self.co)):
+            L_.ghm_hist_level(self.co[l], self.bo[l], self.A, self.Cn, self.cls_labels, targets, self.level_offsets[l], self.ghm,
+                              g["cls_bins"], g["reg_bins"], g["reg_mu"], self.ghm_counts[off:])
+            off += self.nparts[l]
+        L_.ghm_weights(self.ghm_counts, off, g["cls_bins"], g["reg_bins"], g["cls_momentum"], g["reg_momentum"], self.ghm_acc,
+                       self.ghm_cnt, self.ghm_coef)
+        off = 0
+        for l in range(len(self.co)):
+            gc = self._buf("gco%d" % l, self.co[l].shape, zero=True)     # padding channels stay zero
+            gb = self._buf("gbo%d" % l, self.bo[l].shape, zero=True)
+            L_.retina_loss_level_ghm(self.co[l], self.bo[l], self.A, self.Cn, self.cls_labels, targets, self.level_offsets[l],
+                                     self.ghm, self.alpha, self.gamma, self.sigma, self.ghm_coef, g["cls_bins"], g["reg_bins"],
+                                     g["cls_weight"], g["reg_mu"], g["reg_weight"], self.num_fg, loss_scale, gc, gb,
+                                     self.partial[2 * off:])
+            off += self.nparts[l]
+            self.gco.append(gc)
+            self.gbo.append(gb)
+        L_.loss_finalize(self.partial, off, self.ncomp, self.loss)
+        return self.loss
 
     def forward(self, P):
         """Layer i of BOTH towers on ALL levels is one grouped launch (10 independent convolutions): 5 launches for the
@@ -142,6 +199,8 @@ class RetinaHead:
         L_.anchor_class_labels(labels, matched, gt_boxes, self.cls_labels, self.num_fg)
         self.matched = matched
         self.gco, self.gbo = [], []
+        if self.ghm != "none":
+            return self._ghm_loss_and_grad(targets, loss_scale)
         off = 0
         for l in range(len(self.co)):
             gc = self._buf("gco%d" % l, self.co[l].shape, zero=True)     # padding channels stay zero

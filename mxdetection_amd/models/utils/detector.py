@@ -241,17 +241,26 @@ class DetectorBase(CheckpointMixin):
 
     @contextlib.contextmanager
     def _weights_restored(self):
-        """Eager steps run in the body plan shapes and allocate buffers only: parameters, momentum and the bf16 /
-        transposed working copies are put back afterwards."""
-        snap = (self.arena.w.clone(), self.arena.m.clone())
+        """Eager steps run in the body plan shapes and allocate buffers only: parameters, momentum, the bf16 /
+        transposed working copies and a model's other step state (_step_state) are put back afterwards."""
+        snap = (self.arena.w.clone(), self.arena.m.clone(), self._step_state())
         yield
         torch.cuda.synchronize()
         self.arena.w.copy_(snap[0])
         self.arena.m.copy_(snap[1])
+        self._set_step_state(snap[2])
         self.arena.refresh_bf16()
         self.refresh_transposed()
         del snap
         torch.cuda.synchronize()
+
+    def _step_state(self):
+        """Device state outside the arena that a training step mutates (none here; RetinaNet: the GHM moving average).
+        _weights_restored hands what this returns back to _set_step_state."""
+        return None
+
+    def _set_step_state(self, state):
+        pass
 
     def capture(self, image, gt_boxes, im_info, lr, image_offset=0, warmup=2, gt_masks=None, momentum=0.9, wd=1e-4,
                 gt_keypoints=None):

@@ -56,6 +56,14 @@ DEFAULTS = {
         "cls_loss_gamma": None,           # null = the kind's published setting (focal 2, qfl beta = 2, vfl 2)
         "reg_max": 0,                     # retinanet box branch: 0 = deltas (dx, dy, dw, dh); R > 0 = each side a distribution over 0..R strides, integral decode + DFL (Li et al. 2020; published 16; needs an IoU-family reg_loss)
         "dfl_weight": 0.25,               # weight of the Distribution Focal Loss (reg_max > 0)
+        "ghm": "none",                    # retinanet: none | cls | reg | both -- gradient harmonizing (GHM-C / GHM-R; Li et al. 2019) in place of the focal / smooth-L1 term; needs cls_loss focal without alpha / gamma, reg_loss smooth_l1, reg_max 0
+        "ghm_cls_bins": 30,               # GHM-C: gradient-norm bins (1..64) ...
+        "ghm_cls_momentum": 0.75,         # ... moving average of the bin counts, in [0, 1); 0 = the step's own counts ...
+        "ghm_cls_weight": 1.0,            # ... weight of the term, as published
+        "ghm_reg_bins": 10,               # GHM-R: bins (1..64) ...
+        "ghm_reg_momentum": 0.7,          # ... momentum ...
+        "ghm_reg_mu": 0.02,               # ... mu of the authentic smooth-L1 sqrt(d^2 + mu^2) - mu ...
+        "ghm_reg_weight": 10.0,           # ... weight of the term, as published
         "assigner": "max_iou",            # retinanet targets: max_iou (thresholds 0.5 / 0.4) | atss (Zhang et al. 2020). The RPN keeps its sampler
         "atss_topk": 9,                   # ATSS: candidates per ground-truth box and pyramid level (1..16)
         "anchor_ratios": [0.5, 1.0, 2.0],  # retinanet anchors per cell: these h/w ratios ...
