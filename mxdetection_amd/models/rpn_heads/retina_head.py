@@ -47,6 +47,9 @@ class RetinaHead:
         (GHM, Li et al. 2019; core.loss.check_ghm: needs cls_loss 'focal' without alpha / gamma, reg_loss 'smooth_l1',
         reg_max 0). The histograms and their moving average (ghm_acc, zeroed by ghm_reset) live on the device, per rank, and
         are no parameters. 'none': today's calls."""
+        if isinstance(num_convs, bool) or not isinstance(num_convs, int) or num_convs < 1:
+            # without a tower layer backward() would mask cls_out's data gradient by P > 0 and never write dP
+            raise ValueError("num_convs = %r: expected an integer >= 1" % (num_convs,))
         self.ghm = ghm
         self.ghm_cfg = L_.check_ghm(ghm, cls_loss, reg_loss, reg_max, cls_loss_alpha, cls_loss_gamma, ghm_cls_bins,
                                     ghm_cls_momentum, ghm_cls_weight, ghm_reg_bins, ghm_reg_momentum, ghm_reg_mu, ghm_reg_weight)

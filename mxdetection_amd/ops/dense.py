@@ -187,7 +187,10 @@ GROUP_HINTS = {}
 
 def conv2d_group(kind, calls, device):
     """Run `calls` (see GroupedConv) as one grouped launch; plans are cached by the tensors' addresses. Under stream
-    capture an unseen group cannot upload its table: it falls back to one launch per call (same results)."""
+    capture an unseen group cannot upload its table: it falls back to one launch per call (same results). An empty
+    list is no launch (the RPN head groups the levels after the first: none on a one-level pyramid)."""
+    if not calls:
+        return
     key = (kind,) + tuple(tuple(t.data_ptr() if torch.is_tensor(t) else t for t in c) for c in calls)
     if PF_TRACE is not None and calls:
         PF_TRACE.append((None, "g", mem_range(*[c[1] for c in calls]), key if len(calls) > 1 else None))
