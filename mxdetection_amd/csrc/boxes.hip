@@ -138,11 +138,7 @@ nms_scan_kernel(const unsigned long long* __restrict__ mask, const int32_t* __re
   }
   // exclusive scan of popcounts over lanes, then ordered emission
   int cnt = __popcll(mykeep);
-  int incl = cnt;
-  for (int off = 1; off < 64; off <<= 1) {
-    int v = __shfl_up(incl, off);
-    if (lane >= off) incl += v;
-  }
+  int incl = wave_incl_scan(cnt, lane);
   int excl = incl - cnt;
   int total = __shfl(incl, 63);
   unsigned long long kb = mykeep;
@@ -251,11 +247,7 @@ nms_scan_rows_kernel(const unsigned long long* __restrict__ mask, const int32_t*
     buf ^= 1;
   }
   int cnt = __popcll(mykeep);
-  int incl = cnt;
-  for (int off = 1; off < 64; off <<= 1) {
-    int v = __shfl_up(incl, off);
-    if (lane >= off) incl += v;
-  }
+  int incl = wave_incl_scan(cnt, lane);
   int excl = incl - cnt;
   int total = __shfl(incl, 63);
   unsigned long long kb = mykeep;

@@ -164,34 +164,7 @@ __device__ __forceinline__ void store_from_f32(void* p, int64_t i, int dtype, fl
     ((float*)p)[i] = v;
 }
 
-// wave-level inclusive/exclusive helpers (wave = 64)
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
-
-__device__ __forceinline__ int wave_excl_count(bool pred, int* total) {
-  unsigned long long m = __ballot(pred);
-  int lane = lane_id();
-  unsigned long long below = (lane == 0) ? 0ull : (m & (~0ull >> (64 - lane)));
-  *total = __popcll(m);
-  return __popcll(below);
-}
-
-// Block-wide exclusive prefix count of a predicate in thread order; returns this thread's rank and
-// the block total. `scratch` must hold (blockDim.x/64 + 1) ints. Contains __syncthreads.
-__device__ inline int block_excl_count(bool pred, int* scratch, int* total) {
-  int wtot;
-  int r = wave_excl_count(pred, &wtot);
-  int wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();  // protect scratch reuse
-  if (lane_id() == 0) scratch[wid] = wtot;
-  __syncthreads();
-  int base = 0, all = 0;
-  for (int i = 0; i < nw; ++i) {
-    int v = scratch[i];
-    if (i < wid) base += v;
-    all += v;
-  }
-  *total = all;
-  return base + r;
-}
-
 }  // namespace mxdet
+
+// wave / block reduce and scan primitives (lane_id, wave_sum, block4_reduce, block_excl_count, ...)
+#include "wave.h"

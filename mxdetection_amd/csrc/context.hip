@@ -11,7 +11,7 @@
 // A dot over C is the lane's fma chain (vector order, then element order), then a 64-lane butterfly; a per-chunk sum is each
 // wave's chain over its positions in order, then the four waves in wave order through LDS; the chunks of an image are folded
 // by the small kernel behind (transform_fwd, transform_bwd, the d_wk fold) in runs whose bounds depend on the shape alone
-// (gc_fold_chunks, gc_block_sum, gc_fold_wk_kernel). Rows past HW and vectors past C / 8 are
+// (gc_fold_chunks, block4_reduce of wave.h, gc_fold_wk_kernel). Rows past HW and vectors past C / 8 are
 // predicates: no address outside a tensor is formed.
 #include <initializer_list>
 
@@ -54,12 +54,6 @@ static size_t gc_layout(const mxdet_gc_desc_t* d, GcK* k, void* base) {
   float* sp = take(N * K);
   if (k) { k->ms = ms; k->part = part; k->u = u; k->gz = gz; k->dh = dh; k->e = e; k->sp = sp; }
   return off;
-}
-
-__device__ __forceinline__ float gc_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;                              // a butterfly: the same bits in every lane
 }
 
 // eight fp32 of a row -> registers; eight bf16 likewise (zeros past the row's end)
@@ -141,7 +135,7 @@ gc_pool_fwd_kernel(const GcK k, const uint4* __restrict__ t, const uint4* __rest
 #pragma unroll
         for (int j = 0; j < 8; ++j) dot += x[i][j] * w[i][j];
       }
-      dot = gc_wave_sum(dot);
+      dot = wave_sum(dot);
       if (c.lane == 0) logits[(long long)c.n * k.HW + pp] = dot;
       const float mn = fmaxf(m, dot), f = __expf(m - mn), pe = __expf(dot - mn);
       s = s * f + pe;
@@ -167,23 +161,6 @@ gc_pool_fwd_kernel(const GcK k, const uint4* __restrict__ t, const uint4* __rest
     k.ms[2 * (size_t)blockIdx.x + 1] = S;
   }
   gc_merge_columns<NV>(k, s_acc, acc, c, s_f);
-}
-
-// The same bits in every thread: a 64-lane butterfly, then the four waves in wave order. s4: kGcWaves floats of LDS.
-__device__ __forceinline__ float gc_block_sum(float v, float* s4) {
-  v = gc_wave_sum(v);
-  __syncthreads();                       // s4 may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((s4[0] + s4[1]) + s4[2]) + s4[3];
-}
-__device__ __forceinline__ float gc_block_max(float v, float* s4) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(s4[0], s4[1]), fmaxf(s4[2], s4[3]));
 }
 
 // Fold the K chunk partials of image n into s_part[w][c]: wave w takes the chunks [w Kq, (w + 1) Kq), Kq = ceil(K / 4), in
@@ -237,10 +214,10 @@ gc_transform_fwd_kernel(const GcK k, const uint4* __restrict__ W1, const float* 
   // maximum and sum over the chunks: thread t the chunks t, t + 256, ... in order, then the block fold
   float M = kGcLowest;
   for (int q = tid; q < k.K; q += kGcThreads) M = fmaxf(M, ms[2 * q]);
-  M = gc_block_max(M, s_4);
+  M = block4_reduce<FMax, kEveryLane, kScratchReused>(M, s_4);
   float S = 0.f;
   for (int q = tid; q < k.K; q += kGcThreads) S += ms[2 * q + 1] * __expf(ms[2 * q] - M);
-  S = gc_block_sum(S, s_4);
+  S = block4_reduce<Sum, kEveryLane, kScratchReused>(S, s_4);
   if (tid == 0) lse[n] = M + logf(S);
   const float inv = 1.0f / S;
   gc_fold_chunks<true>(k, n, M, s_part);
@@ -272,7 +249,7 @@ gc_transform_fwd_kernel(const GcK k, const uint4* __restrict__ W1, const float* 
 #pragma unroll
         for (int j = 0; j < 8; ++j) dot += x[j] * s_ctx[8 * v + j];
       }
-      dot = gc_wave_sum(dot);
+      dot = wave_sum(dot);
       if (lane == 0 && j0 + r < k.P) {
         const float v = dot + b1[j0 + r];
         s_h[j0 + r] = v;
@@ -544,7 +521,7 @@ gc_pool_bwd_e_kernel(const GcK k, const uint4* __restrict__ t, const float* __re
 #pragma unroll
         for (int j = 0; j < 8; ++j) dot += x[j] * w[i][j];
       }
-      dot = gc_wave_sum(dot);
+      dot = wave_sum(dot);
       const long long o = (long long)c.n * k.HW + pp;
       if (c.lane == 0) k.e[o] = dot;
       s += __expf(logits[o] - L) * dot;
@@ -577,7 +554,7 @@ gc_pool_bwd_dt_kernel(const GcK k, const uint4* __restrict__ t, const uint4* __r
   // S[n]: thread t adds the chunks t, t + 256, ... in order, then the block fold (the same bits in every workgroup)
   float S = 0.f;
   for (int q = (int)threadIdx.x; q < k.K; q += kGcThreads) S += k.sp[(size_t)c.n * k.K + q];
-  S = gc_block_sum(S, s_4);
+  S = block4_reduce<Sum, kEveryLane, kScratchReused>(S, s_4);
   for (int p = c.p0 + c.wave; p < c.p1; p += kGcWaves * UN) {
     uint4 rt[UN][NV], rg[UN][NV];
 #pragma unroll

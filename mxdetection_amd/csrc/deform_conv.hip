@@ -217,28 +217,6 @@ deform_index_kernel(DeformArgs a, int mode, const uint16_t* __restrict__ off, in
   }
 }
 
-// block-wide exclusive prefix sum (ints) in thread order; sh holds blockDim.x / 64 ints. Contains __syncthreads.
-__device__ __forceinline__ int block_scan_excl(int v, int* sh, int* total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) sh[wid] = incl;
-  __syncthreads();
-  int base = 0, all = 0;
-  for (int i = 0; i < nw; ++i) {
-    const int s = sh[i];
-    if (i < wid) base += s;
-    all += s;
-  }
-  __syncthreads();
-  *total = all;
-  return base + incl - v;
-}
-
 // scan pass 1: per-block sums of cnt
 __global__ void __launch_bounds__(kScanThreads)
 deform_scan_sums_kernel(const int* __restrict__ cnt, long long nl, int* __restrict__ bsum) {
@@ -249,7 +227,7 @@ deform_scan_sums_kernel(const int* __restrict__ cnt, long long nl, int* __restri
   for (int i = 0; i < kScanPerThread; ++i)
     if (b0 + i < nl) s += cnt[b0 + i];
   int tot;
-  block_scan_excl(s, sh, &tot);
+  block_excl_scan(s, sh, &tot);
   if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
@@ -262,7 +240,7 @@ deform_scan_blocks_kernel(int* __restrict__ bsum, int nb, long long nl, int* __r
     const int i = b + threadIdx.x;
     const int v = i < nb ? bsum[i] : 0;
     int tot;
-    const int ex = block_scan_excl(v, sh, &tot);
+    const int ex = block_excl_scan(v, sh, &tot);
     if (i < nb) bsum[i] = carry + ex;
     carry += tot;
   }
@@ -281,7 +259,7 @@ deform_scan_apply_kernel(const int* __restrict__ cnt, long long nl, const int* _
     s += v[i];
   }
   int tot;
-  int run = bsum[blockIdx.x] + block_scan_excl(s, sh, &tot);
+  int run = bsum[blockIdx.x] + block_excl_scan(s, sh, &tot);
 #pragma unroll
   for (int i = 0; i < kScanPerThread; ++i) {
     if (b0 + i < nl) start[b0 + i] = run;

@@ -198,12 +198,7 @@ dpool_bwd_trans_kernel(DPoolArgs a, long long R, const float* __restrict__ rois,
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    gx = gx + __shfl_xor(gx, o, 64);
-    gy = gy + __shfl_xor(gy, o, 64);
-    gm = gm + __shfl_xor(gm, o, 64);
-  }
+  wave_reduce_each<Sum>(gx, gy, gm);
   uint16_t* tr = d_trans + r * a.ts;
   uint16_t* mr = a.mod ? d_mask + r * a.ms : nullptr;
   if (lane == 0) {
@@ -276,13 +271,8 @@ dpool_prepare_kernel(DPoolArgs a, long long R, const float* __restrict__ rois, c
     e.pad0 = e.pad1 = e.pad2 = 0;
     bin[r * a.NB + lane] = e;
   }
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    int t = __shfl_xor(ylo, d); ylo = t < ylo ? t : ylo;
-    t = __shfl_xor(yhi, d); yhi = t > yhi ? t : yhi;
-    t = __shfl_xor(xlo, d); xlo = t < xlo ? t : xlo;
-    t = __shfl_xor(xhi, d); xhi = t > xhi ? t : xhi;
-  }
+  wave_reduce_each<MinSel, 64, kAscend>(ylo, xlo);
+  wave_reduce_each<MaxSel, 64, kAscend>(yhi, xhi);
   if (lane == 0) {
     DpRoiRec o;
     const bool any = yhi >= 0;

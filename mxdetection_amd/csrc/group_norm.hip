@@ -393,11 +393,7 @@ __global__ void __launch_bounds__(kGnBlock) gn_merge_sums_kernel(GnGeom a, const
     s1 += o[0];
     s2 += o[1];
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    s1 += __shfl_down(s1, off);
-    s2 += __shfl_down(s2, off);
-  }
+  wave_reduce_each<Sum, 64, kDescend, kLane0>(s1, s2);
   if (lane == 0) {
     gsum[(long long)wave * 2] = s1;
     gsum[(long long)wave * 2 + 1] = s2;

@@ -62,7 +62,7 @@ __device__ __forceinline__ float kp_up(const uint16_t* ch, int S_in, int Y, int 
 // block-wide max / fixed-order sum over the loss workgroup's 16 waves (red: 16 floats, 16-byte aligned, read back as four
 // 16-byte loads); every thread gets the result. Contain __syncthreads.
 __device__ __forceinline__ float kp_block_max(float v, float* red) {
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  v = wave_reduce<FMax>(v);
   __syncthreads();   // protect reuse of red
   if (lane_id() == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -71,7 +71,7 @@ __device__ __forceinline__ float kp_block_max(float v, float* red) {
                fmaxf(fmaxf(fmaxf(c.x, c.y), fmaxf(c.z, c.w)), fmaxf(fmaxf(d.x, d.y), fmaxf(d.z, d.w))));
 }
 __device__ __forceinline__ float kp_block_sum(float v, float* red) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+  v = wave_sum_lane0(v);
   __syncthreads();
   if (lane_id() == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -118,10 +118,8 @@ keypoint_count_kernel(const int32_t* __restrict__ targets, long long total, int 
     const int t = targets[i];
     cnt += (t >= 0 && t < SS);
   }
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
-  if (lane_id() == 0) red[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) n_valid[0] = red[0] + red[1] + red[2] + red[3];
+  cnt = block4_reduce<Sum, kLane0, kScratchOnce>(cnt, red);
+  if (threadIdx.x == 0) n_valid[0] = cnt;
 }
 
 // ---- loss + gradient: one workgroup per roi -------------------------------------------------------------------------------
@@ -261,13 +259,11 @@ keypoint_loss_final_kernel(const float* __restrict__ partial, const int* __restr
   }
   float l = 0.0f;
   for (int r = threadIdx.x; r < R; r += 256) l = l + partial[r];   // rows in ascending order per lane
-  for (int off = 32; off > 0; off >>= 1) l += __shfl_down(l, off);
-  if (lane_id() == 0) redf[threadIdx.x >> 6] = l;
-  __syncthreads();
+  l = block4_reduce<Sum, kLane0, kScratchOnce>(l, redf);
   if (threadIdx.x == 0) {
     const int nv = n_valid[0];
     const float k = scale / (float)(nv > 1 ? nv : 1);
-    loss_out[0] = k * (((redf[0] + redf[1]) + redf[2]) + redf[3]);
+    loss_out[0] = k * l;
   }
 }
 

@@ -11,7 +11,7 @@ namespace mxdet {
 
 // deterministic block sum: fixed shuffle tree inside each wave, then wave partials added in order
 __device__ inline float block_sum_fixed(float v, float* smem /* >= blockDim/64 floats */) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+  v = wave_sum_lane0(v);
   int wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
   __syncthreads();
   if (lane_id() == 0) smem[wid] = v;
@@ -359,14 +359,11 @@ __device__ __forceinline__ float rcnn_softmax_ce(const void* __restrict__ cls, i
     float z = load_as_f32(cls, r * ld_cls + c, dtype);
     mx = z > mx ? z : mx;
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    float o = __shfl_xor(mx, off);
-    mx = o > mx ? o : mx;
-  }
+  mx = wave_reduce<MaxSel>(mx);
   float se = 0.0f;
   for (int c = lane; c < num_classes; c += 64)
     se += mxdet_expf(load_as_f32(cls, r * ld_cls + c, dtype) - mx);
-  for (int off = 32; off > 0; off >>= 1) se += __shfl_xor(se, off);
+  se = wave_sum(se);
   float lse = mxdet_logf(se);
   float lcls = 0.0f;
   for (int c = lane; c < num_classes; c += 64) {
@@ -381,8 +378,7 @@ __device__ __forceinline__ float rcnn_softmax_ce(const void* __restrict__ cls, i
     }
     if (kGrad) store_from_f32(gcls, r * ld_cls + c, dtype, g);
   }
-  for (int off = 32; off > 0; off >>= 1) lcls += __shfl_xor(lcls, off);
-  return lcls;
+  return wave_sum(lcls);
 }
 
 // Balanced L1 (Pang et al., CVPR 2019) of one weighted difference d, a = |d|:
@@ -450,9 +446,7 @@ __device__ __forceinline__ float rcnn_reg_elem(const void* __restrict__ reg, int
     }
     if (kGrad) store_from_f32(greg, r * ld_reg + c, dtype, g);
   }
-  // fixed xor tree: every lane ends with the same value
-  for (int off = 32; off > 0; off >>= 1) lreg += __shfl_xor(lreg, off);
-  return lreg;
+  return wave_sum(lreg);   // every lane ends with the same value
 }
 // smooth-L1 (the name ohem.hip scores rows with)
 template <bool kGrad>

@@ -136,11 +136,8 @@ mask_loss_kernel(const uint16_t* __restrict__ logits, const int32_t* __restrict_
     }
     *(uint4*)(grad + pix * Cpad + ck * 8) = o;
   }
-  for (int off = 32; off > 0; off >>= 1) l += __shfl_down(l, off);
-  int wid = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) red[wid] = l;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (((red[0] + red[1]) + red[2]) + red[3]) * norm;
+  l = block4_reduce<Sum, kLane0, kScratchOnce>(l, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = l * norm;
 }
 
 __global__ void count_pos_kernel(const int32_t* __restrict__ cls, int R, int* __restrict__ out) {
@@ -155,10 +152,8 @@ mask_finalize_kernel(const float* __restrict__ partial, int count, float* __rest
   __shared__ float red[4];
   float acc = 0.0f;
   for (int i = threadIdx.x; i < count; i += blockDim.x) acc += partial[i];
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = ((red[0] + red[1]) + red[2]) + red[3];
+  acc = block4_reduce<Sum, kLane0, kScratchOnce>(acc, red);
+  if (threadIdx.x == 0) out[0] = acc;
 }
 
 // ---- mask paste-back (inference): class channel -> probability map -> bilinear resize into the detection box -> threshold

@@ -12,21 +12,6 @@ namespace mxdet {
 
 constexpr int kAreaChunks = 16;   // workgroups per instance of the whole-instance area pass (partials, summed in order)
 
-// sum over the wave (64 lanes on gfx950): lane 0 holds the total
-__device__ __forceinline__ int wave_sum_i32(int v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-  return v;
-}
-
-// block-wide integer sum (256 threads = 4 waves); every thread gets the total. Contains __syncthreads.
-__device__ __forceinline__ int block_sum_i32(int v, int* red) {
-  v = wave_sum_i32(v);
-  __syncthreads();   // protect reuse of red
-  if (lane_id() == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
 __device__ __forceinline__ int nonzero_bytes(unsigned w) {
   // one bit per non-zero byte: (b | b>>1 | ... ) folded into bit 0 of each byte
   w |= w >> 4; w |= w >> 2; w |= w >> 1;
@@ -67,7 +52,7 @@ maskiou_area_kernel(const uint8_t* __restrict__ gt_masks, const float* __restric
     const long long hi = lo + per < HW ? lo + per : HW;
     int cnt = 0;
     if (lo < hi) cnt = count_span(gt_masks + (long long)inst * HW + lo, hi - lo, threadIdx.x, 256);
-    total = block_sum_i32(cnt, red);
+    total = block4_reduce<Sum, kLane0, kScratchReused>(cnt, red);
   }
   if (threadIdx.x == 0) partial[inst * kAreaChunks + chunk] = total;
 }
@@ -113,10 +98,10 @@ maskiou_target_kernel(const float* __restrict__ rois, const int32_t* __restrict_
     const int t = tg[i] != 0;
     cnt_pred += p; cnt_tgt += t; cnt_ovr += p & t;
   }
-  const int a_in = block_sum_i32(cnt_in, red);
-  const int a_pred = block_sum_i32(cnt_pred, red);
-  const int a_tgt = block_sum_i32(cnt_tgt, red);
-  const int a_ovr = block_sum_i32(cnt_ovr, red);
+  const int a_in = block4_reduce<Sum, kLane0, kScratchReused>(cnt_in, red);
+  const int a_pred = block4_reduce<Sum, kLane0, kScratchReused>(cnt_pred, red);
+  const int a_tgt = block4_reduce<Sum, kLane0, kScratchReused>(cnt_tgt, red);
+  const int a_ovr = block4_reduce<Sum, kLane0, kScratchReused>(cnt_ovr, red);
   if (threadIdx.x == 0) {
     int a_full = 0;
     for (int k = 0; k < kAreaChunks; ++k) a_full += partial[inst * kAreaChunks + k];
@@ -188,7 +173,7 @@ maskiou_loss_kernel(const uint16_t* __restrict__ pred, const int32_t* __restrict
     const int c = cls[r];
     np += (c > 0 && c <= ld && tgt[r] > 0.0f);
   }
-  const int n_pos = block_sum_i32(np, red);
+  const int n_pos = block4_reduce<Sum, kLane0, kScratchReused>(np, red);
   const float k = scale / (float)(n_pos > 1 ? n_pos : 1);
   float l = 0.0f;
   for (int r = threadIdx.x; r < R; r += 256) {   // rows in ascending order per lane
@@ -199,10 +184,8 @@ maskiou_loss_kernel(const uint16_t* __restrict__ pred, const int32_t* __restrict
       l += 0.5f * (d * d);
     }
   }
-  for (int off = 32; off > 0; off >>= 1) l += __shfl_down(l, off);
-  if (lane_id() == 0) redf[threadIdx.x >> 6] = l;
-  __syncthreads();
-  if (threadIdx.x == 0) loss_out[0] = k * (((redf[0] + redf[1]) + redf[2]) + redf[3]);
+  l = block4_reduce<Sum, kLane0, kScratchOnce>(l, redf);
+  if (threadIdx.x == 0) loss_out[0] = k * l;
   // the gradient, written completely: consecutive lanes on consecutive 16-byte chunks
   const int CH = ld >> 3;
   for (int it = threadIdx.x; it < R * CH; it += 256) {

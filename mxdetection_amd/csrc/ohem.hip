@@ -88,8 +88,7 @@ ohem_rank_kernel(const float* __restrict__ score, const int32_t* __restrict__ la
       }
     }
   }
-#pragma unroll
-  for (int off = 1; off < kRankLanes; off <<= 1) rank += __shfl_xor(rank, off);
+  wave_reduce_each<Sum, kRankLanes, kAscend>(rank);
   if (mine && sub == 0) {
     const float* ro = rois + (row0 + i) * 5;
     order[row0 + rank] = i;
@@ -128,7 +127,7 @@ ohem_choose_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict
   __syncthreads();
   int local = 0;
   for (int i = tid; i < P; i += nt) local += (flag[i] && labels[row0 + i] > 0) ? 1 : 0;
-  for (int off = 32; off > 0; off >>= 1) local += __shfl_xor(local, off);
+  local = wave_sum(local);
   if ((tid & 63) == 0 && local) atomicAdd(&s_nfg, local);     // integer: any order gives the same sum
   __syncthreads();
   const int nfg = s_nfg;

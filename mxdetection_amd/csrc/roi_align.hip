@@ -220,12 +220,8 @@ roi_bwd_tab_kernel(FeatPyr f, const float* __restrict__ rois, const int32_t* __r
     if (a.valid) { lo = a.lo; hi = a.hi; }
   }
   // min / max inside each 32-lane half (rows | columns)
-#pragma unroll
-  for (int d = 1; d < 32; d <<= 1) {
-    const int olo = __shfl_xor(lo, d), ohi = __shfl_xor(hi, d);
-    lo = olo < lo ? olo : lo;
-    hi = ohi > hi ? ohi : hi;
-  }
+  lo = wave_reduce<MinSel, 32, kAscend>(lo);
+  hi = wave_reduce<MaxSel, 32, kAscend>(hi);
   const int xlo = __shfl(lo, 32), xhi = __shfl(hi, 32);
   if (lane == 0) {
     t.n = g.batch; t.lvl = g.lvl;

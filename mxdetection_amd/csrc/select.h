@@ -52,12 +52,7 @@ __device__ __forceinline__ void wave_scan_bins(const unsigned* hist, int remaini
   const uint4 v = *(const uint4*)(hist + lane * 4);
   const int c[4] = {(int)v.x, (int)v.y, (int)v.z, (int)v.w};
   const int s = c[0] + c[1] + c[2] + c[3];
-  int incl = s;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    int t = __shfl_up(incl, off);
-    if (lane >= off) incl += t;
-  }
+  const int incl = wave_incl_scan(s, lane);
   const int excl = incl - s;
   *total = __shfl(incl, 63);
   // the serial rule `cum + c >= remaining && c > 0`: with remaining <= 0 it is the first non-empty bin

@@ -110,6 +110,53 @@ def test_loss_nothing_valid_and_no_rows(hip, S_in, Kpad, K):
     assert float(loss) == 0.0
 
 
+def test_loss_final_sum_order_bit_exact(hip):
+    """keypoint_loss_final_kernel's sum of the per-roi partials, bit for bit in its documented order: lane t of the one
+    256-thread workgroup adds rows t, t + 256, ... ascending; each wave folds its 64 lanes by the descending tree (lane l
+    takes lane l + 32, 16 .. 1); the four wave sums are ((w0 + w1) + w2) + w3; loss = k * sum. 300 rois (every wave
+    contributes, 44 lanes hold two rows) whose cross-entropies run from about 1e-6 to 3e3, more than 2^24 apart, so that
+    another association gives other bits (asserted on the reference). The partials are read back from the workspace."""
+    import torch
+    from mxdetection_amd.core import mask as M_
+    R, S_in, Kpad, K = 300, 2, 8, 1
+    a = np.concatenate([np.linspace(60.0, -30.0, 150), -np.geomspace(1.0, 3000.0, 150)]).astype(np.float32)
+    a = a[np.random.default_rng(5).permutation(R)]
+    logits = np.zeros((R, S_in, S_in, Kpad), np.float32)
+    logits[:, 0, 0, 0] = a                                 # target 0 = the corner, whose upsampled value is the pixel's own
+    lg, tgt = _t(logits, torch.bfloat16), _t(np.zeros((R, K), np.int32))
+    ws = M_.keypoint_loss_workspace(R, "cuda")
+    loss = torch.zeros((1,), device="cuda")
+    grad = torch.empty((R, S_in, S_in, Kpad), dtype=torch.bfloat16, device="cuda")
+    M_.keypoint_loss(lg, tgt, loss, grad, ws, LOSS_SCALE, WEIGHT)
+    torch.cuda.synchronize()
+    raw = ws.cpu().numpy()
+    nv = int(raw[:4].view(np.int32)[0])
+    p = raw[256:256 + 4 * R].view(np.float32).copy()
+    assert nv == R and np.isfinite(p).all() and p.min() > 0 and p.max() / p.min() > 2.0 ** 24
+    f32 = np.float32
+    lanes = np.zeros(256, f32)
+    for r in range(R):
+        lanes[r % 256] = f32(lanes[r % 256] + p[r])
+    waves = []
+    for w in range(4):
+        x = lanes[64 * w:64 * w + 64].copy()
+        off = 32
+        while off > 0:
+            x[:off] = x[:off] + x[off:2 * off]
+            off >>= 1
+        waves.append(x[0])
+    total = f32(f32(f32(waves[0] + waves[1]) + waves[2]) + waves[3])
+    k = f32(f32(f32(LOSS_SCALE) * f32(WEIGHT)) / f32(nv))
+    want = f32(k * total)
+    other = f32(0.0)
+    for r in range(R):
+        other = f32(other + p[r])
+    assert other.view(np.uint32) != total.view(np.uint32), "the data does not make the summation order visible"
+    got = loss.cpu().numpy()
+    print("keypoint final sum %r want %r (row-order sum %r)" % (float(got[0]), float(want), float(f32(k * other))))
+    assert got.view(np.uint32)[0] == want.view(np.uint32)
+
+
 @pytest.mark.parametrize("S_in,Kpad,K", ref.SHAPES)
 def test_decode_bit_exact(hip, S_in, Kpad, K):
     import torch
